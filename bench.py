@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: "utterances/sec end-to-end S2ST (fbank→waveform) + dag_loss fwd+bwd ms/batch".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself under torch.distributed.run with N ranks (one per
@@ -14,21 +14,30 @@ The default run (`--workload headline`) measures BOTH halves of the metric and p
      precision: fp32 acoustic model and fp32 vocoder (HIP kernels; the vocoder and the FastSpeech2 convolutions multiply fp32 operands
      split hi/lo on the fp16 matrix cores with fp32 accumulation — within 2^-22 of an fp32 convolution, waveform <= 1e-4 of the
      reference generator's).  One STEP = one batch through S2SNATGenerator.  K steps timed between barrier + synchronize on both
-     sides.  `value` = utterances/s over all ranks, `ms_per_step` = ms per batch.  `s2st_fp16_vocoder` is the same pipeline with the
-     fp16-STORAGE vocoder (narrower than the reference: 1.5e-3 off its waveform) — reported beside the headline, never as it.
-     `s2st_sustained` repeats the headline leg for 200 more batches (a longer GPU phase for the driver's utilisation sampler).
+     sides.  `value` = utterances/s over all ranks, `ms_per_step` = ms per batch.
   B. C2 (configs[1]): the DAG training hot path, B=32 per GPU, graph_len 4096, tgt_len 512, vocab 8192, TR=32, fp32:
      dag_logsoftmax_gather_inplace -> dag_loss fwd (alpha || beta) -> dag_loss bwd -> gather bwd -> dag_best_alignment.
      K passes, each phase bracketed by HIP events on the launch stream; `dag.dag_loss_fwd_bwd_ms` is the metric's second half and
-     `roofline` prices the DP forward launch against SURVEY.md §8(d)'s algorithmic bytes.  Every pass starts from FRESH logits
-     (restored from a master copy between the event brackets), and a second input set with peaked, trained-model-like scores
-     (`dag.peaked`) exercises the exactness-guard paths the random inputs never enter.
-  C. C1 (configs[0]: B=4, T=256, L=2048, V=512, TR=L-1, the reference's CPU-runnable case) on the HIP ops, next to
-     `cpu_baseline`: the reference's torch CPU path (twin in oracle/torch_port.py) MEASURED at C1 on this box's host cores
-     — thread count swept, warm-up + median, no extrapolation (rank 0, N=1 only).
+     `roofline` prices the DP forward launch against SURVEY.md §8(d)'s algorithmic bytes (HBM traffic from the committed PMC record,
+     profiles/pmc_dag_fwd.json).  Every pass starts from FRESH logits (restored from a master copy between the event brackets).
 
-Other workloads (`--workload dag|s2st|s2tt|train`) run one of the parts alone (train = C5 per-GPU step with the flat-bucket
-gradient all-reduce).
+`--full` adds every side leg to the headline line (each run of its own, none of them feeds `value` or `ms_per_step`):
+  * `s2st_sustained` repeats the headline leg for 200 more batches (a longer GPU phase for the driver's utilisation sampler);
+    `s2st_fp16_vocoder` is the same pipeline with the fp16-STORAGE vocoder (narrower than the reference: 1.5e-3 off its waveform) —
+    reported beside the headline, never as it; `s2st_vocoder_roofline` times the vocoder call alone.
+  * `dag.peaked`: a second input set with peaked, trained-model-like scores exercises the exactness-guard paths the random inputs
+    never enter; `dag.lazy_softmax` the gather's lazy mode; `roofline.traffic` observed by two rocprofv3 --pmc child passes.
+  * `dag_tr4095` / `dag_tr64`: C2 at the README's dense window and at TR=64; `c3_s2tt` / `c5_train`: short C3 and C5 legs.
+  * C1 (configs[0]: B=4, T=256, L=2048, V=512, TR=L-1, the reference's CPU-runnable case) on the HIP ops, next to
+    `cpu_baseline`: the reference's torch CPU path (twin in oracle/torch_port.py) MEASURED at C1 on this box's host cores
+    — thread count swept, warm-up + median, no extrapolation (rank 0, N=1 only).
+
+Other workloads (`--workload dag|s2st|s2tt|train`) run one of the parts alone with its whole report (train = C5 per-GPU step with the
+flat-bucket gradient all-reduce).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step of each timed part returned to its caller (rank 0's) as
+DIR/<name>.npy in float32 / float64; an array of more than DUMP_CAP elements is written as a fixed, seeded sample of its positions.
+The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +54,8 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F16_PEAK_TFLOPS = 2500.0
 MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense fp32 matrix peak
 METRIC = "utterances/sec end-to-end S2ST (fbank→waveform) + dag_loss fwd+bwd ms/batch"
+DUMP_CAP = 1 << 21             # --dump-outputs: elements per array (8 MB in fp32); larger outputs are sampled
+DUMP_LIMIT = 64 << 20          # --dump-outputs: bytes of one dump in all
 
 
 def parse():
@@ -53,8 +64,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="headline", choices=["headline", "dag", "s2tt", "s2st", "train", "plumbing"],
-                    help="headline (default) = C4 S2ST utt/s + C2 DAG ops with the DP roofline + C1 vs the CPU baseline, one JSON line; "
+                    help="headline (default) = C4 S2ST utt/s + C2 DAG ops with the DP roofline, one JSON line; "
                          "dag / s2st / s2tt / train = that part alone")
+    ap.add_argument("--full", action="store_true",
+                    help="headline: also run the side legs (sustained and fp16-vocoder S2ST, vocoder roofline, peaked / lazy DAG inputs, live PMC "
+                         "traffic, dense and TR=64 windows, C3 / C5 legs, C1 vs the CPU baseline); the other workloads always report in full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--tr", type=int, default=32, help="C2 transition window (32 = banded fast path, 4095 = README's --max-transition-length 99999)")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch of the model workloads (default 32; 64 for s2tt, BASELINE configs[2])")
     ap.add_argument("--dag-batch", type=int, default=32)
@@ -170,7 +186,8 @@ class Ctx:
 
     def timed(self, step, steps, warmup, flush=None):
         """`flush` drains a pipelined step (work of the last submitted batch still queued on the host side): called at the end of the
-        warm-up and INSIDE the timed region after the K-th step, so the K timed steps contain all the work of exactly K batches."""
+        warm-up and INSIDE the timed region after the K-th step, so the K timed steps contain all the work of exactly K batches.
+        Returns (seconds, what the K-th step produced: the drained results when there is a `flush`)."""
         for i in range(warmup):
             step(i)
         if flush is not None:
@@ -181,7 +198,7 @@ class Ctx:
         for i in range(steps):
             out = step(warmup + i)
         if flush is not None:
-            flush()
+            out = flush()
         self.barrier()
         self.last_local_s = time.perf_counter() - t0      # this rank's own clock (scaling_diag); the reported time is the max over ranks
         return self.max_over_ranks(self.last_local_s), out
@@ -193,6 +210,47 @@ class Ctx:
             self.dist.all_gather_object(out, obj)
             return out
         return [obj]
+
+
+# ======================================================================================================================
+# --dump-outputs
+# ======================================================================================================================
+def host_array(t):
+    """float32 / float64 host copy of a tensor (integers exactly, as float64); more than DUMP_CAP elements -> the elements at a fixed,
+    seeded set of flat positions (the same set for every tensor of that size)."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if t.numel() > DUMP_CAP:
+        pos = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_CAP))
+        t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+    t = t.cpu()
+    return (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+
+
+def step_arrays(prefix, out):
+    """{name: array} of what one timed step returned: a tensor, a dict of tensors, or S2SNATGenerator's list of per-utterance dicts
+    (each key concatenated over the utterances, flattened, with the per-utterance first dimension in `<key>_lens`)."""
+    import numpy as np
+    import torch
+    if isinstance(out, torch.Tensor):
+        return {prefix: host_array(out)}
+    if isinstance(out, dict):
+        return {f"{prefix}_{k}": host_array(v) for k, v in out.items()}
+    arrays = {}
+    for key in out[0]:
+        arrays[f"{prefix}_{key}"] = host_array(torch.cat([item[key].reshape(-1) for item in out]))
+        arrays[f"{prefix}_{key}_lens"] = np.array([item[key].shape[0] for item in out], dtype=np.float64)
+    return arrays
+
+
+def write_dump(dirname, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ======================================================================================================================
@@ -303,8 +361,9 @@ def run_links_ops(ctx, B, L, TR, steps, warmup, seed):
     return {"links_fwd_ms": timed(infer), "links_fwd_bwd_ms": timed(train)}
 
 
-def run_dag_ops(ctx, B, L, T, V, TR, steps, warmup, seed, peaked=False, lazy=False, fresh=True):
-    """K passes of the DAG hot path; returns per-phase HIP-event times (ms) and the wall time of the passes."""
+def run_dag_ops(ctx, B, L, T, V, TR, steps, warmup, seed, peaked=False, lazy=False, fresh=True, dump=None):
+    """K passes of the DAG hot path; returns per-phase HIP-event times (ms) and the wall time of the passes.  `dump` (a dict) receives
+    the last pass's loss, logits and links gradients and alignment path."""
     torch = ctx.torch
     from daspeech_amd import custom_ops as ops
     mod = sys.modules["daspeech_amd.custom_ops.dag_loss"]
@@ -365,6 +424,8 @@ def run_dag_ops(ctx, B, L, T, V, TR, steps, warmup, seed, peaked=False, lazy=Fal
     phases = {n: sum(a.elapsed_time(b) for a, b in ev[n]) / max(1, len(ev[n])) for n in names}
     from daspeech_amd import _lib
     status = _lib.last_launch_status()
+    if dump is not None:
+        dump.update(step_arrays("dag", dict(zip(("loss", "grad_logits", "grad_links", "path"), out))))
     del logits, master
     torch.cuda.empty_cache()
     return phases, wall, {"finite_losses": int(torch.isfinite(out[0]).sum()), "launch_status": status}
@@ -410,10 +471,11 @@ def live_dp_traffic(args, TR):
                                                             f"(per-dispatch mean of {kern}, FETCH doubled per MI355X_MICROARCH.md)"}
 
 
-def dag_report(ctx, args, steps, warmup):
+def dag_report(ctx, args, steps, warmup, full=True, dump=None):
+    """`full`: also the peaked and lazy-softmax input sets and the live PMC traffic (child runs of their own)."""
     B, L, T, V = args.dag_batch, args.graph_len, args.tgt_len, args.vocab
     TR = min(args.tr, L - 1)
-    phases, wall, info = run_dag_ops(ctx, B, L, T, V, TR, steps, warmup, 1234 + ctx.rank)
+    phases, wall, info = run_dag_ops(ctx, B, L, T, V, TR, steps, warmup, 1234 + ctx.rank, dump=dump)
     BTL, BLV, BLTR = B * T * L * 4.0, B * L * V * 4.0, B * L * TR * 4.0
     # SURVEY.md §8(d): 2 * (B*T*L*4 [read match] + B*L*TR*4 [read links] + B*T*L*4 [write alpha/beta])
     alg_bytes = 2.0 * (BTL + BLTR + BTL)
@@ -423,7 +485,7 @@ def dag_report(ctx, args, steps, warmup):
     achieved = alg_bytes / (ms * 1e-3) / 1e9
     traffic, src = None, None
     live = None
-    if ctx.rank == 0 and ctx.world == 1 and not getattr(args, "no_live_traffic", False):
+    if full and ctx.rank == 0 and ctx.world == 1 and not getattr(args, "no_live_traffic", False):
         ctx.torch.cuda.synchronize()
         live = live_dp_traffic(args, TR)
     pmc = os.path.join(ROOT, "profiles", "pmc_dag_fwd.json")
@@ -452,6 +514,8 @@ def dag_report(ctx, args, steps, warmup):
                                 "frac_of_hbm_peak": phase_bytes[n] / (phases[n] * 1e-3) / 1e9 / HBM_PEAK_GBS} for n in phases},
         **info,
     }
+    if not full:
+        return rep, roofline
     if not args.no_peaked:
         pp, _, pinfo = run_dag_ops(ctx, B, L, T, V, TR, max(3, steps // 2), 2, 4321 + ctx.rank, peaked=True)
         rep["peaked"] = {"note": "trained-model-like scores (aligned tokens +14 nats on a band around the diagonal, 4-sigma transition logits)",
@@ -663,10 +727,14 @@ def scaling_diag(ctx, batches, steps):
             "backend": ctx.backend if ctx.world > 1 else "none (single rank)"}
 
 
-def run_model(ctx, args, workload, steps, warmup, sustain=0):
+def run_model(ctx, args, workload, steps, warmup, sustain=0, full=True, dump=None):
+    """`full`: also the vocoder roofline call (s2st).  `dump` (a dict) receives what the K-th timed step returned."""
     step, wl, state = build_model_step(ctx, args, workload)
     warmup = max(warmup, 2 * len(state["batches"]))      # MIOpen / hipBLASLt pick algorithms per new shape: keep that out of the timing
-    elapsed, _ = ctx.timed(step, steps, warmup, flush=state.get("flush"))
+    elapsed, out = ctx.timed(step, steps, warmup, flush=state.get("flush"))
+    if dump is not None:
+        dump.update(step_arrays(workload, out))
+    del out
     B = state["B"]
     rep = {"workload": wl, "value": ctx.world * B * steps / elapsed, "unit": "utt/s", "ms_per_step": elapsed * 1e3 / steps, "steps": steps,
            "warmup": warmup, "batch_per_gpu": B}
@@ -678,7 +746,7 @@ def run_model(ctx, args, workload, steps, warmup, sustain=0):
     if workload == "s2st":
         state["mel_frames_per_utt"] = state["frames"] / max(1, (steps + warmup) * B)
         rep["mel_frames_per_utt"] = state["mel_frames_per_utt"]
-        if ctx.rank == 0:
+        if full and ctx.rank == 0:
             rep["roofline"] = vocoder_roofline(ctx, args, state)
     if workload == "train":
         rep["peak_memory_GB"] = ctx.torch.cuda.max_memory_allocated() / 2 ** 30
@@ -727,8 +795,10 @@ def main():
     base = {"metric": METRIC, "unit": "utt/s", "n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "data": "synthetic"}
     par = f"dp{world} (independent utterances per rank, no data-path collective)"
+    full = args.full or args.workload != "headline"
+    dump = {} if args.dump_outputs else None
     if args.workload in ("s2tt", "s2st", "train"):
-        rep = run_model(ctx, args, args.workload, args.steps, args.warmup)
+        rep = run_model(ctx, args, args.workload, args.steps, args.warmup, dump=dump)
         dtype = ("f32" if args.amp == "none" else args.amp) if args.workload != "train" else ("bf16" if args.amp == "bf16" else "fp16")
         result = {**base, "value": rep["value"], "steps": rep["steps"], "warmup": rep["warmup"], "ms_per_step": rep["ms_per_step"], "dtype": dtype,
                   "config": {"workload": rep["workload"], "batch_per_gpu": rep["batch_per_gpu"], "parallelism": par,
@@ -736,24 +806,26 @@ def main():
                              **({"peak_memory_GB": rep["peak_memory_GB"]} if "peak_memory_GB" in rep else {})},
                   "roofline": rep.get("roofline"), "cpu_baseline": None, "scaling_diag": rep.get("scaling_diag")}
     elif args.workload == "dag":
-        rep, roofline = dag_report(ctx, args, args.steps, args.warmup)
+        rep, roofline = dag_report(ctx, args, args.steps, args.warmup, dump=dump)
         result = {**base, "value": rep["utt_per_s"], "steps": args.steps, "warmup": args.warmup, "ms_per_step": rep["step_ms"], "dtype": "f32",
                   "config": {"workload": rep["workload"], "batch_per_gpu": args.dag_batch, "parallelism": par}, "roofline": roofline, "dag": rep,
                   "cpu_baseline": None}
         if not args.no_c1:
             result["c1"] = c1_report(ctx, args.steps)
     else:
-        # headline: A (C4 S2ST, carries `value`), B (C2 DAG ops, carries `roofline`), C (C1 HIP vs the measured CPU baseline)
+        # headline: A (C4 S2ST, carries `value`), B (C2 DAG ops, carries `roofline`); with --full the side legs, C (C1 HIP vs the
+        # measured CPU baseline) among them
         import copy
-        s2st = run_model(ctx, args, "s2st", args.steps, args.warmup, sustain=args.sustain_steps if args.vocoder_backend == "hip" else 0)
+        s2st = run_model(ctx, args, "s2st", args.steps, args.warmup, sustain=args.sustain_steps if full and args.vocoder_backend == "hip" else 0,
+                         full=full, dump=dump)
         fast = None
-        if args.vocoder_backend == "hip":                 # the fp16-storage vocoder beside the headline
+        if full and args.vocoder_backend == "hip":        # the fp16-storage vocoder beside the headline
             a16 = copy.copy(args); a16.vocoder_backend = "hip_fp16"
             fast = run_model(ctx, a16, "s2st", args.steps, args.warmup)
-        dag, roofline = dag_report(ctx, args, args.steps, args.warmup)
+        dag, roofline = dag_report(ctx, args, args.steps, args.warmup, full=full, dump=dump)
         # the README's training window (--max-transition-length 99999 -> TR = L-1) at C2, timed by THIS run
         tr_full = None
-        if min(args.tr, args.graph_len - 1) != args.graph_len - 1:
+        if full and min(args.tr, args.graph_len - 1) != args.graph_len - 1:
             try:
                 pf, _, inf = run_dag_ops(ctx, args.dag_batch, args.graph_len, args.tgt_len, args.vocab, args.graph_len - 1, 3, 1, 77 + rank)
                 tr_full = {"workload": f"C2 with the README's dense window: B={args.dag_batch}, graph_len={args.graph_len}, tgt_len={args.tgt_len}, TR={args.graph_len - 1}",
@@ -780,13 +852,14 @@ def main():
                 tr_full = {"error": repr(e)[:200]}
         # 32 < TR <= 64: exp-space strips with two vertices per lane (forward), values-only max-DP strips (alignment), the TR <= 32 gradient kernel in two planes of 32 transitions (backward)
         tr64 = None
-        try:
-            p64, _, i64 = run_dag_ops(ctx, args.dag_batch, args.graph_len, args.tgt_len, args.vocab, 64, 3, 1, 55 + rank)
-            b64 = 2.0 * (2 * args.dag_batch * args.tgt_len * args.graph_len * 4.0 + args.dag_batch * args.graph_len * 64 * 4.0)
-            tr64 = {"workload": "C2 with TR=64 (windows 33..64: dag_dp_strip2g forward, dag_dp_maxstripw alignment, backward = the exp-space gradient kernel in two planes of 32 transitions, one launch)", "phases_ms": p64,
-                    "dag_loss_fwd_bwd_ms": p64["dag_fwd"] + p64["dag_bwd"], "dag_fwd_frac_of_hbm_peak": b64 / (p64["dag_fwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, **i64}
-        except Exception as e:      # noqa
-            tr64 = {"error": repr(e)[:200]}
+        if full:
+            try:
+                p64, _, i64 = run_dag_ops(ctx, args.dag_batch, args.graph_len, args.tgt_len, args.vocab, 64, 3, 1, 55 + rank)
+                b64 = 2.0 * (2 * args.dag_batch * args.tgt_len * args.graph_len * 4.0 + args.dag_batch * args.graph_len * 64 * 4.0)
+                tr64 = {"workload": "C2 with TR=64 (windows 33..64: dag_dp_strip2g forward, dag_dp_maxstripw alignment, backward = the exp-space gradient kernel in two planes of 32 transitions, one launch)", "phases_ms": p64,
+                        "dag_loss_fwd_bwd_ms": p64["dag_fwd"] + p64["dag_bwd"], "dag_fwd_frac_of_hbm_peak": b64 / (p64["dag_fwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, **i64}
+            except Exception as e:      # noqa
+                tr64 = {"error": repr(e)[:200]}
         result = {**base, "value": s2st["value"], "steps": s2st["steps"], "warmup": s2st["warmup"], "ms_per_step": s2st["ms_per_step"],
                   "dtype": "f32" if args.amp == "none" else args.amp,
                   "dag_loss_fwd_bwd_ms_per_batch": dag["dag_loss_fwd_bwd_ms"],
@@ -805,9 +878,10 @@ def main():
                                            "vocoder_roofline": fast.get("roofline")}
         if tr_full is not None:
             result["dag_tr%d" % (args.graph_len - 1)] = tr_full
-        result["dag_tr64"] = tr64
+        if tr64 is not None:
+            result["dag_tr64"] = tr64
         # C3 and C5 in the same driver-timed line (short legs; `--workload s2tt|train` run them alone at the contract's K)
-        if not args.no_extra_legs:
+        if full and not args.no_extra_legs:
             for key, wl, nb in (("c3_s2tt", "s2tt", 64), ("c5_train", "train", 32)):
                 try:
                     ax = copy.copy(args); ax.batch = nb
@@ -818,15 +892,17 @@ def main():
                                    **({k: rr[k] for k in ("peak_memory_GB", "loss_scale", "last_grad_norm") if k in rr})}
                 except Exception as e:      # noqa: legs of their own
                     result[key] = {"error": repr(e)[:300]}
-        if not args.no_c1:
+        if full and not args.no_c1:
             result["c1"] = c1_report(ctx, args.steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("headline", "dag"):
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("headline", "dag"):
         cb = cpu_baseline_c1(args.cpu_budget)
         result["cpu_baseline"] = cb
         if "c1" in result and cb["tgt_len"] == 256:
             gpu_s = result["c1"]["gather_plus_dag_fwd_bwd_ms"] * 1e-3
             result["c1"]["speedup_vs_cpu_baseline"] = cb["seconds_per_batch"] / gpu_s
     if rank == 0:
+        if dump is not None:
+            write_dump(args.dump_outputs, dump)
         print(json.dumps(result))
     if world > 1:
         ctx.dist.destroy_process_group()

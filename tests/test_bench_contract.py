@@ -1,11 +1,14 @@
-"""The bench line the driver parses (committed in profiles/ from the last GPU run of `python bench.py`) carries every field of the
+"""The bench line the driver parses (committed in profiles/ from the last GPU run of `python bench.py --full`) carries every field of the
 contract: metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
-config{workload}, `roofline` of the dominant kernel and the `cpu_baseline` leg.  CPU-only: checks the committed line and the CLI."""
+config{workload}, `roofline` of the dominant kernel and the `cpu_baseline` leg.  Checks the committed line and the CLI on the CPU; one GPU
+test runs a small plain line with --dump-outputs."""
 import glob
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,7 +20,7 @@ def _latest(pattern):
 
 
 def test_committed_dag_bench_line_has_the_contract_fields():
-    d = json.loads(open(_latest("r0*_bench_headline.json")).read().strip().split("\n")[-1])     # `python bench.py`, the driver's command
+    d = json.loads(open(_latest("r0*_bench_headline.json")).read().strip().split("\n")[-1])     # `python bench.py --full`
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -43,7 +46,7 @@ def test_committed_dag_bench_line_has_the_contract_fields():
 def test_bench_cli_accepts_the_driver_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -94,6 +97,52 @@ def test_bench_under_a_launcher_world2_gloo_rehearsal():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "plumbing"], capture_output=True, text=True,
                          timeout=300, env={**env, "WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert bad.returncode != 0 and "WORLD_SIZE=2" in (bad.stderr + bad.stdout)
+
+
+def test_dump_arrays_are_float_fixed_and_capped(tmp_path):
+    """--dump-outputs: every array float32 / float64 (integers exactly, as float64), S2SNATGenerator's per-utterance results concatenated
+    with their lengths, an array above DUMP_CAP sampled at the same seeded positions on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_CAP + 12345, dtype=torch.float32)
+    a = bench.step_arrays("dag", {"loss": torch.randn(3, dtype=torch.float16), "path": torch.arange(6).view(2, 3), "g": big})
+    assert a["dag_loss"].dtype == np.float32 and a["dag_path"].dtype == np.float64 and a["dag_path"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    b = bench.step_arrays("dag", {"g": big.clone()})["dag_g"]
+    assert np.array_equal(a["dag_g"], b) and 0.5 * bench.DUMP_CAP < b.size <= bench.DUMP_CAP and np.all(np.diff(b) > 0)
+    out = [{"tokens": torch.arange(4), "feature": torch.ones(n, 80), "waveform": torch.zeros(n * 256)} for n in (5, 7)]
+    s = bench.step_arrays("s2st", out)
+    assert s["s2st_feature"].shape == (12 * 80,) and s["s2st_feature_lens"].tolist() == [5.0, 7.0]
+    assert s["s2st_waveform_lens"].tolist() == [1280.0, 1792.0] and s["s2st_tokens"].tolist() == [0, 1, 2, 3] * 2
+    bench.write_dump(str(tmp_path / "d"), {**a, **s})
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in {**a, **s})
+    assert np.array_equal(np.load(tmp_path / "d" / "dag_g.npy"), b)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` at a small size: the headline's fields over K timed steps, none of the
+    --full side legs, and the last timed step's outputs of both timed parts as float arrays within 64 MB."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                          "--dag-batch", "4", "--graph-len", "1024", "--tgt-len", "128", "--vocab", "1024", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = _json_line(out.stdout)
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "utt/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and abs(d["value"] - 1e3 * 4 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["dag_loss_fwd_bwd_ms_per_batch"] > 0 and d["dag"]["launch_status"] == 0 and d["dag"]["finite_losses"] == 4
+    for k in ("c1", "s2st_sustained", "s2st_fp16_vocoder", "dag_tr1023", "dag_tr64", "c3_s2tt", "c5_train"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and d["s2st_vocoder_roofline"] is None and "peaked" not in d["dag"] and "lazy_softmax" not in d["dag"]
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"s2st_tokens", "s2st_feature", "s2st_waveform", "dag_loss", "dag_grad_logits", "dag_grad_links", "dag_path"} <= set(arrays)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["s2st_waveform_lens"].shape == (4,) and arrays["s2st_waveform"].size == arrays["s2st_waveform_lens"].sum()
+    assert arrays["s2st_feature"].size == 80 * arrays["s2st_feature_lens"].sum() and np.isfinite(arrays["s2st_waveform"]).all()
+    assert arrays["dag_loss"].shape == (4,) and np.isfinite(arrays["dag_loss"]).all() and arrays["dag_path"].shape == (4, 1024)
 
 
 def test_live_traffic_reads_the_per_dispatch_counters(tmp_path, monkeypatch):

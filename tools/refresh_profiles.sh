@@ -3,7 +3,7 @@
 # stats of the DAG workload, FETCH / WRITE / SQ counter passes (separate --pmc runs, --kernel-trace only) for the DP and HiFi-GAN kernels
 TAG=${1:-r03}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_headline.json 2> $OUT/bench_headline.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_headline.json 2> $OUT/bench_headline.err
 cd /tmp && export TMPDIR=/tmp
 DAGCMD="python $GRAFT_REPO_ROOT/bench.py --workload dag --no-cpu-baseline --no-c1 --no-peaked --steps 10 --warmup 2"
 rm -rf /tmp/ks; rocprofv3 --kernel-trace --stats -d /tmp/ks -o k --output-format csv -- $DAGCMD > /dev/null 2>&1
