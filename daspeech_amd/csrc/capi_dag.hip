@@ -1,80 +1,122 @@
-// capi_dag.hip — extern "C" entry points of the DP ops (argument checks + kernel selection).
-#include "common.h"
+// capi_dag.hip — extern "C" entry points of the DP ops: argument checks, and the one place that decides which kernel family runs.
+#include "dag_dp.h"
+#include <algorithm>
 #include <string.h>
 
 namespace dsp {
-int launch_dag_fwd_generic(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int, hipStream_t);
-int launch_pick_loss(const float*, const float*, const int64_t*, const int64_t*, float*, int, int, int, int, hipStream_t);
-int launch_best_alignment_generic(const float*, const float*, const int64_t*, const int64_t*, float*, int32_t*, int64_t*, int, int, int, int, hipStream_t);
-int launch_dag_bwd_generic(const float*, const float*, const float*, const float*, const float*, const int64_t*, const int64_t*,
-                           float*, float*, int, int, int, int, int, int, int, hipStream_t);
 
-bool banded_supported(int L, int TR);
-void caller_ws_begin(void* p, size_t n);
-void caller_ws_end();
-void status_begin(hipStream_t st);
-void status_end(hipStream_t st);
 struct CallerWsScope {
     hipStream_t st;
     CallerWsScope(void* p, size_t n, hipStream_t s) : st(s) { caller_ws_begin(p, n); status_begin(st); }
     ~CallerWsScope() { status_end(st); caller_ws_end(); }
 };
-void set_k5_path(int v);
-void set_k5_fuse(int v);
-void set_mx_cpl(int v);
-void set_bt_ring(int v);
-int k5_diag(unsigned int* out);
-int launch_dag_banded(int mode, const float*, const float*, const int64_t*, const int64_t*, float*, float*, int32_t*, int, int, int, int, hipStream_t);
-int banded_last_error_word(hipStream_t st, unsigned int* word);
-int launch_max_alpha_generic(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
-                             float* alpha, int32_t* trace, int B, int T, int L, int TR, hipStream_t st);
-int launch_backtrace(const int32_t* trace, const int64_t* out_len, const int64_t* tgt_len, int64_t* path, int B, int T, int L, hipStream_t st);
 
-bool strip4g_supported(const void* match, const void* alpha, const void* beta, int L, int TR, int ldm, int ldo);
-int launch_dag_strip4g(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int, int, int, hipStream_t);
+// ---- kernel selection ----------------------------------------------------------------------------------------------------------------------
+// The kernel families (one dag_dp_*.hip file each; dag_dp_generic.hip serves any shape and whatever the others do not take).  F_NONE: no
+// family serves these rows / this call, the entry point says why.
+enum Family { F_NONE, F_GENERIC, F_STRIP4G, F_STRIP2G, F_STRIP1G, F_STRIP2, F_BANDED, F_DENSE_MFMA, F_MAXSTRIP, F_MAXSTRIPW, F_DENSE_MAX };
+static constexpr unsigned fam(Family f) { return 1u << f; }
 
-
-bool dense_mfma_supported(int L, int TR);
-int launch_dag_dense_mfma(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int, hipStream_t);
-void set_dm_depth(int v);
-void set_dm_mt(int v);
-void set_dx_mt(int v);
-void set_xl_tile(int v);
-void set_xl_mfma(int v);
-void set_xl_contract(int v);
-void set_dm_budget(int v);
-size_t dense_rows_gated_bytes(int B, int L, int ndir);
-bool dense_rows_gated_supported(int L);
-
-bool dense_max_supported(int L, int TR);
-int launch_dag_dense_max(const float*, const float*, const int64_t*, const int64_t*, float*, int64_t*, int, int, int, int, hipStream_t, unsigned short* block_trace = nullptr);
-int launch_dag_dense_backtrace(const float*, const unsigned short*, const float*, const int64_t*, const int64_t*, int64_t*, int, int, int, int, hipStream_t);
-
-bool maxstrip_supported(const void* match, const void* alpha_max, int L, int TR, int ldm, int ldo);
-int launch_dag_maxstrip(const float*, const float*, const int64_t*, const int64_t*, float*, int64_t*, int, int, int, int, int, int, hipStream_t);
-
-bool maxstripw_supported(int L, int TR);
-size_t maxstripw_ws_bytes(int B, int T, int L, int TR);
-int launch_dag_maxstripw(const float*, const float*, const int64_t*, const int64_t*, float*, int64_t*, int, int, int, int, int, int, hipStream_t);
-bool strip1g_supported(int L, int TR);
-size_t strip1g_ws_bytes(int B, int T, int L, int ndir);
-int launch_dag_strip1g(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int, int, int, hipStream_t);
-bool strip2g_supported(int L, int TR);
-int launch_dag_strip2g(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int, int, int, hipStream_t);
-
-bool strip2_supported(const void* match, const void* alpha, const void* beta, const void* trace, int L, int TR);
-int launch_dag_strip2(int mode, const float*, const float*, const int64_t*, const int64_t*, float*, float*, int32_t*, int, int, int, int, hipStream_t);
-
-// test hook: dsp_dag_set_option("dp_path", n): 0 = auto, 1 = generic row-sequential, 2 = banded 2-column log-space,
-// 4 = strip2 (2 columns/lane, loader wave), 5 = strip4g (4 columns/lane, exp space, one exponent per lane group),
-// 7 = values-only max-DP strips + lazy back-trace for dag_best_alignment (the auto choice when trace == NULL),
-// 8 = strip2g / strip1g (2 columns/lane x 64 transitions, 1 x 128: exp space, windows 33 .. 64 / 65 .. 128: the auto choice there since r06),
-// 9 = dense-window exp-space blocked product on the f32 matrix cores (the auto choice for TR > 32).
-// (3 and 6 were the strip4 / strip4h generations, removed in r02.)  Per THREAD: a test pinning a kernel family does not change what
-// another thread's calls launch.
+// dsp_dag_set_option("dp_path", n) pins the families a launch of the calling THREAD may pick (a test pinning a family does not change what
+// another thread's calls launch); the generic kernels serve whatever the pinned families do not take.  (3 and 6 were the strip4 / strip4h
+// generations, removed in r02: like any other value they leave the generic kernels only.)
+struct Pin { unsigned fwd, align; };
+static Pin pin_of(int dp_path)
+{
+    switch (dp_path) {
+    case 0: return {fam(F_STRIP4G) | fam(F_STRIP2G) | fam(F_STRIP1G) | fam(F_BANDED) | fam(F_DENSE_MFMA),          // auto
+                    fam(F_MAXSTRIP) | fam(F_MAXSTRIPW) | fam(F_DENSE_MAX) | fam(F_STRIP2) | fam(F_BANDED)};
+    case 2: return {fam(F_BANDED), fam(F_BANDED)};
+    case 4: return {fam(F_STRIP2), fam(F_STRIP2)};
+    case 5: return {fam(F_STRIP4G), 0};
+    case 7: return {0, fam(F_MAXSTRIP) | fam(F_MAXSTRIPW)};
+    case 8: return {fam(F_STRIP2G) | fam(F_STRIP1G), 0};
+    case 9: return {fam(F_DENSE_MFMA), fam(F_DENSE_MAX)};
+    default: return {0, 0};                                   // 1: the generic kernels
+    }
+}
 static thread_local int g_path = 0;
 static unsigned int g_last_fallbacks = 0;
 static unsigned int g_dbg[64] = {0};
+
+// rows16: every row starts on a 16-byte boundary and holds round4(L) columns (what the 4-columns-per-lane strips read and write)
+static bool rows16(int L, int ldm, int ldo, uintptr_t ptrs)
+{
+    const int L4 = (L + 3) & ~3;
+    return !(ldm & 3) && !(ldo & 3) && ldm >= L4 && ldo >= L4 && !(ptrs & 15);
+}
+
+// dag_loss forward.  Pitched rows (ld != L) are served by the strip families of windows <= 128 only.
+static Family select_fwd(int L, int TR, bool pitched, bool rows_16)
+{
+    const unsigned m = pin_of(g_path).fwd;
+    if ((m & fam(F_STRIP4G)) && strip4g_supported(L, TR, rows_16)) return F_STRIP4G;
+    if ((m & fam(F_STRIP2G)) && strip2g_supported(L, TR)) return F_STRIP2G;
+    if ((m & fam(F_STRIP1G)) && strip1g_supported(L, TR)) return F_STRIP1G;
+    if (pitched) return F_NONE;
+    if ((m & fam(F_STRIP2)) && strip2_supported(L, TR, rows_16)) return F_STRIP2;
+    if ((m & fam(F_BANDED)) && banded_supported(L, TR)) return F_BANDED;
+    if ((m & fam(F_DENSE_MFMA)) && dense_mfma_supported(L, TR)) return F_DENSE_MFMA;
+    return F_GENERIC;
+}
+
+// dag_best_alignment.  Pitched rows: the values-only strips (windows <= 128).  Without a trace buffer only the values-only strips and the
+// blocked max-plus kernels serve; with one, the traced strips + trace walk take windows <= 64 (the banded ones before the dense kernels on
+// windows 33 .. 64: C2 at TR = 64 2.0 ms against 3.1).
+static Family select_align(int L, int TR, bool pitched, bool rows_16, bool trace)
+{
+    const unsigned m = pin_of(g_path).align;
+    if (pitched) {
+        if ((m & fam(F_MAXSTRIP)) && maxstrip_supported(L, TR, rows_16)) return F_MAXSTRIP;
+        if ((m & fam(F_MAXSTRIPW)) && maxstripw_supported(L, TR)) return F_MAXSTRIPW;
+        return F_NONE;
+    }
+    if ((m & fam(F_MAXSTRIPW)) && maxstripw_supported(L, TR)) return F_MAXSTRIPW;
+    const bool row_image = (size_t)L * 4 <= 160 * 1024;                      // the trace walk keeps one row of the path in LDS
+    const bool traced = (m & (fam(F_STRIP2) | fam(F_BANDED))) != 0;
+    const bool mid = TR > 32 && TR <= 64 && trace && (m & fam(F_BANDED)) && row_image && banded_supported(L, TR);
+    if ((m & fam(F_DENSE_MAX)) && !mid && dense_max_supported(L, TR)) return F_DENSE_MAX;
+    if (!trace || !traced) {                                                   // a given trace goes to the traced strips unless the pin excludes them
+        if ((m & fam(F_MAXSTRIP)) && maxstrip_supported(L, TR, rows_16)) return F_MAXSTRIP;
+        if (!trace) return F_NONE;
+    }
+    if (row_image) {
+        if ((m & fam(F_STRIP2)) && strip2_supported(L, TR, rows_16)) return F_STRIP2;
+        if ((m & fam(F_BANDED)) && banded_supported(L, TR)) return F_BANDED;
+    }
+    return F_GENERIC;
+}
+
+// ---- workspace: what the chosen family's launch takes from the caller (ws_piece per caller_ws_take / banded_acquire_ws) ---------------------------
+static size_t acquired(size_t halo_bytes) { return ws_piece(DP_WS_COUNTERS + halo_bytes); }
+
+static size_t fwd_ws_bytes(Family f, int B, int T, int L, int TR, int ndir)
+{
+    switch (f) {
+    case F_STRIP4G: return acquired(strip4g_ws_bytes(B, T, L, ndir));
+    case F_STRIP2G: return acquired(strip2g_ws_bytes(B, T, L, ndir));
+    case F_STRIP1G: return acquired(strip1g_ws_bytes(B, T, L, ndir));
+    case F_STRIP2: return acquired(strip2_ws_bytes(B, T, L, ndir));
+    case F_BANDED: return acquired(banded_ws_bytes(B, T, L, TR, ndir));
+    case F_DENSE_MFMA:                          // + the stand-by log-space kernels' hand-off rows and their copy of the transition matrix
+        return acquired(dense_mfma_ws_bytes(B, T, L, ndir, true)) + ws_piece(links_copy_bytes(B, L, TR));
+    case F_GENERIC: return generic_fwd_ws_bytes(B, L, TR, ndir);
+    default: return 0;
+    }
+}
+
+static size_t align_ws_bytes(Family f, int B, int T, int L, int TR)
+{
+    switch (f) {
+    case F_MAXSTRIP: return acquired(maxstrip_ws_bytes(B, T, L));
+    case F_MAXSTRIPW: return acquired(maxstripw_ws_bytes(B, T, L, TR));
+    case F_DENSE_MAX: return acquired(dense_max_ws_bytes(B, T, L, true));
+    case F_STRIP2: return acquired(strip2_ws_bytes(B, T, L, 1));
+    case F_BANDED: return acquired(banded_ws_bytes(B, T, L, TR, 1));
+    case F_GENERIC: return generic_align_ws_bytes(B, L, TR);
+    default: return 0;
+    }
+}
 
 static int check_dims(const char* fn, int B, int T, int L, int TR) {
     if (B < 0 || T < 1 || L < 1 || TR < 1) { set_error("%s: bad sizes B=%d T=%d L=%d TR=%d", fn, B, T, L, TR); return DSP_EINVAL; }
@@ -84,75 +126,27 @@ static int check_dims(const char* fn, int B, int T, int L, int TR) {
 
 using namespace dsp;
 
-// Scratch a forward launch takes from the caller (mirrors the launchers' own sizing; a launcher that finds the workspace too small
-// falls back to the library's scratch, so an under-estimate costs a hipMalloc, not correctness).
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-static size_t dense_fwd_ws_bytes(int B, int T, int L, int TR)
-{
-    // dense window on the matrix cores: progress words + (exponent, first-live) per (row, block)
-    const size_t NJ = (size_t)(L + 63) / 64;
-    const size_t halo = align256((size_t)2 * B * NJ * 4) + align256((size_t)2 * B * T * NJ * 8);
-    // ... and its stand-by log-space kernels (a batch whose transitions exp space cannot hold): hand-off rows + the re-laid-out
-    // ("incoming") copy of the transition matrix
-    if (dense_mfma_supported(L, TR) && dense_rows_gated_supported(L))
-        return align256(256 + halo + dense_rows_gated_bytes(B, L, 2)) + align256((size_t)B * L * TR * 4) + 1024;
-    return align256(256 + halo) + 512;
-}
-static size_t dense_align_ws_bytes(int B, int T, int L, int TR)
-{
-    if (dense_max_supported(L, TR)) {                 // blocked max-plus DP: progress words + one block maximum per (row, block)
-        const size_t NJ = (size_t)(L + 63) / 64;
-        return align256(256 + align256((size_t)B * NJ * 4) + align256((size_t)B * T * NJ * 4) + (size_t)B * T * L * 2) + 512;     // (+ the block trace)
-    }
-    return align256((size_t)B * L * TR * 4) + align256(256 + (size_t)B * 2 * L * 8) + 1024;
-}
-
+// The largest take of the families the selection may return for this shape under the calling thread's pin: dense or pitched rows (a pitched
+// caller asks with L rounded up to 4; 16-byte aligned bases), alpha and / or beta.
 extern "C" size_t dsp_dag_workspace_bytes(int B, int T, int L, int TR)
 {
     if (B <= 0 || T <= 0 || L <= 0 || TR <= 0) return 0;
-    if (TR <= 32 && !(L & 3)) {                       // strip4g: 1024-column strips when they still fill the chip, else 512
-        const long ns1024 = (L + 1023) / 1024, ns512 = (L + 511) / 512;
-        const long NS = (2L * B * ns1024 >= 200) ? ns1024 : ns512;
-        return align256(256 + (size_t)2 * B * NS * T * 32 * 8) + 512;
-    }
-    if (TR <= 64) {                                   // banded 2-column strips of 512 (log-space rows: windows 33 .. 64) ...
-        const size_t banded = align256(256 + (size_t)2 * B * ((L + 511) / 512) * T * (TR <= 32 ? 32 : 64) * 8) + 512;
-        // ... which the dense kernels serve instead under dp_path 9 (r05 ADVICE: sized for whichever family runs, so that the launch never falls
-        // back to the library's own scratch — a hipMalloc per call, not capturable)
-        const size_t dense = (TR > 32 && dense_mfma_supported(L, TR)) ? dense_fwd_ws_bytes(B, T, L, TR) : 0;
-        return banded > dense ? banded : dense;
-    }
-    const size_t dense = dense_fwd_ws_bytes(B, T, L, TR);
-    if (strip1g_supported(L, TR)) {                   // windows 65 .. 128: exp-space strips of 256 columns, 128 granules per row and strip
-        const size_t strips = align256(strip1g_ws_bytes(B, T, L, 2)) + 512;
-        return strips > dense ? strips : dense;
-    }
-    return dense;
+    size_t n = 0;
+    for (const bool pitched : {false, true})
+        for (int ndir = 1; ndir <= 2; ++ndir)
+            n = std::max(n, fwd_ws_bytes(select_fwd(L, TR, pitched, pitched || !(L & 3)), B, T, L, TR, ndir));
+    return n;
 }
 
-// ... and the alignment (dsp_dag_best_alignment_ws): the value-only strip DP's hand-off rows, or for dense windows the re-laid-out
-// ("incoming") copy of the transition matrix plus the row hand-off of the log-space max-DP.
+// ... and of the alignment (dsp_dag_best_alignment_ws / _ld), with and without a trace buffer.
 extern "C" size_t dsp_dag_alignment_workspace_bytes(int B, int T, int L, int TR)
 {
     if (B <= 0 || T <= 0 || L <= 0 || TR <= 0) return 0;
-    if (TR <= 32) {
-        const long ns1024 = (L + 1023) / 1024, ns512 = (L + 511) / 512;
-        const long NS = ((long)B * ns1024 >= 200) ? ns1024 : ns512;
-        const size_t strip = (size_t)B * ((L + 383) / 384) * T * 32 * 8;              // strip2 (with a trace buffer): 384-column strips
-        const size_t mx = (size_t)B * NS * T * 32 * 8;
-        return align256(256 + (strip > mx ? strip : mx)) + 512;
-    }
-    if (TR <= 64) {                                   // values-only strips (r06) / banded strips + trace walk; under dp_path 9 or L * 4 > 150 KB: the dense kernels
-        const size_t banded = align256(256 + (size_t)B * ((L + 511) / 512) * T * 64 * 8) + 512;
-        const size_t dense = dense_max_supported(L, TR) ? dense_align_ws_bytes(B, T, L, TR) : 0;
-        return banded > dense ? banded : dense;
-    }
-    const size_t dense = dense_align_ws_bytes(B, T, L, TR);
-    if (maxstripw_supported(L, TR)) {                 // windows 65 .. 128: values-only strips of 256 columns, 128 granules per row and strip
-        const size_t strips = align256(maxstripw_ws_bytes(B, T, L, TR)) + 512;
-        return strips > dense ? strips : dense;
-    }
-    return dense;
+    size_t n = 0;
+    for (const bool pitched : {false, true})
+        for (const bool trace : {false, true})
+            n = std::max(n, align_ws_bytes(select_align(L, TR, pitched, pitched || !(L & 3), trace), B, T, L, TR));
+    return n;
 }
 
 // Row pitches (r06, ABI 2): ld_match / ld_ab are the distances in ELEMENTS between consecutive target rows of match and of alpha / beta
@@ -176,29 +170,20 @@ extern "C" int dsp_dag_loss_fwd_ld(const float* match, int ld_match, const float
     if (!match || !links || !out_len || !tgt_len || (!alpha && !beta)) { set_error("dag_loss_fwd: null pointer"); return DSP_EINVAL; }
     if ((rc = check_ld("dag_loss_fwd", L, ld_match, ld_ab))) return rc;
     hipStream_t st = as_stream(stream);
-    const bool dense = ld_match == L && ld_ab == L;
-    // auto: strip4g for the log-sum DP, strip2 for the max-DP with a trace
-    if ((g_path == 0 || g_path == 5) && strip4g_supported(match, alpha, beta, L, TR, ld_match, ld_ab))
-        rc = launch_dag_strip4g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st);
-    // windows 33 .. 64 (r06): exp-space strips with two vertices per lane (dag_dp_strip2g.hip); dp_path 2 keeps the log-space strips they replace
-    else if ((g_path == 0 || g_path == 8) && strip2g_supported(L, TR))
-        rc = launch_dag_strip2g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st);
-    // windows 65 .. 128 (r06): exp-space strips with one vertex per lane (dag_dp_strip1g.hip); dp_path 9 keeps the dense-window kernels on them
-    else if ((g_path == 0 || g_path == 8) && strip1g_supported(L, TR))
-        rc = launch_dag_strip1g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st);
-    else if (!dense) {
+    const bool pitched = ld_match != L || ld_ab != L;
+    switch (select_fwd(L, TR, pitched, rows16(L, ld_match, ld_ab, (uintptr_t)match | (uintptr_t)alpha | (uintptr_t)beta))) {
+    case F_STRIP4G: rc = launch_dag_strip4g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st); break;
+    case F_STRIP2G: rc = launch_dag_strip2g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st); break;
+    case F_STRIP1G: rc = launch_dag_strip1g(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, ld_match, ld_ab, st); break;
+    case F_STRIP2: rc = launch_dag_strip2(0, match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, st); break;
+    case F_BANDED: rc = launch_dag_banded(0, match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, st); break;
+    case F_DENSE_MFMA: rc = launch_dag_dense_mfma(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, st); break;
+    case F_GENERIC: rc = launch_dag_fwd_generic(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, st); break;
+    default:
         set_error("dag_loss_fwd: pitched rows (ld_match=%d ld_ab=%d, L=%d) are served by the strip kernels of windows <= 128 only (TR <= 32: 16-byte "
                   "aligned pointers, pitches that are multiples of 4); TR=%d / this kernel pin needs dense tensors", ld_match, ld_ab, L, TR);
         return DSP_EINVAL;
     }
-    else if (g_path == 4 && strip2_supported(match, alpha, beta, nullptr, L, TR))
-        rc = launch_dag_strip2(0, match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, st);
-    else if ((g_path == 0 || g_path == 2) && banded_supported(L, TR))
-        rc = launch_dag_banded(0, match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, st);
-    else if ((g_path == 0 || g_path == 9) && dense_mfma_supported(L, TR))
-        rc = launch_dag_dense_mfma(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, st);
-    else
-        rc = launch_dag_fwd_generic(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, st);
     if (rc) return rc;
     if (loss) rc = launch_pick_loss(alpha, beta, out_len, tgt_len, loss, B, T, L, ld_ab, st);
     return rc;
@@ -258,7 +243,7 @@ extern "C" int dsp_dag_best_alignment_ws(const float* match, const float* links,
 }
 
 // ... with row pitches (see dsp_dag_loss_fwd_ld): ld_match / ld_am = elements between consecutive rows of match / alpha_max.  Pitched rows are
-// served by the values-only strip DP + lazy back-trace (TR <= 32, no trace tensor); `trace` must be dense ([B,T,L]) if given and is left untouched.
+// served by the values-only strip DP + back-trace (windows <= 128, no trace tensor); `trace` must be dense ([B,T,L]) if given and is left untouched.
 extern "C" int dsp_dag_best_alignment_ld(const float* match, int ld_match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                                          float* alpha_max, int ld_am, int32_t* trace, int64_t* path, int B, int T, int L, int TR,
                                          void* workspace, size_t workspace_bytes, dsp_stream_t stream)
@@ -279,43 +264,28 @@ static int best_alignment_impl(const float* match, const float* links, const int
     if (ld_match == 0) ld_match = L;
     if (ld_am == 0) ld_am = L;
     if ((rc = check_ld("dag_best_alignment", L, ld_match, ld_am))) return rc;
-    if (ld_match != L || ld_am != L) {
-        if ((g_path == 0 || g_path == 7) && maxstrip_supported(match, alpha_max, L, TR, ld_match, ld_am))
-            return launch_dag_maxstrip(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, ld_match, ld_am, st);
-        if ((g_path == 0 || g_path == 7) && maxstripw_supported(L, TR))
-            return launch_dag_maxstripw(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, ld_match, ld_am, st);
-        set_error("dag_best_alignment: pitched rows (ld_match=%d ld_alpha_max=%d, L=%d) are served by the TR <= 32 strip kernels only (L <= 8192, "
-                  "16-byte aligned pointers, pitches that are multiples of 4)", ld_match, ld_am, L);
+    const bool pitched = ld_match != L || ld_am != L;
+    // (a trace buffer is dense and only the traced kernels write it: its alignment counts on dense rows only)
+    const uintptr_t ptrs = (uintptr_t)match | (uintptr_t)alpha_max | (pitched ? 0 : (uintptr_t)trace);
+    switch (select_align(L, TR, pitched, rows16(L, ld_match, ld_am, ptrs), trace != nullptr)) {
+    case F_MAXSTRIP: return launch_dag_maxstrip(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, ld_match, ld_am, st);
+    case F_MAXSTRIPW: return launch_dag_maxstripw(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, ld_match, ld_am, st);
+    case F_DENSE_MAX: return launch_dag_dense_max(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, st);
+    case F_STRIP2:
+        if ((rc = launch_dag_strip2(1, match, links, out_len, tgt_len, alpha_max, nullptr, trace, B, T, L, TR, st))) return rc;
+        return launch_backtrace(trace, out_len, tgt_len, path, B, T, L, st);
+    case F_BANDED:
+        if ((rc = launch_dag_banded(1, match, links, out_len, tgt_len, alpha_max, nullptr, trace, B, T, L, TR, st))) return rc;
+        return launch_backtrace(trace, out_len, tgt_len, path, B, T, L, st);
+    case F_GENERIC: return launch_best_alignment_generic(match, links, out_len, tgt_len, alpha_max, trace, path, B, T, L, TR, st);
+    default:
+        if (pitched)
+            set_error("dag_best_alignment: pitched rows (ld_match=%d ld_alpha_max=%d, L=%d) are served by the strip kernels of windows <= 128 only "
+                      "(TR <= 32: L <= 8192, 16-byte aligned pointers, pitches that are multiples of 4)", ld_match, ld_am, L);
+        else
+            set_error("dag_best_alignment: this shape / kernel family needs a trace buffer (see dsp_dag_alignment_trace_optional)");
         return DSP_EINVAL;
     }
-    // windows 33 .. 128 (r06): values-only max-DP strips with 2 x 64 / 1 x 128 transitions per lane + the wide back-trace (dag_dp_maxstripw.hip):
-    // no trace tensor.  dp_path 2 / 9 keep the log-space strips + trace walk / the blocked max-plus kernels on these windows.
-    if ((g_path == 0 || g_path == 7) && maxstripw_supported(L, TR))
-        return launch_dag_maxstripw(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, L, L, st);
-    // windows 33 .. 64 with a trace buffer: the banded log-space strips + trace walk (C2 at TR = 64: 2.0 ms against 3.1 for the dense kernels)
-    const bool mid = TR > 32 && TR <= 64 && trace && (g_path == 0 || g_path == 2) && (size_t)L * 4 <= 160 * 1024 && banded_supported(L, TR);
-    // dense window: blocked max-plus DP + trace-free back-trace (the trace buffer, if given, is left untouched)
-    if ((g_path == 0 || g_path == 9) && !mid && dense_max_supported(L, TR))
-        return launch_dag_dense_max(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, st);
-    // trace == NULL: values-only DP + lazy back-trace (no B*T*L trace tensor); only the banded strip kernel offers it
-    if (!trace || g_path == 7) {
-        if ((g_path == 0 || g_path == 7) && maxstrip_supported(match, alpha_max, L, TR, L, L))
-            return launch_dag_maxstrip(match, links, out_len, tgt_len, alpha_max, path, B, T, L, TR, L, L, st);
-        if (!trace) { set_error("dag_best_alignment: this shape / kernel family needs a trace buffer (see dsp_dag_alignment_trace_optional)"); return DSP_EINVAL; }
-    }
-    if ((size_t)L * 4 <= 160 * 1024) {
-        if ((g_path == 0 || g_path == 4) && strip2_supported(match, alpha_max, nullptr, trace, L, TR)) {
-            rc = launch_dag_strip2(1, match, links, out_len, tgt_len, alpha_max, nullptr, trace, B, T, L, TR, st);
-            if (rc) return rc;
-            return launch_backtrace(trace, out_len, tgt_len, path, B, T, L, st);
-        }
-        if ((g_path == 0 || g_path == 2) && banded_supported(L, TR)) {
-            rc = launch_dag_banded(1, match, links, out_len, tgt_len, alpha_max, nullptr, trace, B, T, L, TR, st);
-            if (rc) return rc;
-            return launch_backtrace(trace, out_len, tgt_len, path, B, T, L, st);
-        }
-    }
-    return launch_best_alignment_generic(match, links, out_len, tgt_len, alpha_max, trace, path, B, T, L, TR, st);
 }
 
 extern "C" int dsp_dag_max_alpha(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
@@ -340,7 +310,7 @@ extern "C" int dsp_dag_backtrace(const int32_t* trace, const int64_t* out_len, c
 
 // The same two halves on the dense-window kernels (blocked max-plus DP, 2-byte block trace, back-trace that recomputes the arg-max of the cells
 // it visits): what the Viterbi graph decode runs when the window is wider than 32 (the model's default: --max-transition-length 99999).
-extern "C" int dsp_dag_max_alpha_blocks_supported(int L, int TR) { return ((g_path == 0 || g_path == 9) && dense_max_supported(L, TR)) ? 1 : 0; }
+extern "C" int dsp_dag_max_alpha_blocks_supported(int L, int TR) { return ((pin_of(g_path).align & fam(F_DENSE_MAX)) && dense_max_supported(L, TR)) ? 1 : 0; }
 
 extern "C" int dsp_dag_max_alpha_blocks(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                                         float* alpha_max, uint16_t* block_trace, int B, int T, int L, int TR, dsp_stream_t stream)
@@ -370,36 +340,24 @@ extern "C" int dsp_dag_backtrace_blocks(const float* alpha_max, const uint16_t* 
 extern "C" int dsp_dag_pitch_supported(int op, int L, int TR)
 {
     if (L < 1) return 0;
-    if (TR > 32)           // windows 33 .. 128 (r06): the wide strips read match by 4-byte DMA and write their tables row by row — any pitch
-        return op == 0 ? (((g_path == 0 || g_path == 8) && (strip2g_supported(L, TR) || strip1g_supported(L, TR))) ? 1 : 0)
-                       : (((g_path == 0 || g_path == 7) && maxstripw_supported(L, TR)) ? 1 : 0);
-    if (op == 0) return (g_path == 0 || g_path == 5) ? 1 : 0;
-    return ((g_path == 0 || g_path == 7) && L <= 8192) ? 1 : 0;
+    return (op == 0 ? select_fwd(L, TR, true, true) : select_align(L, TR, true, true, false)) != F_NONE ? 1 : 0;
 }
 
 extern "C" int dsp_dag_alignment_trace_optional(int L, int TR)
 {
-    if ((g_path == 0 || g_path == 7) && maxstripw_supported(L, TR)) return 1;     // windows 33 .. 128: values-only strips + wide back-trace
-    if ((g_path == 0 || g_path == 2) && TR > 32 && TR <= 64) return 0;             // the banded log-space strips of this window keep a trace
-    if ((g_path == 0 || g_path == 9) && dense_max_supported(L, TR)) return 1;
-    return ((g_path == 0 || g_path == 7) && TR <= 32 && (L & 3) == 0 && L <= 8192) ? 1 : 0;
+    return select_align(L, TR, false, !(L & 3), false) != F_NONE ? 1 : 0;
 }
+
+static void set_dp_path(int v) { g_path = v; }
+static const struct { const char* name; void (*set)(int); } k_options[] = {
+    {"dp_path", set_dp_path}, {"k5_path", set_k5_path}, {"k5_fuse", set_k5_fuse}, {"dm_mt", set_dm_mt}, {"dm_budget", set_dm_budget},
+    {"dx_mt", set_dx_mt}, {"xl_tile", set_xl_tile}, {"xl_mfma", set_xl_mfma}, {"xl_contract", set_xl_contract},
+};
 
 extern "C" int dsp_dag_set_option(const char* name, int value)
 {
-    if (name && !strcmp(name, "dp_path")) { g_path = value; return DSP_OK; }
-    if (name && !strcmp(name, "k5_path")) { set_k5_path(value); return DSP_OK; }
-    if (name && !strcmp(name, "k5_fuse")) { set_k5_fuse(value); return DSP_OK; }
-    if (name && !strcmp(name, "mx_cpl")) { set_mx_cpl(value); return DSP_OK; }
-    if (name && !strcmp(name, "bt_ring")) { set_bt_ring(value); return DSP_OK; }
-    if (name && !strcmp(name, "dm_depth")) { set_dm_depth(value); return DSP_OK; }
-    if (name && !strcmp(name, "dm_mt")) { set_dm_mt(value); return DSP_OK; }
-    if (name && !strcmp(name, "dx_mt")) { set_dx_mt(value); return DSP_OK; }
-    if (name && !strcmp(name, "xl_tile")) { set_xl_tile(value); return DSP_OK; }
-    if (name && !strcmp(name, "xl_mfma")) { set_xl_mfma(value); return DSP_OK; }
-    if (name && !strcmp(name, "xl_contract")) { set_xl_contract(value); return DSP_OK; }
-    if (name && !strcmp(name, "dm_budget")) { set_dm_budget(value); return DSP_OK; }
-    if (name && !strcmp(name, "force_generic")) { g_path = value ? 1 : 0; return DSP_OK; }
+    for (const auto& o : k_options)
+        if (name && !strcmp(name, o.name)) { o.set(value); return DSP_OK; }
     set_error("dsp_dag_set_option: unknown option");
     return DSP_EINVAL;
 }

@@ -20,7 +20,7 @@
 //   * PLACEMENT-INDEPENDENT ORDER.  Workgroups draw tickets; a strip's producer always holds a smaller ticket, so the
 //     oldest unfinished workgroup never waits on an unscheduled one (no residency assumption, no deadlock).  Every
 //     spin is bounded and reports through an error word.
-#include "common.h"
+#include "dag_dp.h"
 #include <mutex>
 #include <unordered_map>
 
@@ -298,12 +298,13 @@ static int get_ws(hipStream_t st, size_t need, BandedWS** out)
 }
 
 bool banded_supported(int L, int TR) { (void)L; return TR <= 64; }
+size_t banded_ws_bytes(int B, int T, int L, int TR, int ndir) { return (size_t)ndir * B * ((L + ST_W - 1) / ST_W) * T * (TR <= 32 ? 32 : 64) * sizeof(u64); }
 
 // Shared by every DP launcher that hands rows between workgroups: 256 bytes of counters (ticket, status word, fallback counters,
 // debug slots) + `halo_bytes` of tagged granules / progress words.
 int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base)
 {
-    const size_t need = 256 + halo_bytes;
+    const size_t need = DP_WS_COUNTERS + halo_bytes;
     if (void* c = caller_ws_take(need)) {
         hipError_t e = hipMemsetAsync(c, 0, need, st);               // stream-ordered, capturable; tags of this launch start at 1
         if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
@@ -385,11 +386,10 @@ int launch_dag_banded(int mode, const float* match, const float* links, const in
     const int TRP = TR <= 32 ? 32 : 64;
     const int NS = (L + ST_W - 1) / ST_W;
     const int ndir = (mode == 0 && alpha && beta) ? 2 : 1;
-    const size_t halo_bytes = (size_t)ndir * B * NS * T * TRP * sizeof(u64);
     StripParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
     p.alpha = alpha; p.beta = beta; p.trace = trace;
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, banded_ws_bytes(B, T, L, TR, ndir), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.dbg = 0;
     const dim3 grid((unsigned)(ndir * B * NS)), block(ST_THREADS);

@@ -15,7 +15,7 @@
 // maxima: the torch rule).  r03: the max-DP also leaves, per cell, the index of the 64-column BLOCK that holds its arg-max
 // (2 bytes instead of the reference's 4-byte trace entry), so a hop evaluates 64 candidates instead of up to L
 // (dag_dense_backtrace_blk_kernel; the full scan it replaces took 6 us per hop at C2 / TR = 4095: 0.5 MB of cache lines for one cell).
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -444,12 +444,19 @@ __global__ __launch_bounds__(256) void dag_dense_backtrace_blk_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-
 static thread_local int g_dx_mt = 0;                   // diagnostic switch (dsp_dag_set_option "dx_mt"): 0 = auto, 1 / 2 = 16- / 32-row chunks
 void set_dx_mt(int v) { g_dx_mt = (v == 1 || v == 2) ? v : 0; }
 
 bool dense_max_supported(int L, int TR) { return TR > 32 && L >= 128 && (size_t)L * 4 <= 150 * 1024 && (long)L * TR < (1L << 31); }
+
+// progress words + one block maximum per (row, block) [+ the [B,T,L] block trace when the caller keeps none]
+static size_t dense_max_prog_bytes(int B, int NJ) { return ((size_t)B * NJ * sizeof(u32) + 255) / 256 * 256; }
+static size_t dense_max_s_bytes(int B, int T, int NJ) { return ((size_t)B * T * NJ * sizeof(float) + 255) / 256 * 256; }
+size_t dense_max_ws_bytes(int B, int T, int L, bool own_block_trace)
+{
+    const int NJ = (L + DX_BW - 1) / DX_BW;
+    return dense_max_prog_bytes(B, NJ) + dense_max_s_bytes(B, T, NJ) + (own_block_trace ? (size_t)B * T * L * sizeof(unsigned short) : 0);
+}
 
 static int launch_dense_backtrace(const float* alpha_max, const unsigned short* btrace, const float* links, const int64_t* out_len,
                                   const int64_t* tgt_len, int64_t* path, int B, int T, int L, int TR, hipStream_t st);
@@ -463,11 +470,9 @@ int launch_dag_dense_max(const float* match, const float* links, const int64_t* 
     DXParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha_max;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NJ = NJ;
-    const size_t prog_bytes = ((size_t)B * NJ * sizeof(u32) + 255) / 256 * 256;
-    const size_t s_bytes = ((size_t)B * T * NJ * sizeof(float) + 255) / 256 * 256;
-    const size_t bt_bytes = block_trace ? 0 : (size_t)B * T * L * sizeof(unsigned short);
+    const size_t prog_bytes = dense_max_prog_bytes(B, NJ), s_bytes = dense_max_s_bytes(B, T, NJ);
     u64* area = nullptr;
-    int rc = banded_acquire_ws(st, prog_bytes + s_bytes + bt_bytes, T, &p.counters, &area, &p.tag_base);
+    int rc = banded_acquire_ws(st, dense_max_ws_bytes(B, T, L, !block_trace), T, &p.counters, &area, &p.tag_base);
     if (rc) return rc;
     p.progress = reinterpret_cast<u32*>(area);
     p.S = reinterpret_cast<float*>(reinterpret_cast<char*>(area) + prog_bytes);

@@ -30,7 +30,7 @@
 // cell that has a live predecessor is recomputed exactly in log space (all flagged columns of the row at once, one lane each, over the
 // live predecessors).  That guard assumes no finite transition flushes to zero in exp space: a range check ahead of the kernel
 // (dag_links_weak_kernel) and a budget on the redo work hand batches for which it does not hold to stand-by log-space kernels (`aborted`).
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -51,7 +51,7 @@ struct DMParams {
     float2* S;                // [ndir * B][T][NJ]     (.x block exponent or DM_SENT, .y first live column of the block (0..63) or 64)
     u32 tag_base;
     int B, T, L, TR, NJ, ndir;
-    int dbg;                  // 2 = DSP_DEBUG=prof: cycle accounting of one workgroup (counters[40..47])
+    int dbg;                  // 2 = a -DDSP_PROF build run with DSP_DEBUG=prof: cycle accounting of one workgroup (counters[40..47])
     u32 exact_budget;         // predecessors the exact redo may visit before the launch gives up: see launch_dag_dense_mfma
 };
 
@@ -906,31 +906,33 @@ __global__ __launch_bounds__(256) void dag_links_weak_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-size_t dense_rows_gated_bytes(int B, int L, int ndir);
-bool dense_rows_gated_supported(int L);
-int launch_dag_dense_rows_gated(const float*, const float*, const int64_t*, const int64_t*, float*, float*, int, int, int, int,
-                                unsigned int*, unsigned long long*, unsigned int, const unsigned int*, hipStream_t);
-
 // (L beyond what the stand-by log-space kernels take has no exact fallback for transitions exp space flushes: such shapes stay with the
 // generic log-space kernel)
 // (r05: windows 33 .. 64 too — until then they fell through to the row-sequential generic kernel: 112 ms at C2 / TR = 64; the partially
 //  masked tiles of such a window take the predicated conversion path, at most two source blocks per column block)
 bool dense_mfma_supported(int L, int TR) { return TR > 32 && L >= 128 && (long)L * TR < (1L << 31) && dense_rows_gated_supported(L); }
 
-template <int D, int MT>
-static int launch_dm(const DMParams& p, int nwg, hipStream_t st)
+// progress words + (exponent, first-live) per (row, block) [+ the stand-by kernels' hand-off rows]
+static size_t dense_mfma_prog_bytes(int B, int NJ, int ndir) { return ((size_t)ndir * B * NJ * sizeof(u32) + 255) / 256 * 256; }
+static size_t dense_mfma_s_bytes(int B, int T, int NJ, int ndir) { return ((size_t)ndir * B * T * NJ * sizeof(float2) + 255) / 256 * 256; }
+size_t dense_mfma_ws_bytes(int B, int T, int L, int ndir, bool standby)
+{
+    const int NJ = (L + DM_BW - 1) / DM_BW;
+    return dense_mfma_prog_bytes(B, NJ, ndir) + dense_mfma_s_bytes(B, T, NJ, ndir) + (standby ? dense_rows_gated_bytes(B, L, ndir) : 0);
+}
+
+// one launch of the DP with MT 16-row MFMA tiles per chunk
+template <int MT>
+static int launch_dm(void (*k)(DMParams), const DMParams& p, int nwg, hipStream_t st)
 {
     constexpr int TM = DM_TM * MT;
     const size_t lds = (size_t)(2 * TM * DM_AP + 2 * DM_ET + 6 * TM + 4 + 2 * TM + 68 + 64) * 4 + 64;
-    auto k = dag_dense_mfma_kernel<D, MT>;
     set_max_dynamic_lds((const void*)k, (int)lds);
     hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(256), lds, st, p);
     return check_launch("dag_loss_fwd(dense mfma)");
 }
 
-static thread_local int g_dm_depth = 0, g_dm_mt = 0, g_dm_budget = 0;      // (diagnostic switches are per calling thread, like dp_path)
-void set_dm_depth(int v) { g_dm_depth = v; }
+static thread_local int g_dm_mt = 0, g_dm_budget = 0;      // (kernel pins are per calling thread, like dp_path)
 void set_dm_mt(int v) { g_dm_mt = v; }
 void set_dm_budget(int v) { g_dm_budget = v; }          // 0 = auto, -1 = no stand-by (never give up), n > 0 = that many visited predecessors
 
@@ -942,17 +944,19 @@ int launch_dag_dense_mfma(const float* match, const float* links, const int64_t*
     DMParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha; p.beta = beta;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NJ = NJ; p.ndir = ndir;
-    { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "prof")) ? 2 : 0; }      // (read once per process: no getenv on the launch path)
-    const size_t prog_bytes = ((size_t)ndir * B * NJ * sizeof(u32) + 255) / 256 * 256;
-    const size_t s_bytes = ((size_t)ndir * B * T * NJ * sizeof(float2) + 255) / 256 * 256;
+#ifdef DSP_PROF                                     // instrumentation build only: cycle accounting of one workgroup (counters[40..47])
+    { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "prof")) ? 2 : 0; }
+#else
+    p.dbg = 0;
+#endif
+    const size_t prog_bytes = dense_mfma_prog_bytes(B, NJ, ndir), s_bytes = dense_mfma_s_bytes(B, T, NJ, ndir);
     // the stand-by log-space kernels (see `aborted` in the kernel).  A predecessor visited by the exact redo costs about one memory
     // latency, roughly what a DP row of a block costs when nothing is flagged: the launch may visit one per (row, block) pair on average
     // before it hands the batch over (ordinary batches: a handful per row next to the diagonal)
     const bool standby = g_dm_budget >= 0 && dense_rows_gated_supported(L);
-    const size_t gran_bytes = standby ? dense_rows_gated_bytes(B, L, ndir) : 0;
     p.exact_budget = !standby ? 0xFFFFFFFFu : g_dm_budget > 0 ? (u32)g_dm_budget : (u32)(4096 + (size_t)ndir * B * T * NJ);
     u64* area = nullptr;
-    int rc = banded_acquire_ws(st, prog_bytes + s_bytes + gran_bytes, T, &p.counters, &area, &p.tag_base);
+    int rc = banded_acquire_ws(st, dense_mfma_ws_bytes(B, T, L, ndir, standby), T, &p.counters, &area, &p.tag_base);
     if (rc) return rc;
     p.progress = reinterpret_cast<u32*>(area);
     p.S = reinterpret_cast<float2*>(reinterpret_cast<char*>(area) + prog_bytes);
@@ -968,31 +972,11 @@ int launch_dag_dense_mfma(const float* match, const float* links, const int64_t*
         return launch_dag_dense_rows_gated(match, links, out_len, tgt_len, alpha, beta, B, T, L, TR, p.counters, gran, p.tag_base, p.counters + 3, st);
     };
     const int nwg = ndir * B * NJ;
-    const int depth = g_dm_depth ? g_dm_depth : 2;       // source blocks in flight per workgroup
-    // 16-row MFMA tiles per chunk: 2 (32-row chunks, one register stage) halves the source blocks per DP row and was faster or equal at
-    // every shape of the r02 sweep on the pipelined kernel (C1 1.53 / 1.53 ms, B=16 T=150 L=1024 0.79 / 0.71, C2 at TR = 4095 38.6 / 31.2
-    // for 16- / 32-row chunks; the pre-pipeline kernel had it the other way round: its blocks cost a memory round trip each)
-    const int mt = g_dm_mt ? g_dm_mt : 2;
-    if (mt == 14) return then_standby(launch_dm<1, 4>(p, nwg, st));    // (64-row chunks, one workgroup per CU: comparison build)
-    if (mt == 3 || mt == 4) {                            // 48- / 64-row chunks, two workgroups per CU: 2/3 / half the passes over the transition matrix
-        const int TM = DM_TM * mt;
-        const size_t lds = (size_t)(2 * TM * DM_AP + 2 * DM_ET + 6 * TM + 4 + 2 * TM + 68 + 64) * 4 + 64;
-        auto k = mt == 3 ? dag_dense_mfma_kernel_occ2<1, 3> : dag_dense_mfma_kernel_occ2<1, 4>;
-        set_max_dynamic_lds((const void*)k, (int)lds);
-        hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(256), lds, st, p);
-        return then_standby(check_launch("dag_loss_fwd(dense mfma)"));
-    }
-    if (mt >= 2 && g_dm_depth != 9) {                    // default: 32-row chunks, one stage, two workgroups per CU
-        constexpr int TM = DM_TM * 2;
-        const size_t lds = (size_t)(2 * TM * DM_AP + 2 * DM_ET + 6 * TM + 4 + 2 * TM + 68 + 64) * 4 + 64;
-        auto k = dag_dense_mfma_kernel_occ2<1, 2>;
-        set_max_dynamic_lds((const void*)k, (int)lds);
-        hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(256), lds, st, p);
-        return then_standby(check_launch("dag_loss_fwd(dense mfma)"));
-    }
-    if (mt >= 2) return then_standby(launch_dm<1, 2>(p, nwg, st));     // (dm_depth 9: the one-workgroup-per-CU build of the same kernel, for comparison)
-    if (depth <= 1) return then_standby(launch_dm<1, 1>(p, nwg, st));
-    return then_standby(launch_dm<2, 1>(p, nwg, st));                  // (three stages: 27 spills)
+    // 16-row MFMA tiles per chunk: 2 (32-row chunks, one register stage, two workgroups per CU: the default) halves the source blocks per DP
+    // row and was faster or equal at every shape of the r02 sweep on the pipelined kernel (C1 1.53 / 1.53 ms, B=16 T=150 L=1024 0.79 / 0.71,
+    // C2 at TR = 4095 38.6 / 31.2 for 16- / 32-row chunks; the pre-pipeline kernel had it the other way round: its blocks cost a memory round
+    // trip each).  dm_mt 1 pins the 16-row chunks (two source blocks in flight per workgroup; three stages: 27 spills).
+    return then_standby(g_dm_mt == 1 ? launch_dm<1>(dag_dense_mfma_kernel<2, 1>, p, nwg, st) : launch_dm<2>(dag_dense_mfma_kernel_occ2<1, 2>, p, nwg, st));
 }
 
 }  // namespace dsp

@@ -12,11 +12,9 @@
 // (dag_best_alignment.cu:39-130) + calculate_backtrace_kernel (:170-206).  Semantics as the fp32 operators: cells outside
 // {t < T_b, t <= j < L_b} are -inf, an empty predecessor set stays -inf, invalid / unreachable samples give -inf and zero gradients,
 // Viterbi ties take the smallest predecessor index.
-#include "common.h"
+#include "dag_dp.h"
 
 namespace dsp {
-
-int launch_backtrace(const int32_t* trace, const int64_t* out_len, const int64_t* tgt_len, int64_t* path, int B, int T, int L, hipStream_t st);
 
 constexpr int D64_THREADS = 1024;
 #define D64_NEG (-__builtin_huge_val())

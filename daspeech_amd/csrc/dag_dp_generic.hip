@@ -8,7 +8,7 @@
 //
 // Replaces: calculate_alpha_kernel (dag_loss.cu:40-140), calculate_beta_kernel (:178-274),
 //           calculate_maxalpha_kernel (dag_best_alignment.cu:39-130), calculate_backtrace_kernel (:170-206).
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
@@ -215,13 +215,13 @@ __global__ __launch_bounds__(256) void dag_transpose_links_kernel(const float* _
 static std::mutex g_et_mutex;
 static std::unordered_map<unsigned long long, std::pair<void*, size_t>> g_et;
 
-void* caller_ws_take(size_t n);
+size_t links_copy_bytes(int B, int L, int TR) { return (size_t)B * L * TR * sizeof(float); }
 
 static const float* transposed_links(const float* links, int B, int L, int TR, hipStream_t st, long* sR, long* sD, long* sB)
 {
     *sR = TR; *sD = 1; *sB = (long)L * TR;
     if (TR <= 64) return links;                         // short windows: the original layout is fine
-    if (void* c = caller_ws_take((size_t)B * L * TR * sizeof(float))) {          // caller workspace first (capi: dsp_dag_*_workspace_bytes)
+    if (void* c = caller_ws_take(links_copy_bytes(B, L, TR))) {          // caller workspace first (capi: dsp_dag_*_workspace_bytes)
         hipLaunchKernelGGL(dag_transpose_links_kernel, dim3((TR + 31) / 32, (L + 31) / 32, B), dim3(256), 0, st, links, (float*)c, L, TR);
         *sR = 1; *sD = L;
         return (const float*)c;
@@ -230,7 +230,7 @@ static const float* transposed_links(const float* links, int B, int L, int TR, h
     int dev = 0; (void)hipGetDevice(&dev);
     const unsigned long long key = ((unsigned long long)dev << 48) ^ (unsigned long long)(uintptr_t)st;
     auto& e = g_et[key];
-    const size_t need = (size_t)B * L * TR * sizeof(float);
+    const size_t need = links_copy_bytes(B, L, TR);
     if (e.second < need) {
         if (e.first) (void)hipFree(e.first);
         e.first = nullptr; e.second = 0;
@@ -430,7 +430,7 @@ static const float* incoming_links(const float* links, int B, int L, int TR, hip
 {
     int gx0 = (TR + 255) / 256; if (gx0 > 8) gx0 = 8;
     const int gy = gate ? (L < 128 ? L : 128) : L;              // a stand-by launch keeps its (normally idle) grid small
-    if (void* c = caller_ws_take((size_t)B * L * TR * sizeof(float))) {
+    if (void* c = caller_ws_take(links_copy_bytes(B, L, TR))) {
         hipLaunchKernelGGL(dag_incoming_links_kernel, dim3(gx0, gy, B), dim3(256), 0, st, links, (float*)c, L, TR, gate);
         return (const float*)c;
     }
@@ -438,7 +438,7 @@ static const float* incoming_links(const float* links, int B, int L, int TR, hip
     int dev = 0; (void)hipGetDevice(&dev);
     const unsigned long long key = ((unsigned long long)dev << 48) ^ (unsigned long long)(uintptr_t)st;
     auto& e = g_in[key];
-    const size_t need = (size_t)B * L * TR * sizeof(float);
+    const size_t need = links_copy_bytes(B, L, TR);
     if (e.second < need) {
         if (e.first) (void)hipFree(e.first);
         e.first = nullptr; e.second = 0;
@@ -458,15 +458,11 @@ int launch_backtrace(const int32_t* trace, const int64_t* out_len, const int64_t
     return check_launch("dag_best_alignment(back-trace)");
 }
 
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, unsigned int** counters, unsigned long long** halo, unsigned int* tag_base);
-
 // how many workgroups may share one (sample, direction): everything the launch puts on the device must be co-resident (the
 // per-row hand-off spins), with a factor 2 of slack for whatever else is running
 template <typename K>
 static int dense_slices(K kernel, size_t lds, int groups, int L)
 {
-    static int forced = -1;                      // DSP_DENSE_NS: sweeps only — the co-residency bound below still applies
-    if (forced < 0) { const char* e = getenv("DSP_DENSE_NS"); forced = e ? atoi(e) : 0; }
     int nb = 0, dev = 0, cus = 0;
     (void)hipGetDevice(&dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, DP_THREADS, lds) != hipSuccess || nb < 1) { (void)hipGetLastError(); return 1; }
@@ -478,7 +474,6 @@ static int dense_slices(K kernel, size_t lds, int groups, int L)
     const int by_cols = L / (4 * (DP_THREADS / 64));               // at least one 64-column round per workgroup and row
     if (ns > by_cols) ns = by_cols;
     if (ns > 32) ns = 32;
-    if (forced > 0 && forced < ns) ns = forced;
     return ns < 1 ? 1 : ns;
 }
 
@@ -495,7 +490,7 @@ int launch_dag_fwd_generic(const float* match, const float* links, const int64_t
             if (lds > 48 * 1024) set_max_dynamic_lds((const void*)dag_dense_kernel<0>, (int)lds);
             const int NS = dense_slices(dag_dense_kernel<0>, lds, B * ndir, L);
             unsigned int* cnt = nullptr; unsigned long long* gran = nullptr; unsigned int tag_base = 0;
-            int rcw = banded_acquire_ws(st, (size_t)B * ndir * 2 * L * sizeof(unsigned long long), T, &cnt, &gran, &tag_base);
+            int rcw = banded_acquire_ws(st, dense_rows_gated_bytes(B, L, ndir), T, &cnt, &gran, &tag_base);
             if (rcw) return rcw;
             hipLaunchKernelGGL(dag_dense_kernel<0>, dim3(B, ndir, NS), dim3(DP_THREADS), lds, st, match, links, in, out_len, tgt_len,
                                alpha, beta, (int32_t*)nullptr, B, T, L, TR, cnt, gran, tag_base, (const unsigned int*)nullptr);
@@ -514,6 +509,20 @@ int launch_dag_fwd_generic(const float* match, const float* links, const int64_t
 // this shape (the DP row does not fit the LDS, or no room for the re-laid-out transition copy): the caller then never gives up.
 size_t dense_rows_gated_bytes(int B, int L, int ndir) { return (size_t)B * ndir * 2 * L * sizeof(unsigned long long); }
 bool dense_rows_gated_supported(int L) { return 2 * (size_t)L * sizeof(float) <= 160 * 1024; }
+
+// Caller workspace of launch_dag_fwd_generic / launch_best_alignment_generic (see ws_piece): windows <= 64 take none, dense windows the
+// re-laid-out transition matrix + the hand-off rows of the wave-per-column kernel.
+size_t generic_fwd_ws_bytes(int B, int L, int TR, int ndir)
+{
+    if (TR <= 64 || !dense_rows_gated_supported(L)) return 0;
+    return ws_piece(links_copy_bytes(B, L, TR)) + ws_piece(DP_WS_COUNTERS + dense_rows_gated_bytes(B, L, ndir));
+}
+size_t generic_align_ws_bytes(int B, int L, int TR)
+{
+    if (TR <= 64 || !dense_rows_gated_supported(L)) return 0;
+    if (3 * (size_t)L * sizeof(float) > 160 * 1024) return ws_piece(links_copy_bytes(B, L, TR));          // (the transposed copy)
+    return ws_piece(links_copy_bytes(B, L, TR)) + ws_piece(DP_WS_COUNTERS + dense_rows_gated_bytes(B, L, 1));
+}
 int launch_dag_dense_rows_gated(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                                 float* alpha, float* beta, int B, int T, int L, int TR,
                                 unsigned int* cnt, unsigned long long* gran, unsigned int tag_base, const unsigned int* gate, hipStream_t st)
@@ -529,7 +538,6 @@ int launch_dag_dense_rows_gated(const float* match, const float* links, const in
     return check_launch("dag_loss_fwd(dense, stand-by)");
 }
 
-bool status_export(hipStream_t st, const unsigned int** src, unsigned int** dst);
 int launch_pick_loss(const float* alpha, const float* beta, const int64_t* out_len, const int64_t* tgt_len, float* loss,
                      int B, int T, int L, int ld, hipStream_t st)
 {
@@ -547,14 +555,14 @@ int launch_max_alpha_generic(const float* match, const float* links, const int64
     const size_t lds = 2 * (size_t)L * sizeof(float);
     if (lds > 160 * 1024) { set_error("dag_best_alignment: graph size L=%d too large (max 20480)", L); return DSP_EINVAL; }
     if (lds > 48 * 1024) set_max_dynamic_lds((const void*)dag_maxalpha_generic_kernel, (int)lds);
-    if (TR > 64) {
+    const size_t lds3 = 3 * (size_t)L * sizeof(float);
+    if (TR > 64 && lds3 <= 160 * 1024) {
         const float* in = incoming_links(links, B, L, TR, st);
-        const size_t lds3 = 3 * (size_t)L * sizeof(float);
-        if (in && lds3 <= 160 * 1024) {
+        if (in) {
             if (lds3 > 48 * 1024) set_max_dynamic_lds((const void*)dag_dense_kernel<1>, (int)lds3);
             const int NS = dense_slices(dag_dense_kernel<1>, lds3, B, L);
             unsigned int* cnt = nullptr; unsigned long long* gran = nullptr; unsigned int tag_base = 0;
-            int rcw = banded_acquire_ws(st, (size_t)B * 2 * L * sizeof(unsigned long long), T, &cnt, &gran, &tag_base);
+            int rcw = banded_acquire_ws(st, dense_rows_gated_bytes(B, L, 1), T, &cnt, &gran, &tag_base);
             if (rcw) return rcw;
             hipLaunchKernelGGL(dag_dense_kernel<1>, dim3(B, 1, NS), dim3(DP_THREADS), lds3, st, match, links, in, out_len, tgt_len,
                                alpha, (float*)nullptr, trace, B, T, L, TR, cnt, gran, tag_base, (const unsigned int*)nullptr);

@@ -10,7 +10,7 @@
 //   * the back-trace recomputes the arg-max for the one cell per row it visits, from alpha_max and the links, with the
 //     reference's tie rule (smallest predecessor index; -1 when every candidate is -inf).
 // Used when the caller passes trace == NULL (the Python operator does); with a trace pointer the eager kernels run.
-#include "common.h"
+#include "dag_dp.h"
 #include <string.h>
 #include <stdlib.h>
 // Cycle accounting / timing ablations of the max-DP (tools/prof_maxstrip.py) exist only in a build with -DDSP_MX_PROF (add it as a
@@ -649,15 +649,17 @@ __global__ __launch_bounds__(256) void dag_backtrace_ring_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-
-bool maxstrip_supported(const void* match, const void* alpha_max, int L, int TR, int ldm, int ldo)
+bool maxstrip_supported(int L, int TR, bool rows16)
 {
-    if (TR > 32 || (ldm & 3) || (ldo & 3) || ldm < ((L + 3) & ~3) || ldo < ((L + 3) & ~3)) return false;
-    if (L > 8192) return false;                                // back-trace: path image (4L) + transition window (96 KB) + segments (25 KB) in LDS
-    const uintptr_t a = (uintptr_t)match | (uintptr_t)alpha_max;
-    return (a & 15) == 0;
+    // back-trace: path image (4L) + transition window (96 KB) + segments (25 KB) in LDS
+    return TR <= 32 && L <= 8192 && rows16;
 }
+
+// one direction only: 4 vertices per lane in 1024-vertex strips when that still fills the chip (>= ~200 workgroups), otherwise 2 vertices
+// per lane in 512-vertex strips (twice the waves for the same vertices)
+static bool maxstrip_wide(int B, int L) { return (long)B * ((L + 1023) / 1024) >= 200; }
+static int maxstrip_strips(int B, int L) { return maxstrip_wide(B, L) ? (L + 1023) / 1024 : (L + 511) / 512; }
+size_t maxstrip_ws_bytes(int B, int T, int L) { return (size_t)B * maxstrip_strips(B, L) * T * MX_TRP * sizeof(u64); }
 
 template <int NT, int CPL>
 static int launch_one_mx(const MStripParams& p, int nwg, hipStream_t st)
@@ -672,21 +674,12 @@ static int launch_one_mx(const MStripParams& p, int nwg, hipStream_t st)
     return check_launch("dag_best_alignment(maxstrip)");
 }
 
-static int g_bt_ring = 1;                     // dsp_dag_set_option("bt_ring", 0): the r01-r03 back-trace kernel (cross-check)
-void set_bt_ring(int v) { g_bt_ring = v; }
-static int g_mx_cpl = 0;                      // experiment switch (dsp_dag_set_option("mx_cpl", 1 | 2 | 4)): vertices per lane of the max-DP; 0 = auto
-void set_mx_cpl(int v) { g_mx_cpl = v; }
-
 // alpha_max by column strips (values only), then the lazy back-trace: no trace tensor
 int launch_dag_maxstrip(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                         float* alpha_max, int64_t* path, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
 {
-    // one direction only: 4 vertices per lane in 1024-vertex strips when that still fills the chip (>= ~200 workgroups),
-    // otherwise 2 vertices per lane in 512-vertex strips (twice the waves for the same vertices)
-    const int ns1024 = (L + 1023) / 1024, ns512 = (L + 511) / 512, ns256 = (L + 255) / 256;
-    const int cpl = g_mx_cpl == 1 || g_mx_cpl == 2 || g_mx_cpl == 4 ? g_mx_cpl : ((long)B * ns1024 >= 200 ? 4 : 2);
-    const bool wide = cpl == 4;
-    const int NS = cpl == 4 ? ns1024 : (cpl == 2 ? ns512 : ns256);
+    const bool wide = maxstrip_wide(B, L);
+    const int NS = maxstrip_strips(B, L);
     MStripParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha_max;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ldm = ldm; p.ldo = ldo;
@@ -695,12 +688,11 @@ int launch_dag_maxstrip(const float* match, const float* links, const int64_t* o
 #else
     p.dbg = 0;
 #endif
-    const size_t halo_bytes = (size_t)B * NS * T * MX_TRP * sizeof(u64);
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, maxstrip_ws_bytes(B, T, L), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
-    rc = wide ? launch_one_mx<256, 4>(p, B * NS, st) : (cpl == 2 ? launch_one_mx<256, 2>(p, B * NS, st) : launch_one_mx<256, 1>(p, B * NS, st));
+    rc = wide ? launch_one_mx<256, 4>(p, B * NS, st) : launch_one_mx<256, 2>(p, B * NS, st);
     if (rc) return rc;
-    if (TR == 32 && g_bt_ring && (((uintptr_t)links) & 15) == 0) {
+    if (TR == 32 && (((uintptr_t)links) & 15) == 0) {
         const size_t lds3 = ((size_t)BR_RW * 32 + 2 * BR_H * BR_SEG + (size_t)L) * 4;
         set_max_dynamic_lds((const void*)dag_backtrace_ring_kernel, (int)lds3);
         hipLaunchKernelGGL(dag_backtrace_ring_kernel, dim3(B), dim3(256), lds3, st, alpha_max, links, out_len, tgt_len, path, B, T, L, ldo);

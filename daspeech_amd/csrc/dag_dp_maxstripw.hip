@@ -15,7 +15,7 @@
 //   * back-trace (dag_backtrace_wide_kernel): one wave per sample; at (t, pos) lane d evaluates the predecessors at distances d+1 and d+65,
 //     smallest predecessor index among equal maxima (the reference's tie rule as torch states it), -1 / stop where every
 //     candidate is -inf (dag_best_alignment.cu:170-206 chases a stored trace instead).
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 
 #define MW_CHUNK6_0 \
@@ -384,13 +384,11 @@ __global__ __launch_bounds__(64) void dag_backtrace_wide_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-
 bool maxstripw_supported(int L, int TR) { return TR > 32 && TR <= 128 && (size_t)L * 4 <= 150 * 1024; }
 size_t maxstripw_ws_bytes(int B, int T, int L, int TR)
 {
     const int cpl = TR <= 64 ? 2 : 1, W = cpl * MW_NT, TRP = 128 / cpl;
-    return 256 + (size_t)B * ((L + W - 1) / W) * T * TRP * sizeof(u64);
+    return (size_t)B * ((L + W - 1) / W) * T * TRP * sizeof(u64);
 }
 
 template <int CPL>
@@ -398,8 +396,7 @@ static int launch_mw(MWParams& p, int B, int T, int L, hipStream_t st)
 {
     constexpr int W = CPL * MW_NT, TRP = 128 / CPL, RL = W + TRP;
     p.NS = (L + W - 1) / W;
-    const size_t halo_bytes = (size_t)B * p.NS * T * TRP * sizeof(u64);
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, maxstripw_ws_bytes(B, T, L, p.TR), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
     const size_t lds_main = (size_t)(2 * RL + MW_RING * W) * 4 + 16;
     const size_t lds_tile = (size_t)(W + TRP) * 65 * 4 + 16;

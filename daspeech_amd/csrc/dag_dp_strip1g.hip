@@ -14,7 +14,7 @@
 //   * guard and fallbacks as strip2g: sums under 2^-97 (2^30 for a column with a flushed weight) take the diagonal's single-transition
 //     shortcut or the exact log-space form; windows under 125 drop the groups without a predecessor from the row's reference.
 // Replaces calculate_alpha_kernel / calculate_beta_kernel (dag_loss.cu:40-140,178-274) for 64 < translen <= 128.
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 
 // the row's LDS issue groups (generated: operand numbers and byte offsets)
@@ -482,10 +482,8 @@ __global__ __launch_bounds__(H1_NT + 192) void dag_strip1g_kernel(H1Params p)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-
 bool strip1g_supported(int L, int TR) { return TR > 64 && TR <= H1_TRP && L >= 1; }
-size_t strip1g_ws_bytes(int B, int T, int L, int ndir) { return 256 + (size_t)ndir * B * ((L + H1_W - 1) / H1_W) * T * H1_TRP * sizeof(u64); }
+size_t strip1g_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * ((L + H1_W - 1) / H1_W) * T * H1_TRP * sizeof(u64); }
 
 int launch_dag_strip1g(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                        float* alpha, float* beta, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
@@ -495,8 +493,7 @@ int launch_dag_strip1g(const float* match, const float* links, const int64_t* ou
     H1Params p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha; p.beta = beta;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.ldm = ldm; p.ldo = ldo;
-    const size_t halo_bytes = (size_t)ndir * B * NS * T * H1_TRP * sizeof(u64);
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, strip1g_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
     const size_t lds_main = (size_t)(4 * H1_RL + 2 * H1_GL + H1_RING * H1_W) * 4 + 16;
     const size_t lds_tile = (size_t)(H1_W + H1_TRP) * 65 * 4 + 16;

@@ -11,11 +11,8 @@
 //     neighbour strip's halo granules into LDS rings with global_load_lds (sc1 for the granules), PD rows ahead, retired by
 //     ONE counted s_waitcnt per row.  Compute waves only store (alpha / trace / boundary granules) and never wait on vmcnt;
 //     the lanes next to the halo convert the landed granules (tag check; a stale tag falls back to a direct poll).
-#include "common.h"
-#include <stdio.h>
+#include "dag_dp.h"
 #include <stdlib.h>
-#include <string.h>
-#include <vector>
 
 namespace dsp {
 
@@ -456,7 +453,7 @@ __global__ __launch_bounds__(NT + 64, 3) void dag_strip2_kernel(StripParams p)
     const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
     const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
     u64* census = nullptr;
-    if (p.dbg && tid == 0) {                          // residency census (DSP_DEBUG=census): hw id + start clock per workgroup
+    if (p.dbg && tid == 0) {                          // residency census of r01 (dbg != 0; the launcher passes 0): hw id + start clock per workgroup
         census = p.halo + (size_t)p.ndir * p.B * p.NS * T * 32 + (size_t)ticket * 4;
         u32 hwid, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -485,14 +482,12 @@ __global__ __launch_bounds__(NT + 64, 3) void dag_strip2_kernel(StripParams p)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
+// 192 compute lanes + 64 loader lanes = 4 waves per workgroup = ONE WAVE PER SIMD per workgroup: with 5-wave workgroups the hardware admitted a
+// single workgroup per CU although the occupancy API reported 2 (census in tools/census.py); 4-wave workgroups stack 3 deep at 168 VGPRs.
+constexpr int S2_NT = 192, S2_W = 2 * S2_NT;
 
-bool strip2_supported(const void* match, const void* alpha, const void* beta, const void* trace, int L, int TR)
-{
-    if (TR > 32 || (L & 3)) return false;
-    const uintptr_t a = (uintptr_t)match | (uintptr_t)alpha | (uintptr_t)beta | (uintptr_t)trace;
-    return (a & 15) == 0;
-}
+bool strip2_supported(int L, int TR, bool rows16) { return TR <= 32 && !(L & 3) && rows16; }
+size_t strip2_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * ((L + S2_W - 1) / S2_W) * T * 32 * sizeof(u64); }
 
 template <int NT, int MODE>
 static int launch_strip2(const StripParams& p, int nwg, hipStream_t st)
@@ -500,16 +495,9 @@ static int launch_strip2(const StripParams& p, int nwg, hipStream_t st)
     constexpr int W = 2 * NT, RL = W + 32;
     const size_t lds_main = (size_t)(6 * RL + S2_RING * W) * 4 + (size_t)S2_RING * 32 * 8;
     const size_t lds_tile = (size_t)(NT + 34) * 33 * 4;
-    size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    { static const char* const e = getenv("DSP_S2_LDS"); if (e) lds = (size_t)atoi(e); }
+    const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
     auto k = dag_strip2_kernel<NT, MODE>;
     set_max_dynamic_lds((const void*)k, (int)lds);
-    static const char* const e_dbg = getenv("DSP_DEBUG");
-    if (e_dbg) {
-        int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, NT + 64, lds);
-        fprintf(stderr, "[dsp] strip2<%d,%d>: lds=%zu bytes, occupancy API = %d blocks/CU, grid=%d\n", NT, MODE, lds, nb, nwg);
-    }
     hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(NT + 64), lds, st, p);
     return check_launch(MODE == 0 ? "dag_loss_fwd(strip2)" : "dag_best_alignment(strip2)");
 }
@@ -518,31 +506,15 @@ int launch_dag_strip2(int mode, const float* match, const float* links, const in
                       float* alpha, float* beta, int32_t* trace, int B, int T, int L, int TR, hipStream_t st)
 {
     const int ndir = (mode == 0 && alpha && beta) ? 2 : 1;
-    // 192 compute lanes + 64 loader lanes = 4 waves per workgroup = ONE WAVE PER SIMD per workgroup: with 5-wave
-    // workgroups the hardware admitted a single workgroup per CU although the occupancy API reported 2 (census in
-    // tools/census.py); 4-wave workgroups stack 3 deep at 168 VGPRs.
-    constexpr int NT = 192, W = 2 * NT;
-    const int NS = (L + W - 1) / W;
+    const int NS = (L + S2_W - 1) / S2_W;
     StripParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
     p.alpha = alpha; p.beta = beta; p.trace = trace;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.dbg = 0;
-    const size_t halo_bytes = (size_t)ndir * B * NS * T * 32 * sizeof(u64);
     const int nwg = ndir * B * NS;
-    static const char* const dbg = getenv("DSP_DEBUG");
-    const bool census = dbg && !strcmp(dbg, "census");
-    p.dbg = census ? 1 : 0;
-    int rc = banded_acquire_ws(st, halo_bytes + (census ? (size_t)nwg * 32 : 0), T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, strip2_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
-    rc = mode == 0 ? launch_strip2<NT, 0>(p, nwg, st) : launch_strip2<NT, 1>(p, nwg, st);
-    if (census && rc == 0) {
-        std::vector<u64> h((size_t)nwg * 4);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h.data(), p.halo + (size_t)ndir * B * NS * T * 32, h.size() * 8, hipMemcpyDeviceToHost);
-        FILE* f = fopen("/tmp/census.txt", "w");
-        if (f) { for (int i = 0; i < nwg; ++i) fprintf(f, "%d %llx %llu %llu %llu\n", i, h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]); fclose(f); }
-    }
-    return rc;
+    return mode == 0 ? launch_strip2<S2_NT, 0>(p, nwg, st) : launch_strip2<S2_NT, 1>(p, nwg, st);
 }
 
 }  // namespace dsp

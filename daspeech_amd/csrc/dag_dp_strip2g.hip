@@ -15,7 +15,7 @@
 //     weights, and the exact path serves the same cells.
 // Until r06 these windows ran the log-space strips of dag_dp_banded.hip (2 x 64 v_exp per lane-row: 2.5 ms at C2 / TR = 64).
 // Replaces calculate_alpha_kernel / calculate_beta_kernel (dag_loss.cu:40-140,178-274) for 32 < translen <= 64.
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 
 namespace dsp {
@@ -490,9 +490,8 @@ __global__ __launch_bounds__(H2_NT + 192) void dag_strip2g_kernel(H2Params p)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
-
 bool strip2g_supported(int L, int TR) { return TR > 32 && TR <= H2_TRP && L >= 1; }
+size_t strip2g_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * ((L + H2_W - 1) / H2_W) * T * H2_TRP * sizeof(u64); }
 
 int launch_dag_strip2g(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                        float* alpha, float* beta, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
@@ -502,8 +501,7 @@ int launch_dag_strip2g(const float* match, const float* links, const int64_t* ou
     H2Params p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha; p.beta = beta;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.ldm = ldm; p.ldo = ldo;
-    const size_t halo_bytes = (size_t)ndir * B * NS * T * H2_TRP * sizeof(u64);
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+    int rc = banded_acquire_ws(st, strip2g_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
     const size_t lds_main = (size_t)(4 * H2_RL + 2 * H2_GL + H2_RING * H2_W) * 4 + 16;
     const size_t lds_tile = (size_t)(H2_W + H2_TRP) * 65 * 4 + 16;

@@ -15,7 +15,7 @@
 // nine group exponents: scaled values are <= 2^120 and nothing above 2^-246 of the window maximum is flushed, so a sum
 // S >= 2^-97 has lost at most 36 * 2^-126: exact to fp32.  S < 2^-97 or inf sends the cell to the register-only "medium" path
 // (own maximum, log-domain row) and then the exact log-space path as in strip4.
-#include "common.h"
+#include "dag_dp.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -50,7 +50,7 @@ __device__ __forceinline__ u64 g4_gran_load(const u64* p) {
 __device__ __forceinline__ void g4_gran_store(u64* p, u32 tag, float v) {
     __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// DSP_DEBUG=prof: per-wave cycle accounting (s_memtime) of own work / barrier wait / LDS-read wait, for two workgroups
+// dbg 2 (a -DDSP_PROF build run with DSP_DEBUG=prof): per-wave cycle accounting (s_memtime) of own work / barrier wait / LDS-read wait, for two workgroups
 struct G4Prof { u64 last, work, wait, rd, fma, tmid; };
 template <bool PROF>
 __device__ __forceinline__ void g4_barrier(G4Prof& pf) {
@@ -318,8 +318,8 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                     need_fb |= flag[c];
                     a2[c] = (okl & !flag[c]) ? (__builtin_amdgcn_logf(S[c]) + (ref + base[c])) : NEG_INF;
                 }
-                if (__builtin_expect(need_fb && p.dbg != 4, 0)) {      // (DSP_DEBUG=nofallback: timing experiment, WRONG results)
-                    // diagnostics (DSP_DEBUG=medium only: a returning global atomic costs the wave a memory round trip per entry)
+                if (__builtin_expect(need_fb && p.dbg != 4, 0)) {      // (dbg 4, r01 timing experiment: WRONG results; never set)
+                    // diagnostics (dbg 1, r01; never set: a returning global atomic costs the wave a memory round trip per entry)
                     if (p.dbg == 1) {
                         const u32 slot = atomicAdd(&p.counters[3], 1u);
                         if (slot < 14) { const int fc = flag[0] ? 0 : flag[1] ? 1 : flag[2] ? 2 : 3;
@@ -610,16 +610,14 @@ __global__ __launch_bounds__(NT + 192) void dag_strip4g_kernel(GStripParams p)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int banded_acquire_ws(hipStream_t st, size_t halo_bytes, int T, u32** counters, u64** halo, u32* tag_base);
+// rows start on 16-byte boundaries (rows16: the PITCHES are multiples of 4, the graph length need not be — a lane whose four columns straddle
+// L loads / stores inside the pitch padding; columns >= L are outside every sample's graph and come out -inf)
+bool strip4g_supported(int L, int TR, bool rows16) { (void)L; return TR <= 32 && rows16; }
 
-bool strip4g_supported(const void* match, const void* alpha, const void* beta, int L, int TR, int ldm, int ldo)
-{
-    // rows start on 16-byte boundaries: the PITCHES are multiples of 4, the graph length need not be (a lane whose four columns straddle L
-    // loads / stores inside the pitch padding; columns >= L are outside every sample's graph and come out -inf)
-    if (TR > 32 || (ldm & 3) || (ldo & 3) || ldm < ((L + 3) & ~3) || ldo < ((L + 3) & ~3)) return false;
-    const uintptr_t a = (uintptr_t)match | (uintptr_t)alpha | (uintptr_t)beta;
-    return (a & 15) == 0;
-}
+// strip width: 1024 columns when that still yields >= ~200 workgroups, else 512
+static bool strip4g_wide(int B, int L, int ndir) { return (long)ndir * B * ((L + 1023) / 1024) >= 200; }
+static int strip4g_strips(int B, int L, int ndir) { return strip4g_wide(B, L, ndir) ? (L + 1023) / 1024 : (L + 511) / 512; }
+size_t strip4g_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * strip4g_strips(B, L, ndir) * T * G4_TRP * sizeof(u64); }
 
 template <int NT, bool PROF>
 static int launch_one_g(const GStripParams& p, int nwg, hipStream_t st)
@@ -638,20 +636,23 @@ int launch_dag_strip4g(const float* match, const float* links, const int64_t* ou
                        float* alpha, float* beta, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
 {
     const int ndir = (alpha && beta) ? 2 : 1;
-    // strip width: 1024 columns when that still yields >= ~200 workgroups, else 512
-    const int ns1024 = (L + 1023) / 1024, ns512 = (L + 511) / 512;
-    const bool wide = (long)ndir * B * ns1024 >= 200;
-    const int NS = wide ? ns1024 : ns512;
+    const bool wide = strip4g_wide(B, L, ndir);
+    const int NS = strip4g_strips(B, L, ndir);
     GStripParams p;
     p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
     p.alpha = alpha; p.beta = beta; p.trace = nullptr;
     p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.ldm = ldm; p.ldo = ldo;
-    { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "medium")) ? 1 : (e && !strcmp(e, "prof")) ? 2 : (e && !strcmp(e, "nofallback")) ? 4 : 0; }
-    const size_t halo_bytes = (size_t)ndir * B * NS * T * G4_TRP * sizeof(u64);
-    int rc = banded_acquire_ws(st, halo_bytes, T, &p.counters, &p.halo, &p.tag_base);
+#ifdef DSP_PROF                                     // instrumentation build only (tools/prof_strip.py): nothing on the product's launch path
+    { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "prof")) ? 2 : 0; }
+#else
+    p.dbg = 0;
+#endif
+    int rc = banded_acquire_ws(st, strip4g_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
     if (rc) return rc;
     const int nwg = ndir * B * NS;
+#ifdef DSP_PROF
     if (p.dbg == 2 && wide) return launch_one_g<256, true>(p, nwg, st);
+#endif
     return wide ? launch_one_g<256, false>(p, nwg, st) : launch_one_g<128, false>(p, nwg, st);
 }
 

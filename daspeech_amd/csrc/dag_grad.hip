@@ -1,6 +1,6 @@
 // dag_grad.hip — K4 (grad wrt match_all) and K5 (grad wrt links) for gfx950, generic log-space form.
 // Replaces calculate_grad_match_all_kernel (dag_loss.cu:378-401) and calculate_grad_links_kernel (:432-485).
-#include "common.h"
+#include "dag_dp.h"
 #include <atomic>
 #include <cmath>
 #include <type_traits>
@@ -549,10 +549,9 @@ static int launch_gx(const float* g_out, const float* alpha, const float* beta, 
 {
     const size_t lds = (size_t)4 * gx_wave_words(TC, FUSE && !MREG) * 4;
     auto kern = dag_grad_links_exp_kernel<TC, FUSE, MREG, AUX>;
-    static const char* const e_rm = getenv("DSP_GX_REMAP");
     set_max_dynamic_lds((const void*)kern, (int)lds);
     hipLaunchKernelGGL(kern, dim3(((L + 255) / 256) * B, (TR + 31) / 32), dim3(256), lds, st,
-                       g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, e_rm ? 1 : 0);
+                       g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, 0);
     return check_launch(FUSE ? "dag_loss_bwd(grad_match + grad_links, exp space, one launch)" : "dag_loss_bwd(grad_links, exp space)");
 }
 
@@ -600,12 +599,8 @@ int launch_dag_bwd_generic(const float* g_out, const float* alpha, const float* 
     // both gradients of a banded graph: ONE launch reads alpha / beta / match once (k5_last 4 / 5)
     if (g_match && g_links && expk && pitched_m && g_k5_path != 1 && fuse != 3 && ((((uintptr_t)match) | ((uintptr_t)g_match)) & 15) == 0) {
         // measured at C2 (r06, us per launch): default cache policy + XCD-contiguous tiles 285, nt 276, round-robin tiles 269, round-robin + nt 257
-        // (nt = aux 2 on the LDS-DMA row loads and a non-temporal grad_match store: every byte is touched once).  DSP_GX_NT=0 / DSP_GX_REMAP=1
-        // bring the other variants back for measurements.
-        static const char* const e_nt = getenv("DSP_GX_NT");
-        const bool nt = !(e_nt && e_nt[0] == '0');
-        int rc = (fuse != 1 && nt) ? launch_gx<3, true, false, 2>(g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, st)
-               : fuse != 1 ? launch_gx<3, true, false>(g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, st)
+        // (nt = aux 2 on the LDS-DMA row loads and a non-temporal grad_match store: every byte is touched once)
+        int rc = fuse != 1 ? launch_gx<3, true, false, 2>(g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, st)
                            : launch_gx<4, true, true>(g_out, alpha, beta, links, out_len, tgt_len, g_links, match, g_match, B, T, L, TR, lda, ldm, ldg, st);
         if (rc) return rc;
         g_k5_last = fuse != 1 ? 5u : 4u;

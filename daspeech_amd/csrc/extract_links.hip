@@ -9,7 +9,7 @@
 // computed: one workgroup per (sample, 4 source vertices), thread = (head h, successor j): 8 heads x 32 successors per step, soft-max
 // over the slots inside the 32 lanes of a head, the log-sum-exp over heads through LDS; the per-head scores of the four vertices are
 // parked in LDS (any TR, incl. README's --max-transition-length 99999: TR = L-1).
-#include "common.h"
+#include "dag_dp.h"
 #include <atomic>
 
 namespace dsp {

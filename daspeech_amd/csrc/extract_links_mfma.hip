@@ -31,7 +31,7 @@
 // same end (lock-step for a dense window): L2 hit rate 3 % -> 85-90 %, STATS 1.98 -> 1.41 ms at the C2 shape.
 // Same arithmetic as extract_links.hip (same masks, same -inf conventions, same `stats` layout), so the two families are interchangeable
 // per call (tests compare them element by element, and both with torch autograd / the fp64 oracle).
-#include "common.h"
+#include "dag_dp.h"
 #include <atomic>
 #include "../../include/daspeech_decode.h"
 #include <type_traits>
@@ -639,12 +639,10 @@ extern "C" int dsp_extract_links_ws(const float* q, const float* k, const float*
     hipLaunchKernelGGL(xl_mfma_split_kernel, dim3((unsigned)p.NT, (unsigned)B), dim3(256), 0, st, k, static_cast<char*>(workspace), L, p.NT, (const float*)nullptr, (size_t)0);
     if (int rc = check_launch("extract_links(split)")) return rc;
     g_xl_ran |= 4u;
-    static const char* const e_sq = getenv("DSP_XM_STATS_QG");
-    const int sq = e_sq ? atoi(e_sq) : (L <= 1536 ? 1 : 2);          // as EMIT below (us at B = 32, 64- / 32-owner tiles — L = 256: 20 / 14, L = 1024: 121 / 93)
+    const int sq = L <= 1536 ? 1 : 2;          // as EMIT below (us at B = 32, 64- / 32-owner tiles — L = 256: 20 / 14, L = 1024: 121 / 93)
     if (int rc = sq == 1 ? xm_launch<XM_STATS, 1>(p, st, "extract_links(matrix-core soft-max state)")
                          : xm_launch<XM_STATS, 2>(p, st, "extract_links(matrix-core soft-max state)")) return rc;
-    static const char* const e_qg = getenv("DSP_XM_EMIT_QG");
-    const int qg = e_qg ? atoi(e_qg) : (L <= 1536 ? 1 : 2);
+    const int qg = L <= 1536 ? 1 : 2;
     // 32-owner tiles with one barrier per two tiles on graphs up to ~1 500 vertices (us at B = 32, 64- vs 32-owner tiles — L = 256: 28 / 18,
     // L = 400: 42 / 39, L = 1024: 174 / 153), 64-owner tiles above (half the fragment traffic — L = 2048: 552 / 585, L = 4096: 1 950 / 2 130)
     if (qg == 1) return xm_launch<XM_EMIT, 1>(p, st, "extract_links(matrix-core emission)");
@@ -675,8 +673,7 @@ extern "C" int dsp_extract_links_bwd_ws(const float* q, const float* k, const fl
     hipLaunchKernelGGL(xl_mfma_split_kernel, dim3((unsigned)p.NT, (unsigned)B, 2), dim3(256), 0, st, k, ws, L, p.NT, q, one);      // k -> ws, q -> ws + one
     if (int rc = check_launch("extract_links_bwd(split)")) return rc;
     p.pa = ws;
-    static const char* const e_aq = getenv("DSP_XM_SA_QG");
-    const int aq = e_aq ? atoi(e_aq) : (L <= 1536 ? 1 : 2);          // (L = 256: 27 / 18 us, L = 1024: 183 / 173)
+    const int aq = L <= 1536 ? 1 : 2;          // (L = 256: 27 / 18 us, L = 1024: 183 / 173)
     if (int rc = aq == 1 ? xm_launch<XM_SA, 1>(p, st, "extract_links_bwd(matrix-core SA)") : xm_launch<XM_SA, 2>(p, st, "extract_links_bwd(matrix-core SA)")) return rc;
     p.dout = grad_q;
     if (xm_bf16_contraction(L)) {

@@ -27,7 +27,7 @@ struct HgParams {
     float pre_slope, scale;
     int shifts[DSP_HG_MAX_TAPS];
     int min_shift, max_shift;
-    int dbg;                      // ablation bits (HG_ABLATE env, timing experiments only): 1 no staging loads, 2 no MFMA loop, 4 no epilogue
+    int dbg;                      // ablation bits (r01 timing experiments; the launcher passes 0): 1 no staging loads, 2 no MFMA loop, 4 no epilogue
     const int* lens; int len_mul; // per-sample valid input length = lens[b] * len_mul (NULL: T): rows beyond it are read as ZERO, so a
                                   // padded batch computes, on each sample's valid region, what the sample computes alone
 };
@@ -498,7 +498,7 @@ static int hg_conv_one(const void* x, const void* w, const float* bias, const vo
     p.x = (const _Float16*)x; p.w = (const _Float16*)w; p.bias = bias; p.res = (const _Float16*)res; p.out = (_Float16*)out;
     p.B = B; p.T = T; p.M = M; p.ntaps = ntaps; p.Tout = Tout; p.Cout = Cout; p.out_mode = out_mode; p.up_u = up_u; p.up_pad = up_pad;
     p.pre_slope = pre_slope; p.scale = scale; p.lens = lens; p.len_mul = len_mul;
-    { static int ablate = -1; if (ablate < 0) { const char* ab = getenv("HG_ABLATE"); ablate = ab ? atoi(ab) : 0; } p.dbg = ablate; }
+    p.dbg = 0;
     p.min_shift = p.max_shift = host_shifts[0];
     for (int k = 0; k < ntaps; ++k) { p.shifts[k] = host_shifts[k]; p.min_shift = min(p.min_shift, host_shifts[k]); p.max_shift = max(p.max_shift, host_shifts[k]); }
     // tile / wave-grid choices: sweeps r01e (tap-major weights) and r01f (fragment-order weights; 512-column tiles and MI=4 wave tiles

@@ -89,7 +89,8 @@ int dsp_logsoftmax_gather_bwd_lazy(void* logits_inout, int dtype,
  *   (the status words dsp_dag_last_launch_status reads are moved to a 256-byte library buffer on `stream` before the call returns: the
  *   workspace may be released, stream-ordered, at once) — so the launch (memset + kernels + that copy) can be captured in a hipGraph.
  *   workspace == NULL (or too small) selects a library-owned grow-only buffer per (device, stream) instead: not capturable.
- *   For dense windows (TR > 64) the size includes the stand-by log-space path's scratch (a B*L*TR*4-byte re-laid-out copy of links). */
+ *   The size is the largest take of the kernel families the calling thread's dispatch may choose for (B,T,L,TR), dense or pitched rows;
+ *   for dense windows it includes the stand-by log-space path's scratch (a B*L*TR*4-byte re-laid-out copy of links). */
 size_t dsp_dag_workspace_bytes(int B, int T, int L, int TR);
 int dsp_dag_loss_fwd(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                      float* alpha, float* beta, float* loss, int B, int T, int L, int TR,
@@ -97,11 +98,13 @@ int dsp_dag_loss_fwd(const float* match, const float* links, const int64_t* out_
 
 /* ... with ROW PITCHES (ABI 2).  ld_match / ld_ab = elements between consecutive target rows of match and of alpha / beta (batch stride =
  *   T * ld; dense tensors: ld = L, which is what dsp_dag_loss_fwd passes).  A graph length is floor(src_upsample * frames) — three graphs in
- *   four are not a multiple of 4 and their dense rows are not 16-byte aligned; a pitch rounded up to 4 keeps them aligned and the TR <= 32
- *   strip kernels (16-byte row loads) serve such a graph WITHOUT a padded copy of match / alpha / beta: columns L .. ld-1 are never read as
- *   data, alpha / beta come back -inf there.  dsp_logsoftmax_gather writes `match` with any pitch (its out_ss stride), so the gather can
- *   produce the pitched layout directly.  Only the TR <= 32 families take pitched rows (ld multiples of 4, >= L rounded up to 4, 16-byte
- *   aligned bases); every other window needs ld = L and the call fails with DSP_EINVAL otherwise.  Workspace: size it for L rounded up to 4.
+ *   four are not a multiple of 4 and their dense rows are not 16-byte aligned; a pitch rounded up to 4 keeps them aligned and the strip
+ *   kernels serve such a graph WITHOUT a padded copy of match / alpha / beta.  Columns of match past L are never read as data; alpha / beta
+ *   columns L .. round4(L)-1 come back -inf, and dsp_dag_loss_bwd_ld reads them as such (do not overwrite them between the two calls).
+ *   dsp_logsoftmax_gather writes `match` with any pitch (its out_ss stride), so the gather can produce the pitched layout directly.
+ *   Pitched rows are served for windows <= 128 (TR <= 32: ld multiples of 4, >= L rounded up to 4, 16-byte aligned bases; see
+ *   dsp_dag_pitch_supported); every other window needs ld = L and the call fails with DSP_EINVAL otherwise.  Workspace: size it for L
+ *   rounded up to 4.
  *   Reference contract this replaces: dag_loss.py:103-104 (`.contiguous()` on match_all / links before the CUDA call). */
 int dsp_dag_loss_fwd_ld(const float* match, int ld_match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                         float* alpha, float* beta, int ld_ab, float* loss, int B, int T, int L, int TR,
@@ -114,8 +117,9 @@ int dsp_dag_loss_bwd(const float* grad_out, const float* alpha, const float* bet
                      float* grad_match, float* grad_links, int B, int T, int L, int TR,
                      void* workspace, size_t workspace_bytes, dsp_stream_t stream);
 
-/* ... with row pitches (see dsp_dag_loss_fwd_ld): alpha / beta as the pitched forward left them (ld_ab), match with ld_match, grad_match
- *   written with ld_grad_match (columns past L inside the pitch may be written with unspecified values).  TR <= 32 only when ld_ab != L. */
+/* ... with row pitches (see dsp_dag_loss_fwd_ld): alpha / beta as the pitched forward left them (ld_ab, with their -inf columns
+ *   L .. round4(L)-1), match with ld_match, grad_match written with ld_grad_match (columns past L inside the pitch may be written with
+ *   unspecified values).  Windows <= 128 only when ld_ab != L. */
 int dsp_dag_loss_bwd_ld(const float* grad_out, const float* alpha, const float* beta, int ld_ab, const float* match, int ld_match,
                         const float* links, const int64_t* out_len, const int64_t* tgt_len,
                         float* grad_match, int ld_grad_match, float* grad_links, int B, int T, int L, int TR,
@@ -140,8 +144,9 @@ int dsp_dag_best_alignment_ws(const float* match, const float* links, const int6
                               float* alpha_max, int32_t* trace, int64_t* path, int B, int T, int L, int TR,
                               void* workspace, size_t workspace_bytes, dsp_stream_t stream);
 
-/* ... with row pitches (see dsp_dag_loss_fwd_ld): served by the values-only strip DP + lazy back-trace (TR <= 32, L <= 8192, i.e. where
- *   dsp_dag_alignment_trace_optional(L rounded up to 4, TR) is 1); `trace` is ignored there.  path stays dense [B,L]. */
+/* ... with row pitches (see dsp_dag_loss_fwd_ld): served by the values-only strip DPs + back-trace for windows <= 128 (TR <= 32: L <= 8192,
+ *   ld multiples of 4, 16-byte aligned bases; see dsp_dag_pitch_supported); `trace` is ignored there.  alpha_max columns L .. round4(L)-1
+ *   come back -inf.  path stays dense [B,L]. */
 int dsp_dag_best_alignment_ld(const float* match, int ld_match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                               float* alpha_max, int ld_alpha_max, int32_t* trace, int64_t* path, int B, int T, int L, int TR,
                               void* workspace, size_t workspace_bytes, dsp_stream_t stream);
@@ -188,27 +193,25 @@ int dsp_dag_backtrace_blocks(const float* alpha_max, const uint16_t* block_trace
 
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics (no reference counterpart).
- *   dsp_dag_set_option("dp_path", n) pins the DP kernel family FOR THE CALLING THREAD: 0 = auto, 1 = generic row-sequential /
- *   log-space dense, 2 = banded 2-column log-space strips, 4 = strip2 (2 vertices per lane), 5 = strip4g (exp-space, one exponent per
- *   lane group; the auto choice for TR <= 32), 7 = values-only max-DP strips + lazy back-trace (dag_best_alignment), 8 = strip2g / strip1g (r06: exp space,
- *   2 vertices x 64 transitions / 1 x 128 per lane; the auto choice of the forward for windows 33 .. 64 / 65 .. 128, where 2 / 9 keep the log-space
- *   strips / the dense-window kernels),
- *   9 = dense-window blocked products on the f32 matrix cores (the auto choice for TR > 64); used by tests to
- *   cross-check the families.  "k5_path": 0 = auto, 1 = tiled log-space grad_links kernel, 2 = exp-space (TR <= 32) / block products
+ *   dsp_dag_set_option(name, n) sets a kernel pin; tests use them to cross-check the kernel families.  Every pinned family gives results
+ *   within the tests' tolerance of the auto choice (bit-identical where noted).  Unknown names return DSP_EINVAL.
+ *   "dp_path" (FOR THE CALLING THREAD): the DP kernel families a launch may pick — 0 = auto, 1 = generic row-sequential / log-space dense,
+ *   2 = banded 2-column log-space strips, 4 = strip2 (2 vertices per lane, loader wave), 5 = strip4g (exp space, one exponent per lane group;
+ *   the auto choice of the forward for TR <= 32), 7 = values-only max-DP strips + back-trace (dag_best_alignment: the auto choice for TR <= 128
+ *   without a trace), 8 = strip2g / strip1g (exp space, 2 vertices x 64 transitions / 1 x 128 per lane: the auto choice of the forward for
+ *   windows 33 .. 64 / 65 .. 128), 9 = dense-window blocked products on the f32 matrix cores / blocked max-plus alignment (the auto choice
+ *   for TR > 128).  What the pinned families do not take runs on the generic kernels.
+ *   "k5_path": 0 = auto, 1 = tiled log-space grad_links kernel, 2 = exp-space (TR <= 32) / block products
  *   (TR > 64).  Windows 33 .. 128 with 16-byte aligned rows (r06): the TR <= 32 kernel with one plane of workgroups per block of 32 transitions, beta
  *   read 32 k columns to the right (family 6) — 3 pins it, auto takes it where its estimated cost is under the tiled kernel's (long target axes);
  *   the block products are the auto choice above 128 only.  "k5_fuse" 0|1|2|3 (r06): dsp_dag_loss_bwd on a banded graph (TR <= 32) asked for BOTH gradients — 0 = auto (2), 1 / 2 = ONE
  *   launch writes grad_match and grad_links (alpha, beta, match read once; match rows prefetched into registers with 4-row passes / by
- *   LDS-DMA with 3-row passes), 3 = the two launches of r01-r05 (K4, then K5); the three are bit-identical.  "dm_mt" 1|2: rows per chunk of the dense kernel in MFMA row tiles (default 2 = 32 rows), "dm_depth" 1|2: its register
- *   stages in flight with dm_mt 1 (9 with dm_mt 2: the one-workgroup-per-CU build), "force_generic", "dm_*" affect speed only.
- *   "dm_budget": the dense kernel hands a batch exp space cannot hold (finite transitions under e^-86, or more exact-redo work than
+ *   LDS-DMA with 3-row passes), 3 = the two launches of r01-r05 (K4, then K5); the three are bit-identical.
+ *   "dm_mt" (per thread) 0|2 / 1: 32- / 16-row chunks of the dense kernel (default 32); speed only.
+ *   "dm_budget" (per thread): the dense kernel hands a batch exp space cannot hold (finite transitions under e^-86, or more exact-redo work than
  *   one visited predecessor per (row, 64-column block)) to log-space stand-by kernels queued behind it — 0 = auto, n > 0 = that many
  *   visited predecessors, -1 = no stand-by (diagnostics only: such batches are then slow and their weakest terms unguarded).
- *   "mx_cpl" 0|1|2|4 (r04): vertices per lane of the banded max-DP (0 = auto: 4 when that still gives >= 200 workgroups, else 2; 1 exists
- *   for the co-residency measurement of profiles/r04_dp_coresidency.txt), "bt_ring" 1|0 (r04): the LDS-ring back-trace (TR == 32) or the
- *   r01-r03 window kernel — every combination returns bit-identical paths.
- *   "dm_mt" 3|4|14 (r05): 48- / 64-row chunks at two workgroups per CU, 64 rows at one — measurement builds, bit-identical, slower.
- *   "dx_mt" 0|1|2 (r05): rows per chunk of the dense max-plus alignment kernel in 16-row tiles (0 = auto: 2 for launches of >= 6 rounds of
+ *   "dx_mt" 0|1|2 (r05, per thread): rows per chunk of the dense max-plus alignment kernel in 16-row tiles (0 = auto: 2 for launches of >= 6 rounds of
  *   workgroups); bit-identical paths.  "xl_tile" n (r05): n > 0 forces the TILED extract_links kernels (include/daspeech_decode.h) with a tile
  *   of n slots on any window — by default they serve the windows whose one-image score tile does not fit LDS (TR above ~1100).
  *   "xl_mfma" -1|0|1 (r05): the matrix-core extract_links kernels (dsp_extract_links_ws / _bwd_ws) by size | never | wherever H = 8, CK = 64

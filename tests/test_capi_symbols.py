@@ -2,6 +2,7 @@
 include/daspeech_dag.h declares; the Python operator surface has the reference's eight names.  No compute calls."""
 import ctypes
 import inspect
+import json
 import os
 import re
 
@@ -102,5 +103,45 @@ def test_dispatch_questions_follow_the_window_and_the_kernel_pin(lib_path):
             assert 0 <= a <= b and a <= c, (TR, a, b, c)
             a = lib.dsp_dag_alignment_workspace_bytes(4, 50, 1030, TR); b = lib.dsp_dag_alignment_workspace_bytes(8, 50, 1030, TR)
             assert 0 <= a <= b, (TR, a, b)
+    finally:
+        _lib.set_option("dp_path", 0)
+
+
+def _estimate_sized_another_family(op, L, TR):
+    """Under the default dispatch: the windows where the recorded workspace estimate (hand-written, before the answers were derived from the
+    launchers) was not the take of the family that runs."""
+    if op == "fwd":
+        return (33 <= TR <= 128 and 128 <= L <= 20480      # the strips run; the estimate also counted the dense-window kernels
+                or TR > 128 and L < 128                    # the generic kernels run; the estimate sized the dense-window kernels
+                or TR > 128 and L > 20480)                 # nothing serves the shape (the generic kernel's LDS rows): 0
+    return (33 <= TR <= 128 and L * 4 <= 150 * 1024        # the values-only strips run; the estimate also counted banded / dense / generic
+            or L * 4 > 160 * 1024)                         # nothing serves the shape (the back-trace's row image): 0
+
+
+def test_dispatch_answers_match_the_recorded_ones(lib_path):
+    """The C ABI's dispatch questions against the answers recorded before kernel selection moved into one function per op
+    (tests/golden/dag_dispatch_answers.json, tests/golden/make_dispatch_answers.py): every yes / no answer is identical under every dp_path
+    pin.  The workspace answers are now the largest take of the families the selection may return; under the default dispatch they equal the
+    recorded ones except where the recorded estimate sized a family that does not run there."""
+    from daspeech_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "dag_dispatch_answers.json")) as f:
+        rec = json.load(f)
+    cols = {c: i for i, c in enumerate(rec["columns"])}
+    rows = rec["rows"]
+    assert len(rows) == 8 * 2 * 12 * 11
+    lib = _lib.load()
+    try:
+        for r in rows:
+            path, B, T, L, TR = r[:5]
+            _lib.set_option("dp_path", path)
+            got = [lib.dsp_dag_pitch_supported(0, L, TR), lib.dsp_dag_pitch_supported(1, L, TR), lib.dsp_dag_alignment_trace_optional(L, TR),
+                   lib.dsp_dag_max_alpha_blocks_supported(L, TR)]
+            assert got == r[cols["pitch_fwd"]:cols["blocks_supported"] + 1], r
+            if path != 0:
+                continue
+            for op, col, ws in (("fwd", "workspace_bytes", lib.dsp_dag_workspace_bytes(B, T, L, TR)),
+                                ("align", "alignment_workspace_bytes", lib.dsp_dag_alignment_workspace_bytes(B, T, L, TR))):
+                if not _estimate_sized_another_family(op, L, TR):
+                    assert ws == r[cols[col]], (op, r, ws)
     finally:
         _lib.set_option("dp_path", 0)

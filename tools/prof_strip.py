@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-wave cycle accounting of the strip4g DP kernel (GPU box only; run with DSP_DEBUG=prof).
+"""Per-wave cycle accounting of the strip4g DP kernel (GPU box only; run with DSP_DEBUG=prof; needs a library built with -DDSP_PROF: add
+`// HIPCC_FLAGS: -DDSP_PROF` to the header comment of csrc/dag_dp_strip4g.hip and rebuild).
 usage: DSP_DEBUG=prof python tools/prof_strip.py [B T L TR]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
