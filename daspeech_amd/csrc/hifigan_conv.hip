@@ -492,8 +492,10 @@ static int hg_conv_one(const void* x, const void* w, const float* bias, const vo
     if (B < 0 || T < 1 || M < 1 || ntaps < 1 || ntaps > DSP_HG_MAX_TAPS || !host_shifts) { set_error("hifigan_conv: bad sizes"); return DSP_EINVAL; }
     if (B == 0) return DSP_OK;
     if (!x || !w || !out) { set_error("hifigan_conv: null pointer"); return DSP_EINVAL; }
-    if ((Cout & 3) || (out_mode == DSP_HG_OUT_UPSAMPLE ? (M != up_u * Cout) : (M != Cout || Tout != T))) {
-        set_error("hifigan_conv: inconsistent M=%d Cout=%d mode=%d", M, Cout, out_mode); return DSP_EINVAL; }
+    // the epilogue moves 16-byte chunks of 8 halves per output row: Cout % 8 == 4 would spill half a chunk into the next row (and past
+    // the end of `out` on the last one)
+    if ((Cout & 7) || (out_mode == DSP_HG_OUT_UPSAMPLE ? (M != up_u * Cout) : (M != Cout || Tout != T))) {
+        set_error("hifigan_conv: inconsistent M=%d Cout=%d (a multiple of 8) mode=%d", M, Cout, out_mode); return DSP_EINVAL; }
     HgParams p;
     p.x = (const _Float16*)x; p.w = (const _Float16*)w; p.bias = bias; p.res = (const _Float16*)res; p.out = (_Float16*)out;
     p.B = B; p.T = T; p.M = M; p.ntaps = ntaps; p.Tout = Tout; p.Cout = Cout; p.out_mode = out_mode; p.up_u = up_u; p.up_pad = up_pad;

@@ -41,6 +41,78 @@ def _shifts_array(sh: List[int]):
     return (ctypes.c_int * len(sh))(*sh)
 
 
+def conv_layer_spec(m, ci_pad=None) -> dict:
+    """The tap description of a Conv1d module (no GPU needed): tap-major weight [K][Cout][Cin] in the module's dtype, bias, shifts
+    (k - (K-1)/2) * dilation, and the sizes / epilogue mode the layer record takes (include/daspeech_hifigan.h)."""
+    w = m.weight.detach()                                   # [Cout, Cin, K]
+    Cout, Cin, K = w.shape
+    if ci_pad and ci_pad != Cin:
+        w = torch.nn.functional.pad(w, (0, 0, 0, ci_pad - Cin))
+        Cin = ci_pad
+    d = m.dilation[0]
+    return dict(w=w.permute(2, 0, 1).contiguous(), bias=m.bias.detach() if m.bias is not None else None,
+                shifts=[(k - (K - 1) // 2) * d for k in range(K)], ntaps=K, CI=Cin, M=Cout, Cout=Cout, mode=OUT_STORE, u=1, pad=0, dil=d)
+
+
+def up_layer_spec(m) -> dict:
+    """The same for a ConvTranspose1d(kernel 2u, stride u, padding u/2): two taps with shifts {0, -1} over M = u * Cout phase-major rows
+    (tap j, row (r, co) holds kernel index k = j*u + r), scattered by OUT_UPSAMPLE to time q*u + r - pad."""
+    w = m.weight.detach()                                   # [Cin, Cout, K = 2u]
+    Cin, Cout, K = w.shape
+    u = m.stride[0]
+    assert K == 2 * u and m.padding[0] == (K - u) // 2, "expects the HiFi-GAN upsampler geometry (kernel 2u, pad u/2)"
+    return dict(w=w.permute(2, 1, 0).reshape(2, u * Cout, Cin).contiguous(),      # tap j, row (r, co): k = j*u + r
+                bias=m.bias.detach() if m.bias is not None else None,
+                shifts=[0, -1], ntaps=2, CI=Cin, M=u * Cout, Cout=Cout, mode=OUT_UPSAMPLE, u=u, pad=(K - u) // 2, dil=1)
+
+
+def fill_layer_desc(d: HgLayerDesc, x, w, bias, res, out, T, CI, M, shifts, pre_slope, scale, out_mode, up_u, up_pad, Tout, Cout,
+                    w2=None, bias2=None):
+    """Write one dsp_hg_layer record; pointers are device addresses (int) or None.  The only place that fills the struct."""
+    assert 1 <= len(shifts) <= MAX_TAPS
+    d.x, d.w, d.bias, d.res, d.out = x, w, bias, res, out
+    d.T, d.CI, d.M, d.ntaps = T, CI, M, len(shifts)
+    for k in range(MAX_TAPS):
+        d.shifts[k] = shifts[k] if k < len(shifts) else 0
+    d.pre_slope, d.scale = pre_slope, scale
+    d.out_mode, d.up_u, d.up_pad, d.Tout, d.Cout = out_mode, up_u, up_pad, Tout, Cout
+    d.w2, d.bias2 = w2, bias2
+    return d
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def launch_layer(x: Tensor, w: Tensor, bias, res, out: Tensor, shifts, pre_slope: float = 1.0, scale: float = 1.0, out_mode: int = OUT_STORE,
+                 up_u: int = 1, up_pad: int = 0, M: int = None, w2: Tensor = None, bias2=None, lens: Tensor = None, T0: int = 0,
+                 check: bool = True) -> int:
+    """ONE dsp_hg_layer record through the chain entry points: x / res / out fp32 [B,T,C] and w (w2) packed [hi | lo] buffers ->
+    dsp_hifigan_conv_chain_f32; fp16 tensors and pack_weights buffers -> dsp_hifigan_conv_chain[_lens].  w2 != None makes the record a
+    fused ResBlock unit.  lens [B] int32 with the padded frame count T0 masks per utterance.  Returns the status code; raises on a
+    non-zero one unless check=False (dsp_last_error() then holds the message)."""
+    lib = _lib.load()
+    assert x.dim() == 3 and out.dim() == 3 and x.is_cuda and x.is_contiguous() and out.is_contiguous()
+    assert x.dtype in (torch.float32, torch.float16) and out.dtype == x.dtype and (res is None or res.dtype == x.dtype)
+    assert w.dtype == torch.float16 and (w2 is None or w2.dtype == torch.float16)
+    B, T, CI = x.shape
+    Tout, Cout = out.shape[1], out.shape[2]
+    table = (HgLayerDesc * 1)()
+    fill_layer_desc(table[0], x.data_ptr(), w.data_ptr(), _addr(bias), _addr(res), out.data_ptr(), T, CI, Cout * up_u if M is None else M,
+                    list(shifts), float(pre_slope), float(scale), int(out_mode), int(up_u), int(up_pad), Tout, Cout, _addr(w2), _addr(bias2))
+    with torch.cuda.device(x.device):
+        st = _lib.current_stream_handle()
+        if x.dtype == torch.float32:
+            rc, what = lib.dsp_hifigan_conv_chain_f32(table, 1, B, _lib.ptr(lens), int(T0), st), "dsp_hifigan_conv_chain_f32"
+        elif lens is None:
+            rc, what = lib.dsp_hifigan_conv_chain(table, 1, B, st), "dsp_hifigan_conv_chain"
+        else:
+            rc, what = lib.dsp_hifigan_conv_chain_lens(table, 1, B, _lib.ptr(lens), int(T0), st), "dsp_hifigan_conv_chain_lens"
+    if check:
+        _lib.check(rc, what)
+    return rc
+
+
 def pack_weights(w_tap_major: Tensor) -> Tensor:
     """[ntaps][M][CI] fp16 -> the MFMA fragment order the kernels read (include/daspeech_hifigan.h: dsp_hifigan_pack_weights)."""
     lib = _lib.load()
@@ -99,31 +171,19 @@ class HiFiGANHipRunner:
         else:
             L.w, L.w_lo = pack_weights(w_tap_major.to(torch.float16)), None
 
-    def _conv_layer(self, m, ci_pad=None):
+    def _layer(self, spec: dict):
         L = _Layer()
-        w = m.weight.detach()                                   # [Cout, Cin, K]
-        Cout, Cin, K = w.shape
-        if ci_pad and ci_pad != Cin:
-            w = torch.nn.functional.pad(w, (0, 0, 0, ci_pad - Cin))
-            Cin = ci_pad
-        self._pack(L, w.permute(2, 0, 1).contiguous())
-        L.bias = m.bias.detach().float().contiguous() if m.bias is not None else None
-        d = m.dilation[0]
-        L.shifts = [(k - (K - 1) // 2) * d for k in range(K)]
-        L.ntaps, L.CI, L.M, L.Cout, L.mode, L.u, L.pad, L.dil = K, Cin, Cout, Cout, OUT_STORE, 1, 0, d
+        self._pack(L, spec["w"])
+        L.bias = spec["bias"].float().contiguous() if spec["bias"] is not None else None
+        L.shifts, L.ntaps, L.CI, L.M, L.Cout = spec["shifts"], spec["ntaps"], spec["CI"], spec["M"], spec["Cout"]
+        L.mode, L.u, L.pad, L.dil = spec["mode"], spec["u"], spec["pad"], spec["dil"]
         return L
 
+    def _conv_layer(self, m, ci_pad=None):
+        return self._layer(conv_layer_spec(m, ci_pad))
+
     def _up_layer(self, m):
-        L = _Layer()
-        w = m.weight.detach()                                   # [Cin, Cout, K = 2u]
-        Cin, Cout, K = w.shape
-        u = m.stride[0]
-        assert K == 2 * u and m.padding[0] == (K - u) // 2, "expects the HiFi-GAN upsampler geometry (kernel 2u, pad u/2)"
-        self._pack(L, w.permute(2, 1, 0).reshape(2, u * Cout, Cin).contiguous())      # tap j, row (r, co): k = j*u + r
-        L.bias = m.bias.detach().float().contiguous() if m.bias is not None else None
-        L.shifts = [0, -1]
-        L.ntaps, L.CI, L.M, L.Cout, L.mode, L.u, L.pad = 2, Cin, u * Cout, Cout, OUT_UPSAMPLE, u, (K - u) // 2
-        return L
+        return self._layer(up_layer_spec(m))
 
     def _run(self, L, x: Tensor, slope: float, res: Tensor = None, out: Tensor = None, mode=None, scale: float = 1.0) -> Tensor:
         B, T, CI = x.shape
@@ -220,16 +280,10 @@ class HiFiGANHipRunner:
         for d, rec in zip(table, recs):
             L, xb, rb, ob, tt, slope, mode, scale = rec[:8]
             L2 = rec[8] if len(rec) > 8 else None
-            d.w2 = L2.w.data_ptr() if L2 is not None else None
-            d.bias2 = L2.bias.data_ptr() if (L2 is not None and L2.bias is not None) else None
-            d.x = base + esz * offs[xb]; d.res = (base + esz * offs[rb]) if rb is not None else None; d.out = base + esz * offs[ob]
-            d.w = L.w.data_ptr(); d.bias = L.bias.data_ptr() if L.bias is not None else None
-            d.T, d.CI, d.M, d.ntaps = tt, L.CI, L.M, L.ntaps
-            for k, sh in enumerate(L.shifts):
-                d.shifts[k] = sh
-            d.pre_slope, d.scale = slope, scale
-            d.out_mode = L.mode if mode is None else mode
-            d.up_u, d.up_pad, d.Tout, d.Cout = L.u, L.pad, (tt * L.u if L.mode == OUT_UPSAMPLE else tt), L.Cout
+            ptr = lambda k: (base + esz * offs[k]) if k is not None else None      # noqa: E731
+            fill_layer_desc(d, ptr(xb), L.w.data_ptr(), _addr(L.bias), ptr(rb), ptr(ob), tt, L.CI, L.M, L.shifts, slope, scale,
+                            L.mode if mode is None else mode, L.u, L.pad, (tt * L.u if L.mode == OUT_UPSAMPLE else tt), L.Cout,
+                            L2.w.data_ptr() if L2 is not None else None, _addr(L2.bias) if L2 is not None else None)
         plan = (ws, table, base + esz * offs[x_first], base + esz * offs[x], t, self.ups[-1].Cout if self.ups else self.pre.Cout)
         if len(self._plans) >= 32:
             self._plans.pop(next(iter(self._plans)))

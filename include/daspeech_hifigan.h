@@ -33,7 +33,8 @@ int dsp_hifigan_pack_weights(const void* w_tap_major, void* out, int ntaps, int 
 
 /* x [B,T,CI] fp16 (CI multiple of 32 in {32,64,96,128,256,512}); w packed from [ntaps,M,CI] fp16; bias [Cout] fp32 or NULL;
  * res [B,Tout,Cout] fp16 or NULL (added before `scale`); out [B,Tout,Cout] fp16; v = scale * (acc + bias + res).
- * pre_slope: leaky_relu slope applied to x while staging (1.0 = none).  For STORE/ACCUM Tout == T and Cout == M. */
+ * pre_slope: leaky_relu slope applied to x while staging (1.0 = none).  For STORE/ACCUM Tout == T and Cout == M.  Cout is a multiple of 8
+ * (the fp32 chain below: of 4); anything else is refused with DSP_EINVAL. */
 int dsp_hifigan_conv(const void* x, const void* w, const float* bias, const void* res, void* out,
                      int B, int T, int CI, int M, int ntaps, const int* host_shifts, float pre_slope, float scale,
                      int out_mode, int up_u, int up_pad, int Tout, int Cout, dsp_stream_t stream);

@@ -20,6 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ("fuzz_layers.py", ["30", "6"]),                 # split-precision conv / GEMM tiles, layer norm, depthwise conv + BN + SiLU
     ("fuzz_tts_glue.py", ["40", "4"]),               # length regulator, durations, bucketize + embed, posterior / expected features
     ("fuzz_attention.py", ["30", "1"]),              # matrix-core attention / relative-position attention / feed-forward module / ragged tiles
+    ("fuzz_vocoder.py", ["6", "10"]),                # HiFi-GAN fp32 chain: padded batch == alone, zero past the length, 1e-4 of torch fp32
+    ("fuzz_vocoder.py", ["6", "11", "hip_fp16"]),    # the same on fp16 storage (2e-2 max / 2e-3 mean)
 ])
 def test_randomised_sweep(tool, args):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool)] + args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,

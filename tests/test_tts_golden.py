@@ -94,9 +94,13 @@ def test_hifigan_gpu_torch_backend(golden_dir):
 
 
 @pytest.mark.gpu
-def test_hifigan_hip_matches_torch_fp32():
-    """Hand-written MFMA conv stack (fp16 storage, fp32 accumulate) vs the fp32 torch path of the same V1 generator."""
+@pytest.mark.parametrize("backend", ["hip", "hip_fp16"])
+def test_hifigan_hip_matches_torch_fp32(backend):
+    """Hand-written MFMA conv stack vs the fp32 torch path of the same V1 generator.  "hip_fp16": fp16 storage, fp32 accumulate (max 2e-2,
+    mean 2e-3); "hip": the split-operand fp32 chain, held to what the project claims for it on random weights (1e-4 vs torch fp32, as
+    test_hifigan_fp32_mode_grouped_equals_per_utterance_and_tracks_torch_fp32)."""
     from daspeech_amd.models import HiFiGANGenerator
+    max_tol, mean_tol = (1e-4, 1e-4) if backend == "hip" else (2e-2, 2e-3)
     torch.manual_seed(3)
     g = HiFiGANGenerator().cuda().eval()                      # full V1 widths (512 initial channels)
     with torch.no_grad():
@@ -109,17 +113,18 @@ def test_hifigan_hip_matches_torch_fp32():
     mel = torch.randn(2, 80, 37, device="cuda")
     with torch.no_grad():
         ref = g(mel)
-        g.conv_backend = "hip"
+        g.conv_backend = backend
         out = g(mel)
     assert out.shape == ref.shape == (2, 1, 37 * 256)
     err = (out - ref).abs().max().item()
-    assert err < 2e-2 and torch.isfinite(out).all(), err
-    assert (out - ref).abs().mean().item() < 2e-3
+    print(f"\n[hifigan-generator] {backend} vs torch fp32: max {err:.3e} mean {(out - ref).abs().mean().item():.3e}")
+    assert err < max_tol and torch.isfinite(out).all(), err
+    assert (out - ref).abs().mean().item() < mean_tol
     # odd lengths / tile edges
     mel2 = torch.randn(1, 80, 5, device="cuda")
     with torch.no_grad():
         out2 = g(mel2); g.conv_backend = "torch"; ref2 = g(mel2)
-    assert (out2 - ref2).abs().max().item() < 2e-2
+    assert (out2 - ref2).abs().max().item() < max_tol
 
 
 @pytest.mark.gpu
