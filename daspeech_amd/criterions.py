@@ -183,7 +183,7 @@ class NATDAGLoss:
                 outputs, match_all = custom_ops.dag_logsoftmax_gather_inplace(outputs, idx)
             finally:
                 custom_ops.set_lazy_softmax(prev_mode)
-        match_all = match_all.transpose(1, 2)                                                   # [B,T,L], already contiguous
+        match_all = match_all.transpose(1, 2)                                                   # [B,T,L]: no copy (fp32: rows pitched to 4; float64: dense)
         if matchmask is not None and not self.cfg.no_force_emit:                                # force-emit (:130-132)
             glat_prev_mask = keep_word_mask.unsqueeze(1)
             match_all = match_all.masked_fill(glat_prev_mask, 0) + \

@@ -14,9 +14,14 @@ The first four run hand-written HIP kernels (gfx950) through the C ABI of includ
 the shared library is missing or the tensors are not on a GPU — there is NO silent fallback to the torch path.
 Differences from the reference, all deliberate and documented in DESIGN.md:
   * kernels run on torch's CURRENT stream (the reference used legacy stream 0 + private streams);
-  * `match` returned by dag_logsoftmax_gather_inplace is a [B,L,S]-shaped *view* of a contiguous [B,S,L] buffer, so
-    the caller's `.transpose(1, 2)` (nat_dag_loss.py:128) is already contiguous and dag_loss's `.contiguous()` copies
-    nothing; values are identical;
+  * `match` returned by dag_logsoftmax_gather_inplace is a [B,L,S]-shaped *view* of a [B,S,L] buffer, so the caller's
+    `.transpose(1, 2)` (nat_dag_loss.py:128) needs no transpose copy; values are identical.  For fp32 / fp16 / bf16 logits the
+    buffer is fp32 with rows PITCHED to a multiple of 4 (contiguous only when L is one; the DP takes the pitch, see _row_pitch);
+    for float64 logits it is a DENSE float64 buffer, so the transpose is contiguous and dag_double's `.contiguous()` copies nothing;
+  * dtypes: fp32 / fp16 / bf16 logits run the fp32 kernels (csrc/logsoftmax_gather.hip; `match` fp32, the softmax / gradient left in
+    the logits' dtype); float64 logits run the double kernels (csrc/logsoftmax_gather_f64.hip; every intermediate, `match`, the row
+    statistics and the gradient in double) and feed the double DP of dag_double.py.  torch_dag_logsoftmax_gather_inplace stays the
+    reference's log_softmax(dtype=torch.float), and decode_ops.posterior_features still computes in fp32 on double alpha / beta;
   * invalid samples (unreachable end, bad lengths) give -inf / zero gradients instead of device asserts
     (dag_loss.cu:68-69) — the criteria already zero non-finite losses (nat_dag_loss.py:143-145);
   * Viterbi ties follow the torch implementation's rule (smallest predecessor index), see SURVEY.md §7.
@@ -335,14 +340,17 @@ def set_lazy_softmax(flag: bool) -> bool:
     return prev
 
 
-def _lsg_check(word_ins_out: Tensor, select_idx: Tensor):
+def _lsg_check(word_ins_out: Tensor, select_idx: Tensor, f64: bool = False):
+    """Argument checks of the gather launches -> (device, dtype code, B, L, V, S).  `f64`: the double launches (no dtype code: they have entry
+    points of their own)."""
     dev = _require_gpu("dag_logsoftmax_gather_inplace", word_ins_out, select_idx)
     if word_ins_out.dim() != 3 or select_idx.dim() != 3:
         raise RuntimeError("dag_logsoftmax_gather_inplace: word_ins_out and select_idx must be 3-D")
     if not word_ins_out.is_contiguous():
         raise RuntimeError("dag_logsoftmax_gather_inplace: word_ins_out must be contiguous (it is modified in place)")
-    code = _lib.DTYPE_CODES.get(str(word_ins_out.dtype))
-    if code is None:
+    code = None if f64 else _lib.DTYPE_CODES.get(str(word_ins_out.dtype))
+    served = (word_ins_out.dtype == torch.float64) if f64 else (code is not None)
+    if not served:
         raise RuntimeError(f"dag_logsoftmax_gather_inplace: unsupported dtype {word_ins_out.dtype}")
     if select_idx.dtype != torch.long:
         raise RuntimeError("dag_logsoftmax_gather_inplace: select_idx must be int64")
@@ -408,13 +416,59 @@ def _lsg_backward(softmax_inout: Tensor, select_idx: Tensor, grad_match_bls: Ten
     return softmax_inout
 
 
+# ---- float64 logits: the double-precision kernels of csrc/logsoftmax_gather_f64.hip.  Launch helpers of their own — the fp32 helpers
+# above index _lib.DTYPE_CODES, which has (and keeps) no double entry, so a double tensor cannot reach an fp32 launch.
+
+def _lsg64_forward(word_ins_out: Tensor, select_idx: Tensor, write_softmax: bool, lazy: bool):
+    """Double K1 launch: returns (DENSE [B,S,L] float64 match buffer — the double DP kernels take dense tensors, no row pitch —, row statistics
+    [B,L,2] float64 (max, 1/sum-exp) when `lazy`, else None); word_ins_out becomes softmax if write_softmax."""
+    dev, _, B, L, V, S = _lsg_check(word_ins_out, select_idx, f64=True)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        buf = torch.empty((B, S, L), dtype=torch.float64, device=dev)
+        stats = torch.empty((B, L, 2), dtype=torch.float64, device=dev) if lazy else None
+        isb, isj, iss = _elem_strides(select_idx)
+        rc = lib.dsp_logsoftmax_gather_f64(_lib.ptr(word_ins_out), _lib.ptr(select_idx), isb, isj, iss, _lib.ptr(buf), S * L, 1, L,
+                                           _lib.ptr(stats), B, L, V, S, 1 if (write_softmax and not lazy) else 0,
+                                           _lib.current_stream_handle())
+        _lib.check(rc, "dsp_logsoftmax_gather_f64")
+    return buf, stats
+
+
+def _lsg64_backward(inout: Tensor, select_idx: Tensor, grad_match_bls: Tensor, stats: Tensor = None) -> Tensor:
+    """Double K1 backward launch: inout [B,L,V] float64 (softmax, or the logits when `stats` is given) -> d/d logits in place;
+    grad_match_bls is [B,L,S]-shaped, any strides, any float dtype (WIDENED to double, never narrowed)."""
+    if inout.dtype != torch.float64:
+        raise RuntimeError("internal: the float64 gather backward got " + str(inout.dtype))
+    B, L, V = inout.shape
+    S = select_idx.shape[2]
+    g = grad_match_bls.detach()
+    if g.dtype != torch.float64:
+        g = g.double()
+    lib = _lib.load()
+    with torch.cuda.device(inout.device):
+        isb, isj, iss = _elem_strides(select_idx)
+        gsb, gsj, gss = _elem_strides(g)
+        rc = lib.dsp_logsoftmax_gather_bwd_f64(_lib.ptr(inout), _lib.ptr(select_idx), isb, isj, iss, _lib.ptr(g), gsb, gsj, gss,
+                                               _lib.ptr(stats), B, L, V, S, _lib.current_stream_handle())
+        _lib.check(rc, "dsp_logsoftmax_gather_bwd_f64")
+    return inout
+
+
 class DagLogsoftmaxGatherFunc(Function):
+    """`dag_logsoftmax_gather_inplace` (dag_loss.py:238-299).  fp32 / fp16 / bf16 logits: fp32 kernels, `match` fp32.  float64 logits: the
+    double kernels, `match` float64 (the reference's double instantiation, logsoftmax_gather.cu:340-347) — same contract otherwise.
+    Unchanged on purpose: torch_dag_logsoftmax_gather_inplace keeps the reference's log_softmax(dtype=torch.float) for every input dtype, and
+    decode_ops.posterior_features computes in fp32 on double alpha / beta."""
 
     @staticmethod
     def forward(ctx, word_ins_out, select_idx):
         need = ctx.needs_input_grad[0]
         ctx.lazy = bool(need and LAZY_SOFTMAX)
-        if ctx.lazy:
+        ctx.f64 = word_ins_out.dtype == torch.float64
+        if ctx.f64:
+            buf, stats = _lsg64_forward(word_ins_out, select_idx, need, ctx.lazy)
+        elif ctx.lazy:
             buf, stats = _lsg_forward_lazy(word_ins_out, select_idx)
         else:
             buf, stats = _lsg_forward(word_ins_out, select_idx, need), None
@@ -442,11 +496,12 @@ class DagLogsoftmaxGatherFunc(Function):
             return None, None
         assert not ctx.has_backward, "Cannot backward twice in logsoftmax_gather"
         ctx.has_backward = True
+        bwd = _lsg64_backward if ctx.f64 else _lsg_backward
         if ctx.lazy:
             grad_input, select_idx, stats = ctx.saved_tensors     # holds the logits, becomes the gradient in place
-            return _lsg_backward(grad_input, select_idx, grad_output, stats).detach(), None
+            return bwd(grad_input, select_idx, grad_output, stats).detach(), None
         grad_input, select_idx = ctx.saved_tensors        # holds softmax, becomes the gradient in place
-        return _lsg_backward(grad_input, select_idx, grad_output).detach(), None
+        return bwd(grad_input, select_idx, grad_output).detach(), None
 
 
 dag_logsoftmax_gather_inplace = DagLogsoftmaxGatherFunc.apply

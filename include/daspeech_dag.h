@@ -78,8 +78,32 @@ int dsp_logsoftmax_gather_bwd_lazy(void* logits_inout, int dtype,
                                    const float* g, int64_t g_sb, int64_t g_sj, int64_t g_ss,
                                    const float* row_stats, int B, int L, int V, int S, dsp_stream_t stream);
 
+/* K1 and its backward in DOUBLE precision (csrc/logsoftmax_gather_f64.hip) — the reference dispatches its gather for double as well
+ *   (logsoftmax_gather.cu:46-58,340-347: `selected_result` is at::kDouble).  Every intermediate is a double, accurate exp / log only.
+ *   logits    [B,L,V] contiguous doubles (8-byte aligned; rows of an odd V are served with 16-byte loads after one peeled element).
+ *   idx       as for dsp_logsoftmax_gather (element strides; indices outside [0,V) are clamped).
+ *   match     DOUBLE, written at match[b*out_sb + j*out_sj + s*out_ss].
+ *   The three forward modes in one entry point:
+ *     write_softmax != 0, row_stats == NULL   logits are OVERWRITTEN with softmax(logits) (the reference's in-place contract);
+ *     write_softmax == 0, row_stats != NULL   "lazy": logits untouched, row_stats[(b*L+j)*2] = max, [..+1] = 1 / sum exp(x - max), doubles;
+ *     write_softmax == 0, row_stats == NULL   nothing but `match` is written (no gradient wanted);
+ *     both set                                DSP_EINVAL.
+ *   dsp_logsoftmax_gather_bwd_f64 overwrites `inout` [B,L,V] with d loss / d logits:
+ *       gx = softmax * (-(sum_s g[b,j,s]));  gx[b,j,idx[b,j,s]] += g[b,j,s]   (duplicates accumulate)
+ *     where softmax is the content of `inout` (row_stats == NULL, left there by write_softmax) or exp(inout - max) * inv from the `row_stats`
+ *     of the lazy forward (`inout` then holds the logits).  g DOUBLE, addressed with element strides like `match`.  Any V >= 1 (the scatter
+ *     image in LDS covers a column chunk at a time). */
+int dsp_logsoftmax_gather_f64(double* logits,
+                              const int64_t* idx, int64_t idx_sb, int64_t idx_sj, int64_t idx_ss,
+                              double* match, int64_t out_sb, int64_t out_sj, int64_t out_ss,
+                              double* row_stats, int B, int L, int V, int S, int write_softmax, dsp_stream_t stream);
+int dsp_logsoftmax_gather_bwd_f64(double* inout,
+                                  const int64_t* idx, int64_t idx_sb, int64_t idx_sj, int64_t idx_ss,
+                                  const double* g, int64_t g_sb, int64_t g_sj, int64_t g_ss,
+                                  const double* row_stats, int B, int L, int V, int S, dsp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
- * K2/K3  forward / backward DP       replaces `dag_loss` (dag_loss.cpp:25; dag_loss.cu:313-375)
+ * K2/K3 forward / backward DP       replaces `dag_loss` (dag_loss.cpp:25; dag_loss.cu:313-375)
  *   match [B,T,L] fp32, links [B,L,TR] fp32 (links[b,i,d] = log P(i -> i+d+1)), out_len/tgt_len int64 [B].
  *   alpha [B,T,L] fp32 out; beta [B,T,L] fp32 out or NULL (= the reference's require_gradient=false).
  *   loss  [B] fp32 out or NULL: beta[b,0,0] when beta != NULL else alpha[b,T_b-1,L_b-1] (dag_loss.py:107-110).
@@ -159,7 +183,8 @@ int dsp_dag_pitch_supported(int op, int L, int TR);
  * The three DP operators in DOUBLE precision (r06; csrc/dag_dp_f64.hip) — the reference dispatches its kernels for double as well
  * (AT_DISPATCH_FLOATING_TYPES_AND_HALF, dag_loss.cu:160,294,415,499, dag_best_alignment.cu:143,219).  Dense [B,T,L] / [B,L,TR] double tensors,
  * every intermediate a double, log space, one workgroup per (sample, direction): a correctness path (L <= 10240), not a fast one.  Same
- * semantics as the fp32 entry points; dsp_dag_best_alignment_f64 always needs its int32 trace [B,T,L]. */
+ * semantics as the fp32 entry points; dsp_dag_best_alignment_f64 always needs its int32 trace [B,T,L].  The operator that feeds them, K1, has
+ * its double form above (dsp_logsoftmax_gather_f64 / _bwd_f64): a [B,S,L] dense double `match` goes straight into these. */
 int dsp_dag_loss_fwd_f64(const double* match, const double* links, const int64_t* out_len, const int64_t* tgt_len,
                          double* alpha, double* beta, double* loss, int B, int T, int L, int TR, dsp_stream_t stream);
 int dsp_dag_loss_bwd_f64(const double* grad_out, const double* alpha, const double* beta, const double* match, const double* links,
