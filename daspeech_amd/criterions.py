@@ -321,7 +321,9 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
             input_to_tts = model.adaptor(features_on_path)
         else:
             # expect: z_i = sum_j P(a_i = j | x, y) v_j   (:252-265)
-            # (fused: the [B,T,L] posterior never exists; gradient to the features through dsp_posterior_features_bwd)
+            # (fused: the [B,T,L] posterior never exists; gradient to the features through dsp_posterior_features_bwd; float64 alpha / beta —
+            #  a double-precision run of the DAG chain — take the double kernels dsp_posterior_features_f64 / _bwd_f64 and keep their accuracy:
+            #  the result comes back in the features' dtype, so double features give a full double TTS input)
             # (without a gradient — validation, or --dag-freezing-steps not yet passed — the reference's beta is all zeros, dag_loss.cu:340, and
             #  so is the one handed back here: the "posterior" is then soft-max_j alpha[t, j], as in the reference)
             input_to_tts = model.adaptor(decode_ops.posterior_features(alpha, beta, features)[:, 1:, :])

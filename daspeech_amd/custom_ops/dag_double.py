@@ -13,7 +13,11 @@ double tensor silently would hand back fp32 accuracy under a float64 dtype.  Dou
 
 Semantics follow the kernels (dag_loss.cu:40-140 alpha, :178-274 beta, dag_best_alignment.cu:39-253): cells outside
 {t < T_b, t <= j < L_b} are -inf, an all -inf predecessor set stays -inf (no emission added), Viterbi ties take the smallest predecessor
-index, vertices off the path are -1."""
+index, vertices off the path are -1.
+
+The double chain continues through the expect step: decode_ops.posterior / posterior_features / expect_features take the float64
+(alpha, beta) of dag_loss_with_alpha_beta on the double kernels of csrc/posterior_f64.hip and return a float64 score (the product in the
+features' dtype) — the reference computes that step in the dtype of alpha."""
 import torch
 from torch import Tensor
 

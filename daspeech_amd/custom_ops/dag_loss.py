@@ -21,7 +21,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   * dtypes: fp32 / fp16 / bf16 logits run the fp32 kernels (csrc/logsoftmax_gather.hip; `match` fp32, the softmax / gradient left in
     the logits' dtype); float64 logits run the double kernels (csrc/logsoftmax_gather_f64.hip; every intermediate, `match`, the row
     statistics and the gradient in double) and feed the double DP of dag_double.py.  torch_dag_logsoftmax_gather_inplace stays the
-    reference's log_softmax(dtype=torch.float), and decode_ops.posterior_features still computes in fp32 on double alpha / beta;
+    reference's log_softmax(dtype=torch.float); decode_ops.posterior / posterior_features take the double alpha / beta on double kernels too
+    (csrc/posterior_f64.hip);
   * invalid samples (unreachable end, bad lengths) give -inf / zero gradients instead of device asserts
     (dag_loss.cu:68-69) — the criteria already zero non-finite losses (nat_dag_loss.py:143-145);
   * Viterbi ties follow the torch implementation's rule (smallest predecessor index), see SURVEY.md §7.
@@ -458,8 +459,7 @@ def _lsg64_backward(inout: Tensor, select_idx: Tensor, grad_match_bls: Tensor, s
 class DagLogsoftmaxGatherFunc(Function):
     """`dag_logsoftmax_gather_inplace` (dag_loss.py:238-299).  fp32 / fp16 / bf16 logits: fp32 kernels, `match` fp32.  float64 logits: the
     double kernels, `match` float64 (the reference's double instantiation, logsoftmax_gather.cu:340-347) — same contract otherwise.
-    Unchanged on purpose: torch_dag_logsoftmax_gather_inplace keeps the reference's log_softmax(dtype=torch.float) for every input dtype, and
-    decode_ops.posterior_features computes in fp32 on double alpha / beta."""
+    Unchanged on purpose: torch_dag_logsoftmax_gather_inplace keeps the reference's log_softmax(dtype=torch.float) for every input dtype."""
 
     @staticmethod
     def forward(ctx, word_ins_out, select_idx):

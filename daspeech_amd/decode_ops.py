@@ -3,6 +3,9 @@
 Host-side mirror of the reference code these replace:
   graph_decode        DASpeech/models/s2s_conformer_dag_fastspeech2.py:201-243 (lookahead / greedy branch of forward_decoder)
   posterior / expect_features   DASpeech/criterions/s2s_dag_fastspeech2_loss.py:259-263
+                      (float64 alpha or beta: the double kernels of csrc/posterior_f64.hip — the reference computes the posterior in the
+                      dtype of alpha, so the double DAG chain of custom_ops/dag_double.py continues through this step; every other
+                      dtype takes the fp32 kernels, as before)
   predicted_durations / bucketize_embed_add / length_regulate   fairseq/fairseq/models/text_to_speech/fastspeech2.py:98-114,169-210
 No CPU fallback: GPU tensors only.
 """
@@ -192,9 +195,26 @@ def extract_links_autograd(q: Tensor, k: Tensor, log_gates: Tensor, output_lengt
     return _ExtractLinksFn.apply(q, k, log_gates, output_length, int(TR), dist_bias)
 
 
+def _is_f64(alpha: Tensor, beta: Tensor) -> bool:
+    """float64 alpha or beta: the step runs on the double kernels (the other one is widened, which is exact) — narrowing a double tensor
+    silently would hand back fp32 accuracy under a float64 dtype"""
+    return alpha.dtype == torch.float64 or beta.dtype == torch.float64
+
+
 def posterior(alpha: Tensor, beta: Tensor) -> Tensor:
-    """score = exp(alpha + beta - logsumexp_j(alpha + beta)), NaN -> 0   (s2s_dag_fastspeech2_loss.py:259-260)."""
+    """score = exp(alpha + beta - logsumexp_j(alpha + beta)), NaN -> 0   (s2s_dag_fastspeech2_loss.py:259-260).  fp32, or float64 when
+    alpha or beta is float64 (dsp_posterior_f64)."""
     _gpu("posterior", alpha, beta)
+    if _is_f64(alpha, beta):
+        a = alpha.detach().to(torch.float64).contiguous()
+        b = beta.detach().to(torch.float64).contiguous()
+        B, T, L = a.shape
+        lib = _lib.load()
+        with torch.cuda.device(a.device):
+            score = torch.empty_like(a)
+            _lib.check(lib.dsp_posterior_f64(_lib.ptr(a), _lib.ptr(b), _lib.ptr(score), B, T, L, _lib.current_stream_handle()),
+                       "dsp_posterior_f64")
+        return score
     a = alpha.detach().to(torch.float32).contiguous()
     b = beta.detach().to(torch.float32).contiguous()
     B, T, L = a.shape
@@ -241,10 +261,51 @@ class _PosteriorFeaturesFn(torch.autograd.Function):
         return None, None, df.to(ctx.fdtype)
 
 
+class _PosteriorFeaturesF64Fn(torch.autograd.Function):
+    """_PosteriorFeaturesFn for float64 alpha / beta (dsp_posterior_features_f64 / _bwd_f64): alpha, beta and the row log-sum-exps are saved
+    in double, the features of any floating dtype are widened for the product, result and gradient come back in the features' dtype."""
+
+    @staticmethod
+    def forward(ctx, alpha, beta, features):
+        a = alpha.detach().to(torch.float64).contiguous()
+        b = beta.detach().to(torch.float64).contiguous()
+        f = features.detach().to(torch.float64).contiguous()
+        B, T, L = a.shape
+        D = f.shape[2]
+        lib = _lib.load()
+        with torch.cuda.device(a.device):
+            out = torch.empty((B, T, D), dtype=torch.float64, device=a.device)
+            lse = torch.empty((B, T), dtype=torch.float64, device=a.device)
+            _lib.check(lib.dsp_posterior_features_f64(_lib.ptr(a), _lib.ptr(b), _lib.ptr(f), _lib.ptr(out), _lib.ptr(lse), B, T, L, D,
+                                                      _lib.current_stream_handle()), "dsp_posterior_features_f64")
+        ctx.save_for_backward(a, b, lse)
+        ctx.fdtype = features.dtype
+        return out.to(features.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, b, lse = ctx.saved_tensors
+        B, T, L = a.shape
+        g = grad_out.detach().to(torch.float64).contiguous()
+        D = g.shape[2]
+        lib = _lib.load()
+        with torch.cuda.device(a.device):
+            df = torch.empty((B, L, D), dtype=torch.float64, device=a.device)
+            _lib.check(lib.dsp_posterior_features_bwd_f64(_lib.ptr(a), _lib.ptr(b), _lib.ptr(lse), _lib.ptr(g), _lib.ptr(df), B, T, L, D,
+                                                          _lib.current_stream_handle()), "dsp_posterior_features_bwd_f64")
+        return None, None, df.to(ctx.fdtype)
+
+
 def posterior_features(alpha: Tensor, beta: Tensor, features: Tensor) -> Tensor:
     """[B,T,D] = softmax_j(alpha + beta) @ features, fused (dsp_posterior_features): the posterior never exists in HBM; differentiable
-    w.r.t. `features`.  Falls back to the two-step form when the shape does not fit the kernel (odd D, rows beyond LDS)."""
+    w.r.t. `features`.  Falls back to the two-step form when the shape does not fit the kernel (odd D, rows beyond LDS).
+    float64 alpha or beta: the double kernels (dsp_posterior_features_f64, any T / L / D, no fallback); the result keeps the features'
+    dtype, so float64 features give a full double result."""
     _gpu("posterior_features", alpha, beta, features)
+    if _is_f64(alpha, beta):
+        if not features.is_floating_point():
+            raise RuntimeError(f"posterior_features: features must be floating point, got {features.dtype}")
+        return _PosteriorFeaturesF64Fn.apply(alpha, beta, features)
     B, T, L = alpha.shape
     if features.shape[2] % 2 or 8 * max(L, T) * 4 > 150 * 1024:
         return torch.matmul(posterior(alpha, beta).to(features.dtype), features)

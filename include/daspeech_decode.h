@@ -113,8 +113,19 @@ int dsp_posterior_features(const float* alpha, const float* beta, const float* f
                            int B, int T, int L, int D, dsp_stream_t stream);
 int dsp_posterior_features_bwd(const float* alpha, const float* beta, const float* lse, const float* grad_out, float* grad_features,
                                int B, int T, int L, int D, dsp_stream_t stream);
+/* F1 for DOUBLE alpha / beta (csrc/posterior_f64.hip): the reference computes the posterior in the dtype of alpha, so the float64 pair of
+ *   dsp_dag_loss_fwd_f64 gives a float64 score; every intermediate is a double, accurate exp / log only.  Same semantics as the three fp32
+ *   entry points above (dead rows: score and out 0, lse -inf; lse may be NULL in dsp_posterior_features_f64; no gradient to alpha / beta),
+ *   wider envelope: any T, L, D >= 1 (odd D and D = 1 included) — L and T are walked in chunks, nothing row-sized lives in LDS.  features
+ *   [B,L,D], out / grad_out [B,T,D], grad_features [B,L,D], lse [B,T], all double and contiguous.  No floating-point atomics: two calls on
+ *   the same tensors give the same bits.  Bad sizes / null pointers: DSP_EINVAL; B == 0: DSP_OK without a launch. */
+int dsp_posterior_f64(const double* alpha, const double* beta, double* score, int B, int T, int L, dsp_stream_t stream);
+int dsp_posterior_features_f64(const double* alpha, const double* beta, const double* features, double* out, double* lse,
+                               int B, int T, int L, int D, dsp_stream_t stream);
+int dsp_posterior_features_bwd_f64(const double* alpha, const double* beta, const double* lse, const double* grad_out,
+                                   double* grad_features, int B, int T, int L, int D, dsp_stream_t stream);
 
-/* F6a  predicted durations                                                     (fastspeech2.py:202-205)
+/* F6a predicted durations                                                     (fastspeech2.py:202-205)
  *   dur = clamp(round((exp(log_dur) - 1) * factor), 0) as int64, 0 where pad_mask != 0 (uint8/bool). */
 int dsp_durations(const float* log_dur, const uint8_t* pad_mask, float factor, int64_t* dur, int64_t n, dsp_stream_t stream);
 
