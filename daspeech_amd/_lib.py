@@ -69,6 +69,9 @@ SIGNATURES = {
     "dsp_extract_links_ws": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, _c_p, _c_sz, _c_p]),
     "dsp_extract_links_bwd_ws": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int,
                                           ctypes.c_float, _c_p, _c_sz, _c_p]),
+    "dsp_extract_links_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, _c_p]),
+    "dsp_extract_links_bwd_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                           ctypes.c_double, _c_p]),
     "dsp_extract_links_debug_ran": (ctypes.c_uint, []),
     "dsp_extract_links_debug_range": (ctypes.c_uint, []),
     "dsp_posterior": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),

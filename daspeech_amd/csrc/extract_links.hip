@@ -543,7 +543,8 @@ __global__ __launch_bounds__(256) void extract_links_bwd_tiled_kernel(
 // PROCESS-wide (r06): the backward of an autograd Function runs on PyTorch's device worker thread, which never saw a thread_local pin set by the
 // test's main thread (the "forced" tiled / matrix-core backward never ran).  g_xl_ran collects the kernel families launched since the
 // last dsp_extract_links_debug_ran() so a test can assert its pin took: bit 0 one-image forward, 1 tiled forward, 2 matrix-core forward,
-// 3 one-image backward, 4 tiled backward, 5 matrix-core backward (exact-fp32 contraction), 6 matrix-core backward (bf16-triple contraction).
+// 3 one-image backward, 4 tiled backward, 5 matrix-core backward (exact-fp32 contraction), 6 matrix-core backward (bf16-triple contraction);
+// extract_links_f64.hip adds 7 double forward, 8 double backward, 9 a double window walked in more than one tile.
 static std::atomic<int> g_xl_tile{0};           // dsp_dag_set_option("xl_tile", n): n > 0 forces the tiled kernels with TW = n (tests); 0 = only where the image does not fit
 std::atomic<unsigned int> g_xl_ran{0};
 void set_xl_tile(int v) { g_xl_tile = v > 0 ? ((v + 31) / 32) * 32 : 0; }

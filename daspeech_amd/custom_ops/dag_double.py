@@ -17,7 +17,11 @@ index, vertices off the path are -1.
 
 The double chain continues through the expect step: decode_ops.posterior / posterior_features / expect_features take the float64
 (alpha, beta) of dag_loss_with_alpha_beta on the double kernels of csrc/posterior_f64.hip and return a float64 score (the product in the
-features' dtype) — the reference computes that step in the dtype of alpha."""
+features' dtype) — the reference computes that step in the dtype of alpha.
+
+It STARTS one operator earlier, at the links: decode_ops.extract_links / extract_links_autograd (and DAGDecoder.extract_links on float64
+features) run float64 q / k / log_gates on the double kernels of csrc/extract_links_f64.hip, so the `links` that enter dag_loss in a double
+run are double numbers with double-accurate gradients behind them: q / k / gates -> links -> dag_loss -> backward."""
 import torch
 from torch import Tensor
 

@@ -2,6 +2,10 @@
 
 Host-side mirror of the reference code these replace:
   graph_decode        DASpeech/models/s2s_conformer_dag_fastspeech2.py:201-243 (lookahead / greedy branch of forward_decoder)
+  extract_links / extract_links_autograd   DASpeech/models/s2t_conformer_dag.py:171-212
+                      (float64 q, k or log_gates: the double kernels of csrc/extract_links_f64.hip — float64 links and double-accurate
+                      gradients, so the double chain of custom_ops/dag_double.py STARTS at the links: q / k / gates -> links -> dag_loss ->
+                      backward; every other dtype takes the fp32 / matrix-core kernels, as before)
   posterior / expect_features   DASpeech/criterions/s2s_dag_fastspeech2_loss.py:259-263
                       (float64 alpha or beta: the double kernels of csrc/posterior_f64.hip — the reference computes the posterior in the
                       dtype of alpha, so the double DAG chain of custom_ops/dag_double.py continues through this step; every other
@@ -104,8 +108,11 @@ def graph_decode(logits: Tensor, links: Tensor, features: Tensor, output_length:
 def extract_links(q: Tensor, k: Tensor, log_gates: Tensor, output_length: Tensor, TR: int,
                   dist_bias: Optional[Tensor] = None) -> Tensor:
     """Fused compact transition log-probabilities [B, L, TR] fp32 from the link predictor's q / k [B,L,H,CK] and
-    log_gates [B,L,H] (s2t_conformer_dag.py:171-212); inference only (no gradient)."""
+    log_gates [B,L,H] (s2t_conformer_dag.py:171-212); inference only (no gradient).  float64 q, k or log_gates: float64 links from the
+    double kernels (dsp_extract_links_f64), the other inputs widened."""
     _gpu("extract_links", q, k, log_gates, output_length)
+    if _links_f64(q, k, log_gates):
+        return _links_f64_forward(q, k, log_gates, output_length, int(TR), dist_bias, False)[5]
     qf = q.detach().to(torch.float32).contiguous()
     kf = k.detach().to(torch.float32).contiguous()
     gf = log_gates.detach().to(torch.float32).contiguous()
@@ -188,10 +195,77 @@ class _ExtractLinksFn(torch.autograd.Function):
         return dq.to(dt[0]), dk.to(dt[1]), dg.to(dt[2]), None, None, None
 
 
+def _links_f64(q: Tensor, k: Tensor, log_gates: Tensor) -> bool:
+    """float64 q, k or log_gates: the link producer runs on the double kernels (the other inputs are widened, which is exact) — narrowing a
+    double tensor silently would hand back fp32 accuracy under a float64 dtype"""
+    return q.dtype == torch.float64 or k.dtype == torch.float64 or log_gates.dtype == torch.float64
+
+
+def _links_f64_forward(q, k, log_gates, output_length, TR: int, dist_bias, need_stats: bool):
+    """dsp_extract_links_f64 on the widened inputs: (q, k, log_gates, out_len, dist_bias or None, links, stats or None), all float64.  No
+    workspace, no matrix-core kernels."""
+    for t in (q, k, log_gates, dist_bias):
+        if t is not None and not t.is_floating_point():
+            raise RuntimeError(f"extract_links: expected floating-point tensors, got {t.dtype}")
+    qd = q.detach().to(torch.float64).contiguous()
+    kd = k.detach().to(torch.float64).contiguous()
+    gd = log_gates.detach().to(torch.float64).contiguous()
+    ol = output_length.to(device=qd.device, dtype=torch.long).contiguous()
+    B, L, H, CK = qd.shape
+    bias = None if dist_bias is None else dist_bias.detach().to(device=qd.device, dtype=torch.float64).contiguous()
+    if tuple(kd.shape) != (B, L, H, CK) or tuple(gd.shape) != (B, L, H) or ol.numel() != B or (bias is not None and bias.numel() < TR):
+        raise RuntimeError(f"extract_links: shapes q {tuple(qd.shape)} k {tuple(kd.shape)} log_gates {tuple(gd.shape)} out_len {tuple(ol.shape)}"
+                           f" dist_bias {None if bias is None else tuple(bias.shape)} TR {TR}")
+    lib = _lib.load()
+    with torch.cuda.device(qd.device):
+        links = torch.empty((B, L, TR), dtype=torch.float64, device=qd.device)
+        stats = torch.empty((B, L, H, 2), dtype=torch.float64, device=qd.device) if need_stats else None
+        _lib.check(lib.dsp_extract_links_f64(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(gd), _lib.ptr(ol), _lib.ptr(bias), _lib.ptr(links), _lib.ptr(stats),
+                                             B, L, H, CK, TR, float(CK) ** -0.5, _lib.current_stream_handle()), "dsp_extract_links_f64")
+    return qd, kd, gd, ol, bias, links, stats
+
+
+def _links_f64_backward(qd, kd, gd, ol, bias, links, stats, grad_links, TR: int):
+    """dsp_extract_links_bwd_f64: (grad_q, grad_k, grad_log_gates) float64; grad_links of any floating dtype is widened"""
+    B, L, H, CK = qd.shape
+    g = grad_links.detach().to(torch.float64).contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(qd.device):
+        dq, dk, dg = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(gd)
+        _lib.check(lib.dsp_extract_links_bwd_f64(_lib.ptr(qd), _lib.ptr(kd), _lib.ptr(gd), _lib.ptr(ol), _lib.ptr(bias), _lib.ptr(links), _lib.ptr(g),
+                                                 _lib.ptr(stats), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dg), B, L, H, CK, TR, float(CK) ** -0.5,
+                                                 _lib.current_stream_handle()), "dsp_extract_links_bwd_f64")
+    return dq, dk, dg
+
+
+class _ExtractLinksF64Fn(torch.autograd.Function):
+    """_ExtractLinksFn for float64 q, k or log_gates (dsp_extract_links_f64 / _bwd_f64): inputs, links and the per-row soft-max state are saved
+    in double, the links come back float64 and every gradient in its input's dtype.  Launch helpers of its own: a double tensor cannot reach
+    an fp32 launch."""
+
+    @staticmethod
+    def forward(ctx, q, k, log_gates, output_length, TR, dist_bias):
+        qd, kd, gd, ol, bias, links, stats = _links_f64_forward(q, k, log_gates, output_length, TR, dist_bias, True)
+        ctx.save_for_backward(qd, kd, gd, ol, links, stats, bias if bias is not None else qd.new_empty(0))
+        ctx.TR, ctx.has_bias, ctx.in_dtypes = TR, bias is not None, (q.dtype, k.dtype, log_gates.dtype)
+        ctx.mark_non_differentiable(output_length)
+        return links
+
+    @staticmethod
+    def backward(ctx, grad_links):
+        qd, kd, gd, ol, links, stats, bias = ctx.saved_tensors
+        dq, dk, dg = _links_f64_backward(qd, kd, gd, ol, bias if ctx.has_bias else None, links, stats, grad_links, ctx.TR)
+        dt = ctx.in_dtypes
+        return dq.to(dt[0]), dk.to(dt[1]), dg.to(dt[2]), None, None, None
+
+
 def extract_links_autograd(q: Tensor, k: Tensor, log_gates: Tensor, output_length: Tensor, TR: int,
                            dist_bias: Optional[Tensor] = None) -> Tensor:
-    """`extract_links` with gradients w.r.t. q, k and log_gates (training: the step in front of dag_loss).  `dist_bias` is a constant."""
+    """`extract_links` with gradients w.r.t. q, k and log_gates (training: the step in front of dag_loss).  `dist_bias` is a constant.
+    float64 q, k or log_gates: float64 links and double-accurate gradients (in each input's dtype) from the double kernels."""
     _gpu("extract_links", q, k, log_gates, output_length)
+    if _links_f64(q, k, log_gates):
+        return _ExtractLinksF64Fn.apply(q, k, log_gates, output_length, int(TR), dist_bias)
     return _ExtractLinksFn.apply(q, k, log_gates, output_length, int(TR), dist_bias)
 
 

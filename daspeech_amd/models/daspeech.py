@@ -384,15 +384,18 @@ class DAGDecoder(nn.Module):
         return decode_ops.linear(feats, self.embed_tokens, lens=lens)        # --share-decoder-input-output-embed (weight [V, d], no bias)
 
     def extract_links(self, feats: Tensor, prev_output_tokens: Tensor, dist_bias: Optional[Tensor] = None, lens: Optional[Tensor] = None) -> Tensor:
-        """Compact transition log-probs [B, L, TR] fp32 (s2t_conformer_dag.py:171-212, banded branch :191-202).  `dist_bias` [>= TR]
-        (optional, not in the reference) is added to the content score of distance d before the window soft-max."""
+        """Compact transition log-probs [B, L, TR] fp32 — float64 for float64 `feats` — (s2t_conformer_dag.py:171-212, banded branch
+        :191-202).  `dist_bias` [>= TR] (optional, not in the reference) is added to the content score of distance d before the window soft-max."""
         a = self.a
         B, L, d = feats.shape
         h, ck = a.decoder_attention_heads, d // a.decoder_attention_heads
         fp = torch.cat([feats, self.link_positional(self.positions(prev_output_tokens))], dim=-1)
-        q = decode_ops.linear(fp, self.query_linear, lens=lens).view(B, L, h, ck).float()
-        k = decode_ops.linear(fp, self.key_linear, lens=lens).view(B, L, h, ck).float()
-        log_gates = F.log_softmax(decode_ops.linear(fp, self.gate_linear), dim=-1, dtype=torch.float)                   # [B,L,h]
+        # float64 features (a double-precision check): q, k and the gates stay double, and so do the links of either branch below — the
+        # double kernels of csrc/extract_links_f64.hip, or the torch formulation; every other dtype gives fp32 links, as in the reference
+        lt = torch.float64 if feats.dtype == torch.float64 else torch.float
+        q = decode_ops.linear(fp, self.query_linear, lens=lens).view(B, L, h, ck).to(lt)
+        k = decode_ops.linear(fp, self.key_linear, lens=lens).view(B, L, h, ck).to(lt)
+        log_gates = F.log_softmax(decode_ops.linear(fp, self.gate_linear), dim=-1, dtype=lt)                            # [B,L,h]
         TR = min(a.max_transition_length, L - 1)
         # the fused kernels keep one tile's scores in LDS: up to TR ~ 1100 (ck = 64) the whole window is ONE tile; wider windows — the README's
         # --max-transition-length 99999 on graphs up to BASELINE's L = 4096 — are walked in 512-slot tiles (r05: extract_links_tiled_kernel,

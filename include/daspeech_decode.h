@@ -91,10 +91,32 @@ int dsp_extract_links_bwd_ws(const float* q, const float* k, const float* log_ga
                              float* grad_q, float* grad_k, float* grad_log_gates, int B, int L, int H, int CK, int TR, float scale,
                              void* workspace, size_t workspace_bytes, dsp_stream_t stream);
 
+/* F0 for DOUBLE q / k / log_gates (csrc/extract_links_f64.hip): the same forward (stats = NULL: inference, else the training forward writing
+ *   stats [B,L,H,2]) and backward as dsp_extract_links / _train / _bwd with every tensor a contiguous double — q, k [B,L,H,CK], log_gates
+ *   [B,L,H], dist_bias [TR] or NULL, links / grad_links [B,L,TR], stats [B,L,H,2] = (window maximum, log of the window's sum of exp(score -
+ *   maximum)), (-inf, 0) for a row without a successor.  Every intermediate is a double (dot-product accumulators, shuffles, the LDS score
+ *   image), accurate exp / log only, products on v_fma_f64.  H = 8, CK = 32, 64 or 128, 1 <= TR <= L-1: a window of up to 381 successors is one
+ *   LDS tile per 4-vertex workgroup, a wider one is walked in tiles of 384 (online soft-max state first, emission second).  No [B,L,L,H] tensor
+ *   in either direction and no workspace: the backward recomputes the scores, and every k row gathers over its <= TR predecessors — no
+ *   floating-point atomics, two calls on the same tensors give the same bits.  The backward writes EVERY element of grad_q, grad_k and
+ *   grad_log_gates (rows at or beyond the graph: zeros); entries of grad_links under -inf links are ignored.  q, k, grad_q, grad_k 16-byte
+ *   aligned.  Null pointers, H != 8, another CK, TR < 1 or TR > L-1: DSP_EINVAL (dsp_last_error says which) before any launch; B == 0: DSP_OK
+ *   without a launch.  The ground truth of the fp32 and matrix-core kernels above that fits on the device, and the first operator of the
+ *   double chain links -> dsp_dag_loss_fwd_f64 -> backward.  Measured times: DESIGN.md §7. */
+int dsp_extract_links_f64(const double* q, const double* k, const double* log_gates, const int64_t* out_len,
+                          const double* dist_bias, double* links, double* stats, int B, int L, int H, int CK, int TR, double scale,
+                          dsp_stream_t stream);
+int dsp_extract_links_bwd_f64(const double* q, const double* k, const double* log_gates, const int64_t* out_len, const double* dist_bias,
+                              const double* links, const double* grad_links, const double* stats,
+                              double* grad_q, double* grad_k, double* grad_log_gates, int B, int L, int H, int CK, int TR, double scale,
+                              dsp_stream_t stream);
+
 /* diagnostics (r06): the extract_links kernel families launched by this process since the last call (then cleared) — bit 0 one-image forward,
  *   1 tiled forward, 2 matrix-core forward, 3 one-image backward, 4 tiled backward, 5 matrix-core backward with exact-fp32 contractions,
- *   6 matrix-core backward with bf16-triple contractions.  The "xl_tile" / "xl_mfma" / "xl_contract" options are PROCESS-wide (PyTorch runs an
- *   autograd backward on its own worker thread); tests assert through this word that the family they pinned is the one that ran. */
+ *   6 matrix-core backward with bf16-triple contractions, 7 double forward (dsp_extract_links_f64), 8 double backward
+ *   (dsp_extract_links_bwd_f64), 9 a double launch walked its window in more than one tile.  The "xl_tile" / "xl_mfma" / "xl_contract" options
+ *   (fp32 families only) are PROCESS-wide (PyTorch runs an autograd backward on its own worker thread); tests assert through this word that the
+ *   family they pinned is the one that ran. */
 unsigned int dsp_extract_links_debug_ran(void);
 /* RANGE of the matrix-core kernels (dsp_extract_links_ws / _bwd_ws): operands are split into fp16 hi / lo pieces, so |k| and |q| * scale * log2(e)
  *   must stay under 65 000 (link-predictor inputs are projections of layer-normed features: |x| ~ 1-10).  A larger operand is clamped — the call
