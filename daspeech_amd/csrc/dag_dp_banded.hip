@@ -12,47 +12,21 @@
 //     SURVEY.md §8(d).
 //   * ROW STATE LIVES IN LDS.  The previous DP row of the strip (+ a TRP-wide halo) is double-buffered in LDS; one
 //     workgroup barrier per row; each lane reads its 33-value window with 8-byte LDS loads.
-//   * STRIP-TO-STRIP HAND-OFF BY TAGGED GRANULES (cdna_hip_programming.md G16 form R2).  Strip s needs, for every row,
-//     the last TRP alphas of strip s-1.  The producer stores them as 8-byte {tag=row epoch, value} write-through (sc1)
-//     granules; the consumer prefetches them PF rows ahead with sc1 loads and re-polls only on a tag mismatch.  No
-//     flags, no fences, no grid barrier, and — unlike the reference's spin-wait on the previous segment's counter
-//     (dag_loss.cu:86-88) — every value is handed over explicitly, so there is no window-wider-than-segment race.
-//   * PLACEMENT-INDEPENDENT ORDER.  Workgroups draw tickets; a strip's producer always holds a smaller ticket, so the
-//     oldest unfinished workgroup never waits on an unscheduled one (no residency assumption, no deadlock).  Every
-//     spin is bounded and reports through an error word.
-#include "dag_dp.h"
+//   * STRIP-TO-STRIP HAND-OFF by tagged granules and PLACEMENT-INDEPENDENT ORDER by tickets: see dag_strip.h.  Unlike the reference's
+//     spin-wait on the previous segment's counter (dag_loss.cu:86-88) every value is handed over explicitly, so there is no
+//     window-wider-than-segment race.  This kernel has no helper waves: wave 0 fetches the halo, the lanes of the boundary columns publish.
+// The second half of this file is the scratch memory of every DP launch (banded_acquire_ws, the status words).
+#include "dag_strip.h"
 #include <mutex>
 #include <unordered_map>
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr int ST_THREADS = 256;
 constexpr int ST_CPT = 2;
 constexpr int ST_W = ST_THREADS * ST_CPT;     // 512 columns per strip
 constexpr int ST_PF = 8;                      // halo prefetch distance in rows
-constexpr u32 SPIN_LIMIT = 1u << 22;
-
-struct StripParams {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha; float* beta; int32_t* trace;
-    u64* halo; u32* counters;                 // counters[0] = ticket, counters[1] = error word
-    u32 tag_base;
-    int B, T, L, TR, NS, ndir;
-    int dbg;
-};
-
-__device__ __forceinline__ u64 gran_load(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
+constexpr int ST_SPIN_SLEEP = 2;              // halo_wait back-off: the polling wave is a compute wave here and has always slept two quanta, not one
 
 // MODE 0: log-sum-exp DP (alpha and/or beta; direction from the ticket).  MODE 1: max DP + trace (alpha direction).
 template <int TRP, int MODE>
@@ -63,16 +37,9 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
     __shared__ u32 s_ticket;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    if (tid == 0) s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = s_ticket;
-    const int per = p.ndir * p.B;
-    const int so = (int)(ticket / per);                 // position in dependency order
-    const int rem = (int)(ticket % per);
-    const bool is_beta = (MODE == 0) && (p.alpha == nullptr || (p.ndir == 2 && rem >= p.B));
-    const int b = rem % p.B;
-    const int dirslot = (p.ndir == 2 && rem >= p.B) ? 1 : 0;
-    const int s = is_beta ? (p.NS - 1 - so) : so;
+    const StripTicket k = strip_ticket_decode(strip_take_ticket(&s_ticket, p.counters), p, p.ndir, MODE == 0);
+    const bool is_beta = k.is_beta;
+    const int b = k.b, s = k.s;
     const int j0 = s * ST_W;
     const int T = p.T, L = p.L, TR = p.TR;
     const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
@@ -95,8 +62,7 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
         else { if (c0_in) o[0] = a0; if (c1_in) o[1] = a1; }
     };
 
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    if (!valid || j0 >= Lb) {                            // nothing reachable in this strip: all -inf, no hand-off needed
+    if (strip_is_dead(p, Lb, Tb, j0)) {                  // (not strip_fill_dead: two columns per lane, and the trace goes with them)
         for (int t = 0; t < T; ++t) { store_row(t, NEG_INF, NEG_INF); if (MODE == 1) store_trace(t, -1, -1); }
         return;
     }
@@ -122,11 +88,10 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
     }
 
     // ---- hand-off bookkeeping ----
-    const bool has_producer = so > 0 && (is_beta ? (j0 + ST_W < Lb) : true);     // beta: right strip exists and is live
-    const bool has_consumer = is_beta ? (s > 0) : (s < p.NS - 1 && j0 + ST_W < Lb);
-    const int prod_strip = is_beta ? s + 1 : s - 1;
-    const u64* hin = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + (has_producer ? prod_strip : 0)) * (size_t)T * TRP;
-    u64* hout = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + s) * (size_t)T * TRP;
+    const StripHalo halo = strip_halo(p, k, is_beta, ST_W, TRP, Lb);
+    const bool has_producer = halo.has_producer, has_consumer = halo.has_consumer;
+    const u64* hin = halo.in;
+    u64* hout = halo.out;
     const bool halo_lane = (tid < TRP);                   // wave 0 (TRP <= 64) fetches the halo
     // producer lanes: alpha -> my strip's last TRP columns; beta -> first TRP columns
     const int pub_c = is_beta ? (ST_CPT * tid) : (ST_CPT * tid - (ST_W - TRP));
@@ -138,14 +103,14 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
     const int halo_li = is_beta ? (ST_W + 1 + tid) : tid;
 
     const int nrows = Tb;                                 // iterations; row index t(it) below
-    u64 g[ST_PF];
+    u64 g[ST_PF][1];
 #pragma unroll
-    for (int k = 0; k < ST_PF; ++k) g[k] = 0;
+    for (int k = 0; k < ST_PF; ++k) g[k][0] = 0;
     if (has_producer && halo_lane) {
 #pragma unroll
         for (int k = 0; k < ST_PF; ++k) {
             const int it = k;
-            if (it < nrows) { const int t = is_beta ? (Tb - 1 - it) : it; g[k] = gran_load(hin + (size_t)t * TRP + tid); }
+            if (it < nrows) { const int t = is_beta ? (Tb - 1 - it) : it; g[k][0] = gran_load(hin + (size_t)t * TRP + tid); }
         }
     }
 
@@ -173,16 +138,11 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
                 float hv = NEG_INF;
                 if (has_producer) {
                     const u32 want = p.tag_base + 1u + (u32)t;
-                    u64 x = g[k];
-                    u32 spins = 0;
-                    while (!__all((u32)(x >> 32) == want)) {
-                        if ((u32)(x >> 32) != want) x = gran_load(hin + (size_t)t * TRP + tid);
-                        if (++spins > SPIN_LIMIT) { if (lane == 0) atomicOr(&p.counters[1], 1u); break; }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                    hv = __uint_as_float((u32)x);
+                    u64 x[1] = {g[k][0]};
+                    halo_wait<1, ST_SPIN_SLEEP>(hin + (size_t)t * TRP + tid, want, x, p.counters, lane);
+                    hv = __uint_as_float((u32)x[0]);
                     const int itn = it + ST_PF;
-                    if (itn < nrows) { const int tn = is_beta ? (Tb - 1 - itn) : itn; g[k] = gran_load(hin + (size_t)tn * TRP + tid); }
+                    if (itn < nrows) { const int tn = is_beta ? (Tb - 1 - itn) : itn; g[k][0] = gran_load(hin + (size_t)tn * TRP + tid); }
                 }
                 cur[halo_li] = hv;
             }
@@ -250,7 +210,7 @@ __global__ __launch_bounds__(ST_THREADS) void dag_strip_kernel(StripParams p)
         }
     }
     // rows the recurrence never reaches
-    if (!is_beta || true) for (int t = Tb; t < T; ++t) { store_row(t, NEG_INF, NEG_INF); if (MODE == 1) store_trace(t, -1, -1); }
+    for (int t = Tb; t < T; ++t) { store_row(t, NEG_INF, NEG_INF); if (MODE == 1) store_trace(t, -1, -1); }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -298,7 +258,7 @@ static int get_ws(hipStream_t st, size_t need, BandedWS** out)
 }
 
 bool banded_supported(int L, int TR) { (void)L; return TR <= 64; }
-size_t banded_ws_bytes(int B, int T, int L, int TR, int ndir) { return (size_t)ndir * B * ((L + ST_W - 1) / ST_W) * T * (TR <= 32 ? 32 : 64) * sizeof(u64); }
+size_t banded_ws_bytes(int B, int T, int L, int TR, int ndir) { return strip_halo_bytes(ndir, B, (L + ST_W - 1) / ST_W, T, TR <= 32 ? 32 : 64); }
 
 // Shared by every DP launcher that hands rows between workgroups: 256 bytes of counters (ticket, status word, fallback counters,
 // debug slots) + `halo_bytes` of tagged granules / progress words.
@@ -386,21 +346,13 @@ int launch_dag_banded(int mode, const float* match, const float* links, const in
     const int TRP = TR <= 32 ? 32 : 64;
     const int NS = (L + ST_W - 1) / ST_W;
     const int ndir = (mode == 0 && alpha && beta) ? 2 : 1;
-    StripParams p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
-    p.alpha = alpha; p.beta = beta; p.trace = trace;
-    int rc = banded_acquire_ws(st, banded_ws_bytes(B, T, L, TR, ndir), T, &p.counters, &p.halo, &p.tag_base);
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha, beta, trace, B, T, L, TR, NS, ndir, L, L);
+    int rc = strip_acquire(p, banded_ws_bytes(B, T, L, TR, ndir), st);
     if (rc) return rc;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.dbg = 0;
-    const dim3 grid((unsigned)(ndir * B * NS)), block(ST_THREADS);
-    if (mode == 0) {
-        if (TRP == 32) hipLaunchKernelGGL((dag_strip_kernel<32, 0>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((dag_strip_kernel<64, 0>), grid, block, 0, st, p);
-    } else {
-        if (TRP == 32) hipLaunchKernelGGL((dag_strip_kernel<32, 1>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((dag_strip_kernel<64, 1>), grid, block, 0, st, p);
-    }
-    return check_launch(mode == 0 ? "dag_loss_fwd(banded)" : "dag_best_alignment(banded)");
+    const int nwg = ndir * B * NS;
+    const char* what = mode == 0 ? "dag_loss_fwd(banded)" : "dag_best_alignment(banded)";
+    if (mode == 0) return TRP == 32 ? launch_strip(dag_strip_kernel<32, 0>, p, nwg, ST_THREADS, 0, st, what) : launch_strip(dag_strip_kernel<64, 0>, p, nwg, ST_THREADS, 0, st, what);
+    return TRP == 32 ? launch_strip(dag_strip_kernel<32, 1>, p, nwg, ST_THREADS, 0, st, what) : launch_strip(dag_strip_kernel<64, 1>, p, nwg, ST_THREADS, 0, st, what);
 }
 
 // error word of the most recent DP launch on this stream (host-synchronising; used by tests / debugging only).  With a caller

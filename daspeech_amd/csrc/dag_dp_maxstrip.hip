@@ -5,12 +5,12 @@
 // predecessor: 4 VALU instructions per transition (add, compare, two selects) and a B*T*L int32 tensor written to HBM, of
 // which the back-trace then reads T entries per sample.  Here:
 //   * the DP keeps VALUES only: per vertex 32 adds and a 3-input max tree (1.5 instructions per transition, no trace store);
-//     same strip / tagged-granule / ticket / helper-wave structure as dag_dp_strip4g.hip, 4 vertices per lane, log domain
+//     launch structure and hand-off of dag_strip.h (alpha direction only, 32 boundary columns), 4 vertices per lane, log domain
 //     (add / max only => alpha_max is bit-identical to the sequential scan);
 //   * the back-trace recomputes the arg-max for the one cell per row it visits, from alpha_max and the links, with the
 //     reference's tie rule (smallest predecessor index; -1 when every candidate is -inf).
 // Used when the caller passes trace == NULL (the Python operator does); with a trace pointer the eager kernels run.
-#include "dag_dp.h"
+#include "dag_strip.h"
 #include <string.h>
 #include <stdlib.h>
 // Cycle accounting / timing ablations of the max-DP (tools/prof_maxstrip.py) exist only in a build with -DDSP_MX_PROF (add it as a
@@ -23,44 +23,18 @@
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-struct MStripParams {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha;
-    u64* halo; u32* counters;                 // counters[0] = ticket, counters[1] = error word
-    u32 tag_base;
-    int B, T, L, TR, NS;
-    int ldm, ldo;                             // row pitch (elements) of match / alpha_max: >= L rounded up to 4, multiples of 4 (r06)
-    int dbg;                                  // DSP_DEBUG=prof (2): cycle accounting of one compute wave (counters[8..12]); DSP_MX_ABLATE bits 4 / 8 / 16: no alpha
-                                              // store / no max trees / no adds either (timing experiments, results wrong)
-};
-
+// dbg (instrumentation build): DSP_DEBUG=prof (2): cycle accounting of one compute wave (counters[8..12]); DSP_MX_ABLATE bits 4 / 8 / 16: no alpha
+// store / no max trees / no adds either (timing experiments, results wrong)
 constexpr int MX_TRP = 32;
-constexpr int MX_RING = 8;
-constexpr int MX_CH = 4;                      // halo prefetch distance of the fetch wave (rows)
-constexpr u32 MX_SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ u64 mx_gran_load(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void mx_gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void mx_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
 typedef float mx_v2f __attribute__((ext_vector_type(2)));
 
 template <int NT, int CPL>
-__device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_raw, int b, int s, int so)
+__device__ __forceinline__ void maxstrip_body(const StripParams& p, char* smem_raw, const StripTicket& k)
 {
-    constexpr int W = CPL * NT, RL = W + 32, NCW = NT / 64, DPR = W / 256;
+    constexpr int W = CPL * NT, RL = W + 32, NCW = NT / 64;
+    const int b = k.b, s = k.s;
     float* Abuf = reinterpret_cast<float*>(smem_raw);          // [2][RL]  alpha_max rows (natural log domain)
     float* Mring = Abuf + 2 * RL;                              // [RING][W] match rows
 
@@ -74,10 +48,7 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
     const int LDM = p.ldm, LDO = p.ldo;
     const int nrows = Tb;
 
-    const bool has_producer = so > 0;
-    const bool has_consumer = s < p.NS - 1 && j0 + W < Lb;
-    const u64* hin = p.halo + ((size_t)b * p.NS + (has_producer ? s - 1 : 0)) * (size_t)T * MX_TRP;
-    u64* hout = p.halo + ((size_t)b * p.NS + s) * (size_t)T * MX_TRP;
+    const StripHalo halo = strip_halo(p, k, false, W, MX_TRP, Lb);
     // LDS geometry: li = col - j0 + 32 (halo [0,32), own [32, W+32))
 
     // ---- prologue: the strip's transition rows -> LDS tile (coalesced, once), then -> registers ----
@@ -124,7 +95,7 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
                 else E[c][q] = tile[(CPL * l + c + q) * 33 + (31 - q)];   // row (j+c-32+k) - (j0-32), transition d-1 = 31-k
             }
         __syncthreads();                         // tile consumed: the loader may start filling the ring over it
-        mx_barrier();                            // prologue barrier: match row 0 is in the ring
+        strip_barrier();                            // prologue barrier: match row 0 is in the ring
 
         const bool prof = (MX_DBG(p) & 2) && b == 0 && s == p.NS - 1 && wave == 0;
         u64 pf[4] = {0, 0, 0, 0}, pf_last = prof ? __builtin_amdgcn_s_memtime() : 0;
@@ -136,11 +107,11 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
 #pragma unroll
             for (int c = 0; c < CPL; ++c) a[c] = NEG_INF;
             if (it == 0) {
-                if (j == 0) a[0] = Mring[(size_t)(it % MX_RING) * W];        // the start vertex
+                if (j == 0) a[0] = Mring[(size_t)(it % STRIP_RING) * W];        // the start vertex
             } else {
                 // row head: the match values and the (32 + CPL)-value window leave as one issue group (see dag_dp_strip4g.hip)
                 float w[(CPL == 2) ? 36 : 32 + CPL], m2[CPL];
-                const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % MX_RING) * W + CPL * l);
+                const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % STRIP_RING) * W + CPL * l);
                 const u32 vaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Abuf + prv * RL + CPL * l);
                 if constexpr (CPL == 4) {
                     mx_v4f mt, pv[9];
@@ -167,7 +138,7 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
                     const float* wp = Abuf + prv * RL + l;                      // 33 dwords, 4-byte aligned: ds_read2_b32 pairs
 #pragma unroll
                     for (int k = 0; k < 33; ++k) w[k] = wp[k];
-                    m2[0] = Mring[(size_t)(it % MX_RING) * W + l];
+                    m2[0] = Mring[(size_t)(it % STRIP_RING) * W + l];
                 } else if constexpr (CPL == 2) {
                     mx_v2f mt; mx_v4f pv[9];
                     const u32 vaddr16 = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Abuf + prv * RL + 4 * (l >> 1));
@@ -261,7 +232,7 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
             }
             if (prof) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             stamp(2);                                       // stores issued, LDS write done
-            mx_barrier();
+            strip_barrier();
             stamp(3);                                       // barrier
         }
         if (prof && lane == 0) { for (int i = 0; i < 4; ++i) p.counters[8 + i] = (u32)(pf[i] >> 4); p.counters[12] = (u32)nrows; }
@@ -271,113 +242,40 @@ __device__ __forceinline__ void maxstrip_body(const MStripParams& p, char* smem_
             else *reinterpret_cast<float2*>(O + (size_t)t * LDO + j) = make_float2(NEG_INF, NEG_INF);
         }
     } else if (wave == NCW) {
-        // =========================================================== loader wave: match rows -> LDS ring (LDS-DMA)
-        auto issue_row = [&](int itr) {
-            const float* rowp = M + (size_t)itr * LDM;
-            float* slot = Mring + (size_t)(itr % MX_RING) * W;
-#pragma unroll
-            for (int i = 0; i < DPR; ++i) {
-                const int col = j0 + i * 256 + lane * 4;
-                const float* g = rowp + (col < L ? col : 0);          // out-of-range lanes re-read a valid address
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(slot + i * 256), 16, 0, 0);
-            }
-        };
+        // loader wave: 16 bytes per lane
         __syncthreads();                         // link tile consumed
-        for (int r = 0; r < MX_RING - 1 && r < nrows; ++r) issue_row(r);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        mx_barrier();                            // prologue barrier
-        for (int it = 0; it < nrows; ++it) {
-            const int nx = it + MX_RING - 1;     // slot (it-1) % RING was last read during iteration it-1: free now
-            if (nx < nrows) {
-                issue_row(nx);
-                if (DPR == 4) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");       // rows it+2 .. it+7 may stay in flight
-                else if (DPR == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            mx_barrier();
-        }
+        strip_loader_wave<W, 16, STRIP_RING, STRIP_RING - 1, false>(M, LDM, Mring, j0, L, nrows, lane);
     } else if (wave == NCW + 1) {
-        // =========================================================== fetch wave: left neighbour's last 32 vertices -> LDS halo
-        const bool hl = lane < MX_TRP;
-        u64 g[MX_CH];
-#pragma unroll
-        for (int k = 0; k < MX_CH; ++k) g[k] = 0;
-        auto load_row = [&](int itr) -> u64 {    // rolling prefetch, MX_CH rows ahead (see dag_dp_strip4g.hip)
-            if (itr < nrows && hl) return mx_gran_load(hin + (size_t)itr * MX_TRP + lane);
-            return 0;
-        };
-        if (has_producer) {
-#pragma unroll
-            for (int k = 0; k < MX_CH; ++k) g[k] = load_row(k);
-        }
+        // fetch wave: the left neighbour's last 32 vertices -> LDS halo, as they are
+        u64 g[STRIP_CH][1];
+        strip_fetch_prime<MX_TRP, 1, STRIP_CH, false>(halo.in, halo.has_producer, nrows, lane, g);
         __syncthreads();                         // link tile consumed
-        mx_barrier();                            // prologue barrier
-        for (int itb = 0; itb < nrows; itb += MX_CH) {
-#pragma unroll
-            for (int k = 0; k < MX_CH; ++k) {
-                const int it = itb + k;
-                if (it >= nrows) break;
-                const int cur = it & 1;
-                float hv = NEG_INF;
-                if (has_producer && hl) {
-                    const u32 want = p.tag_base + 1u + (u32)it;
-                    u64 xg = g[k];
-                    u32 spins = 0;
-                    while (!__all((u32)(xg >> 32) == want)) {
-                        if ((u32)(xg >> 32) != want) xg = mx_gran_load(hin + (size_t)it * MX_TRP + lane);
-                        if (++spins > MX_SPIN_LIMIT) { if (lane == 0) atomicOr(&p.counters[1], 1u); break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    hv = __uint_as_float((u32)xg);
-                }
-                if (hl) Abuf[cur * RL + lane] = hv;
-                if (has_producer) g[k] = load_row(it + MX_CH);
-                mx_barrier();
-            }
-        }
+        strip_fetch_rows<MX_TRP, 1, STRIP_CH, false>(p, halo.in, halo.has_producer, nrows, lane, g, [&](int it, const float (&hv)[1]) {
+            if (strip_halo_lane<MX_TRP, 1>(lane)) Abuf[(it & 1) * RL + lane] = hv[0];
+        });
     } else {
-        // =========================================================== publish wave: last 32 vertices -> granules
-        const bool pl = has_consumer && lane < MX_TRP;
+        // publish wave: the strip's last 32 vertices (li W .. W+31)
         __syncthreads();                         // link tile consumed
-        mx_barrier();                            // prologue barrier
-        for (int it = 0; it <= nrows; ++it) {
-            if (it > 0 && pl) {                  // row it-1 is complete; compute now writes the other buffer
-                const float v = Abuf[((it - 1) & 1) * RL + W + lane];
-                mx_gran_store(hout + (size_t)(it - 1) * MX_TRP + lane, p.tag_base + 1u + (u32)(it - 1), v);
-            }
-            if (it < nrows) mx_barrier();
-        }
+        strip_publish_wave<MX_TRP, 1, false>(p, halo.out, Abuf + W, RL, halo.has_consumer, nrows, lane);
     }
 }
 
 template <int NT, int CPL>
-__global__ __launch_bounds__(NT + 192) void dag_maxstrip_kernel(MStripParams p)
+__global__ __launch_bounds__(NT + 192) void dag_maxstrip_kernel(StripParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 16-byte header (ticket); everything else starts at +16
     constexpr int W = CPL * NT;
-    u32* s_ticket = reinterpret_cast<u32*>(smem_raw);          // 16-byte header; everything else starts at +16
-    const int tid = threadIdx.x;
-    if (tid == 0) *s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = *s_ticket;                              // producers hold smaller tickets than their consumers
-    const int so = (int)(ticket / p.B);
-    const int b = (int)(ticket % p.B);
-    const int s = so;
-    const int j0 = s * W;
-    const int T = p.T, L = p.L;
-    const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    if (!valid || j0 >= Lb) {                    // nothing reachable in this strip: -inf everywhere, no hand-off
-        float* O = p.alpha + (size_t)b * T * p.ldo;
-        for (int j = j0 + 4 * tid; j < j0 + W && j < L; j += 4 * (NT + 192))
-            for (int t = 0; t < T; ++t)
+    const StripTicket k = strip_ticket_decode(strip_take_ticket(reinterpret_cast<u32*>(smem_raw), p.counters), p, 1, false);
+    const int j0 = k.s * W;
+    if (strip_is_dead(p, (int)p.out_len[k.b], (int)p.tgt_len[k.b], j0)) {
+        // vector fill, not strip_fill_dead: rows are 16-byte aligned here
+        float* O = p.alpha + (size_t)k.b * p.T * p.ldo;
+        for (int j = j0 + 4 * (int)threadIdx.x; j < j0 + W && j < p.L; j += 4 * (NT + 192))
+            for (int t = 0; t < p.T; ++t)
                 *reinterpret_cast<float4*>(O + (size_t)t * p.ldo + j) = make_float4(NEG_INF, NEG_INF, NEG_INF, NEG_INF);
         return;
     }
-    maxstrip_body<NT, CPL>(p, smem_raw + 16, b, s, so);
+    maxstrip_body<NT, CPL>(p, smem_raw + 16, k);
 }
 
 // ---- lazy back-trace (replaces the trace tensor of dag_best_alignment.cu:39-130 + the pointer chase of :160-201) ----------
@@ -659,19 +557,16 @@ bool maxstrip_supported(int L, int TR, bool rows16)
 // per lane in 512-vertex strips (twice the waves for the same vertices)
 static bool maxstrip_wide(int B, int L) { return (long)B * ((L + 1023) / 1024) >= 200; }
 static int maxstrip_strips(int B, int L) { return maxstrip_wide(B, L) ? (L + 1023) / 1024 : (L + 511) / 512; }
-size_t maxstrip_ws_bytes(int B, int T, int L) { return (size_t)B * maxstrip_strips(B, L) * T * MX_TRP * sizeof(u64); }
+size_t maxstrip_ws_bytes(int B, int T, int L) { return strip_halo_bytes(1, B, maxstrip_strips(B, L), T, MX_TRP); }
 
 template <int NT, int CPL>
-static int launch_one_mx(const MStripParams& p, int nwg, hipStream_t st)
+static int launch_one_mx(const StripParams& p, int nwg, hipStream_t st)
 {
     constexpr int W = CPL * NT, RL = W + 32;
-    const size_t lds_main = (size_t)(2 * RL + MX_RING * W) * 4 + 16;
+    const size_t lds_main = (size_t)(2 * RL + STRIP_RING * W) * 4 + 16;
     const size_t lds_tile = (size_t)(W + 32) * 33 * 4;
     const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    auto k = dag_maxstrip_kernel<NT, CPL>;
-    set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(NT + 192), lds, st, p);
-    return check_launch("dag_best_alignment(maxstrip)");
+    return launch_strip(dag_maxstrip_kernel<NT, CPL>, p, nwg, NT + 192, lds, st, "dag_best_alignment(maxstrip)");
 }
 
 // alpha_max by column strips (values only), then the lazy back-trace: no trace tensor
@@ -680,15 +575,11 @@ int launch_dag_maxstrip(const float* match, const float* links, const int64_t* o
 {
     const bool wide = maxstrip_wide(B, L);
     const int NS = maxstrip_strips(B, L);
-    MStripParams p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha_max;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ldm = ldm; p.ldo = ldo;
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha_max, nullptr, nullptr, B, T, L, TR, NS, 1, ldm, ldo);
 #ifdef DSP_MX_PROF                                  // instrumentation build only (tools/prof_maxstrip.py): nothing on the product's launch path
     { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "prof")) ? 2 : 0; static const char* const a = getenv("DSP_MX_ABLATE"); if (a) p.dbg |= atoi(a) & 28; }
-#else
-    p.dbg = 0;
 #endif
-    int rc = banded_acquire_ws(st, maxstrip_ws_bytes(B, T, L), T, &p.counters, &p.halo, &p.tag_base);
+    int rc = strip_acquire(p, maxstrip_ws_bytes(B, T, L), st);
     if (rc) return rc;
     rc = wide ? launch_one_mx<256, 4>(p, B * NS, st) : launch_one_mx<256, 2>(p, B * NS, st);
     if (rc) return rc;

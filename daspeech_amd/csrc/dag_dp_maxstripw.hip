@@ -11,12 +11,11 @@
 //     (65 .. 128).  The lane's window starts at the 16-byte boundary under its first predecessor and streams through two 6-read register
 //     buffers (chunk c+1 requested before chunk c is consumed); its transitions sit in registers against that window (-inf where an element
 //     is no predecessor), loaded through an LDS tile in halves of 64 slots.
-//   * loader / fetch / publish helper waves, tagged granules, tickets: as the other strip kernels.
+//   * launch structure and hand-off: dag_strip.h (alpha direction only; 64 or 128 boundary columns, one or two granules per helper lane).
 //   * back-trace (dag_backtrace_wide_kernel): one wave per sample; at (t, pos) lane d evaluates the predecessors at distances d+1 and d+65,
 //     smallest predecessor index among equal maxima (the reference's tie rule as torch states it), -1 / stop where every
 //     candidate is -inf (dag_best_alignment.cu:170-206 chases a stored trace instead).
-#include "dag_dp.h"
-#include <stdlib.h>
+#include "dag_strip.h"
 
 #define MW_CHUNK6_0 \
     "ds_read_b128 %0, %6\n\t" \
@@ -73,36 +72,12 @@
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef float mw_v4f __attribute__((ext_vector_type(4)));
 
-struct MWParams {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha;
-    u64* halo; u32* counters;                 // counters[0] = ticket, counters[1] = error word
-    u32 tag_base;
-    int B, T, L, TR, NS;
-    int ldm, ldo;                             // row pitches (elements) of match / of the max-alpha table (>= L)
-};
-
 constexpr int MW_NT = 256;
-constexpr int MW_RING = 8;
-constexpr int MW_CH = 4;
-constexpr u32 MW_SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ u64 mw_gran_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mw_gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void mw_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 template <int CPL>
-__device__ __forceinline__ void maxstripw_body(const MWParams& p, char* smem_raw, int b, int s, int so)
+__device__ __forceinline__ void maxstripw_body(const StripParams& p, char* smem_raw, const StripTicket& k)
 {
     constexpr int TRP = 128 / CPL, W = CPL * MW_NT, RL = W + TRP, NCW = MW_NT / 64, NW = TRP + 4, NG = NW / 4;      // window: NW values = NG groups of 4
     constexpr int GPL = TRP / 64;                              // halo granules per helper lane
@@ -110,6 +85,7 @@ __device__ __forceinline__ void maxstripw_body(const MWParams& p, char* smem_raw
     float* Mring = Abuf + 2 * RL;                              // [RING][W] match rows
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = k.b, s = k.s;
     const int T = p.T, L = p.L, TR = p.TR;
     const int j0 = s * W;
     const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
@@ -118,10 +94,7 @@ __device__ __forceinline__ void maxstripw_body(const MWParams& p, char* smem_raw
     float* O = p.alpha + (size_t)b * T * p.ldo;
     const int LDO = p.ldo;
     const int nrows = Tb;
-    const bool has_producer = so > 0;
-    const bool has_consumer = s < p.NS - 1 && j0 + W < Lb;
-    const u64* hin = p.halo + ((size_t)b * p.NS + (has_producer ? s - 1 : 0)) * (size_t)T * TRP;
-    u64* hout = p.halo + ((size_t)b * p.NS + s) * (size_t)T * TRP;
+    const StripHalo halo = strip_halo(p, k, false, W, TRP, Lb);
     // LDS geometry: li = col - j0 + TRP (halo [0, TRP))
 
     // ---- prologue: transitions -> registers through an LDS tile, in halves of 64 slots: tile[r][dd] = links[j0 - TRP + r][64 h + dd] (pitch 65)
@@ -169,14 +142,14 @@ __device__ __forceinline__ void maxstripw_body(const MWParams& p, char* smem_raw
         // =========================================================== compute waves
         __builtin_amdgcn_s_setprio(2);
         const bool col_ok = j < L;
-        mw_barrier();                            // prologue barrier: match row 0 is in the ring
+        strip_barrier();                            // prologue barrier: match row 0 is in the ring
         for (int it = 0; it < nrows; ++it) {
             const int t = it;
             const int cur = it & 1, prv = cur ^ 1;
             float a[CPL];
             float m[CPL];
 #pragma unroll
-            for (int c = 0; c < CPL; ++c) { a[c] = NEG_INF; m[c] = Mring[(size_t)(it % MW_RING) * W + CPL * l + c]; }
+            for (int c = 0; c < CPL; ++c) { a[c] = NEG_INF; m[c] = Mring[(size_t)(it % STRIP_RING) * W + CPL * l + c]; }
             if (it == 0) {
                 if (j == 0) a[0] = m[0];                                                       // alpha_max[0][0] = match[0][0]
             } else {
@@ -222,128 +195,41 @@ __device__ __forceinline__ void maxstripw_body(const MWParams& p, char* smem_raw
                 Abuf[cur * RL + TRP + CPL * l + c] = a[c];
                 if (j + c < L) O[(size_t)t * LDO + j + c] = a[c];
             }
-            mw_barrier();
+            strip_barrier();
         }
         if (col_ok) for (int t = Tb; t < T; ++t) {
 #pragma unroll
             for (int c = 0; c < CPL; ++c) if (j + c < L) O[(size_t)t * LDO + j + c] = NEG_INF;
         }
     } else if (wave == NCW) {
-        // =========================================================== loader wave: match rows -> LDS ring (LDS-DMA, 4 bytes per lane)
-        auto issue_row = [&](int itr) {
-            const float* rowp = M + (size_t)itr * p.ldm;
-            float* slot = Mring + (size_t)(itr % MW_RING) * W;
-#pragma unroll
-            for (int i = 0; i < W / 64; ++i) {
-                const int col = j0 + i * 64 + lane;
-                const float* g = rowp + (col < L ? col : 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(slot + i * 64), 4, 0, 0);
-            }
-        };
-        for (int r = 0; r < MW_RING - 1 && r < nrows; ++r) issue_row(r);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        mw_barrier();
-        for (int it = 0; it < nrows; ++it) {
-            const int nx = it + MW_RING - 1;
-            if (nx < nrows) {
-                issue_row(nx);
-                if (W == 512) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");        // rows it+2 .. it+7 may stay in flight: 6 x (W / 64) DMAs
-                else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            mw_barrier();
-        }
+        // loader wave: 4 bytes per lane (rows of a dense tensor are not 16-byte aligned in general)
+        strip_loader_wave<W, 4, STRIP_RING, STRIP_RING - 1, false>(M, p.ldm, Mring, j0, L, nrows, lane);
     } else if (wave == NCW + 1) {
-        // =========================================================== fetch wave: the left strip's TRP boundary values -> LDS (GPL per lane)
-        u64 g[MW_CH][GPL];
+        // fetch wave: the left strip's TRP boundary values -> LDS halo, as they are
+        u64 g[STRIP_CH][GPL];
+        strip_fetch_prime<TRP, GPL, STRIP_CH, false>(halo.in, halo.has_producer, nrows, lane, g);
+        strip_fetch_rows<TRP, GPL, STRIP_CH, false>(p, halo.in, halo.has_producer, nrows, lane, g, [&](int it, const float (&hv)[GPL]) {
 #pragma unroll
-        for (int k = 0; k < MW_CH; ++k)
-#pragma unroll
-            for (int e = 0; e < GPL; ++e) g[k][e] = 0;
-        auto load_row = [&](int itr, u64 (&dst)[GPL]) {
-#pragma unroll
-            for (int e = 0; e < GPL; ++e) dst[e] = itr < nrows ? mw_gran_load(hin + (size_t)itr * TRP + GPL * lane + e) : 0;
-        };
-        if (has_producer) {
-#pragma unroll
-            for (int k = 0; k < MW_CH; ++k) load_row(k, g[k]);
-        }
-        mw_barrier();
-        for (int itb = 0; itb < nrows; itb += MW_CH) {
-#pragma unroll
-            for (int k = 0; k < MW_CH; ++k) {
-                const int it = itb + k;
-                if (it >= nrows) break;
-                const int cur = it & 1;
-                float hv[GPL];
-#pragma unroll
-                for (int e = 0; e < GPL; ++e) hv[e] = NEG_INF;
-                if (has_producer) {
-                    const u32 want = p.tag_base + 1u + (u32)it;
-                    u32 spins = 0;
-                    while (true) {
-                        bool ok = true;
-#pragma unroll
-                        for (int e = 0; e < GPL; ++e) ok &= (u32)(g[k][e] >> 32) == want;
-                        if (__all(ok)) break;
-#pragma unroll
-                        for (int e = 0; e < GPL; ++e) if ((u32)(g[k][e] >> 32) != want) g[k][e] = mw_gran_load(hin + (size_t)it * TRP + GPL * lane + e);
-                        if (++spins > MW_SPIN_LIMIT) { if (lane == 0) atomicOr(&p.counters[1], 1u); break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-#pragma unroll
-                    for (int e = 0; e < GPL; ++e) hv[e] = __uint_as_float((u32)g[k][e]);
-                }
-#pragma unroll
-                for (int e = 0; e < GPL; ++e) Abuf[cur * RL + GPL * lane + e] = hv[e];
-                if (has_producer) load_row(it + MW_CH, g[k]);
-                mw_barrier();
-            }
-        }
+            for (int e = 0; e < GPL; ++e) Abuf[(it & 1) * RL + GPL * lane + e] = hv[e];
+        });
     } else {
-        // =========================================================== publish wave: the strip's last TRP columns -> granules
-        const bool pl = has_consumer;
-        mw_barrier();
-        auto publish = [&](int itp) {            // row itp - 1 is complete
-            const int tp = itp - 1;
-#pragma unroll
-            for (int e = 0; e < GPL; ++e)
-                mw_gran_store(hout + (size_t)tp * TRP + GPL * lane + e, p.tag_base + 1u + (u32)tp, Abuf[((itp - 1) & 1) * RL + W + GPL * lane + e]);
-        };
-        for (int it = 0; it < nrows; ++it) {
-            if (it > 0 && pl) publish(it);
-            mw_barrier();
-        }
-        if (pl && nrows > 0) publish(nrows);
+        // publish wave: the strip's last TRP columns (li W .. W+TRP-1)
+        strip_publish_wave<TRP, GPL, false>(p, halo.out, Abuf + W, RL, halo.has_consumer, nrows, lane);
     }
 }
 
 template <int CPL>
-__global__ __launch_bounds__(MW_NT + 192) void dag_maxstripw_kernel(MWParams p)
+__global__ __launch_bounds__(MW_NT + 192) void dag_maxstripw_kernel(StripParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 16-byte header (ticket); everything else starts at +16
     constexpr int W = CPL * MW_NT;
-    u32* s_ticket = reinterpret_cast<u32*>(smem_raw);
-    const int tid = threadIdx.x;
-    if (tid == 0) *s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = *s_ticket;                              // producers hold smaller tickets than their consumers
-    const int so = (int)(ticket / p.B);
-    const int b = (int)(ticket % p.B);
-    const int s = so;
-    const int j0 = s * W;
-    const int T = p.T, L = p.L;
-    const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    if (!valid || j0 >= Lb) {
-        float* O = p.alpha + (size_t)b * T * p.ldo;
-        for (int jj = j0 + tid; jj < j0 + W && jj < L; jj += MW_NT + 192)
-            for (int t = 0; t < T; ++t) O[(size_t)t * p.ldo + jj] = NEG_INF;
+    const StripTicket k = strip_ticket_decode(strip_take_ticket(reinterpret_cast<u32*>(smem_raw), p.counters), p, 1, false);
+    const int j0 = k.s * W;
+    if (strip_is_dead(p, (int)p.out_len[k.b], (int)p.tgt_len[k.b], j0)) {
+        strip_fill_dead(p.alpha + (size_t)k.b * p.T * p.ldo, p.ldo, p.T, j0, W, p.L, MW_NT + 192);
         return;
     }
-    maxstripw_body<CPL>(p, smem_raw + 16, b, s, so);
+    maxstripw_body<CPL>(p, smem_raw + 16, k);
 }
 
 // ---- back-trace over a window of up to 128 predecessors: one wave per sample -------------------------------------------------------------
@@ -388,33 +274,28 @@ bool maxstripw_supported(int L, int TR) { return TR > 32 && TR <= 128 && (size_t
 size_t maxstripw_ws_bytes(int B, int T, int L, int TR)
 {
     const int cpl = TR <= 64 ? 2 : 1, W = cpl * MW_NT, TRP = 128 / cpl;
-    return (size_t)B * ((L + W - 1) / W) * T * TRP * sizeof(u64);
+    return strip_halo_bytes(1, B, (L + W - 1) / W, T, TRP);
 }
 
 template <int CPL>
-static int launch_mw(MWParams& p, int B, int T, int L, hipStream_t st)
+static int launch_mw(StripParams& p, hipStream_t st)
 {
     constexpr int W = CPL * MW_NT, TRP = 128 / CPL, RL = W + TRP;
-    p.NS = (L + W - 1) / W;
-    int rc = banded_acquire_ws(st, maxstripw_ws_bytes(B, T, L, p.TR), T, &p.counters, &p.halo, &p.tag_base);
+    p.NS = (p.L + W - 1) / W;
+    int rc = strip_acquire(p, maxstripw_ws_bytes(p.B, p.T, p.L, p.TR), st);
     if (rc) return rc;
-    const size_t lds_main = (size_t)(2 * RL + MW_RING * W) * 4 + 16;
+    const size_t lds_main = (size_t)(2 * RL + STRIP_RING * W) * 4 + 16;
     const size_t lds_tile = (size_t)(W + TRP) * 65 * 4 + 16;
     const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    auto k = dag_maxstripw_kernel<CPL>;
-    set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)(B * p.NS)), dim3(MW_NT + 192), lds, st, p);
-    return check_launch("dag_best_alignment(maxstripw)");
+    return launch_strip(dag_maxstripw_kernel<CPL>, p, p.B * p.NS, MW_NT + 192, lds, st, "dag_best_alignment(maxstripw)");
 }
 
 // alpha_max by column strips (values only), then the wide back-trace: no trace tensor
 int launch_dag_maxstripw(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                          float* alpha_max, int64_t* path, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
 {
-    MWParams p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha_max;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.ldm = ldm; p.ldo = ldo;
-    int rc = TR <= 64 ? launch_mw<2>(p, B, T, L, st) : launch_mw<1>(p, B, T, L, st);
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha_max, nullptr, nullptr, B, T, L, TR, 0, 1, ldm, ldo);
+    int rc = TR <= 64 ? launch_mw<2>(p, st) : launch_mw<1>(p, st);
     if (rc) return rc;
     const size_t lds = (size_t)L * 4;
     set_max_dynamic_lds((const void*)dag_backtrace_wide_kernel, (int)lds);

@@ -1,6 +1,6 @@
 // dag_dp_strip2.hip — banded (TR <= 32) DAG DP for gfx950, occupancy-oriented variant of dag_dp_strip4.hip:
-// K2 alpha || K3 beta in exp space, K6 max-DP + trace.  Read dag_dp_banded.hip (strips, granule hand-off, tickets) and
-// dag_dp_strip4.hip (exp-space recurrence, exactness guard) first; this file changes the WORK DISTRIBUTION:
+// K2 alpha || K3 beta in exp space, K6 max-DP + trace.  Strips, tickets and the granule hand-off are those of dag_strip.h; this file changes
+// the WORK DISTRIBUTION:
 //
 //   * 2 COLUMNS PER LANE.  With 4 columns per lane the C2 problem (B=32, L=4096, both directions) is exactly 1024 compute
 //     waves = ONE per SIMD, and rocprofv3 showed the kernel bound by exposed dependency stalls / LDS round trips / the row
@@ -11,64 +11,29 @@
 //     neighbour strip's halo granules into LDS rings with global_load_lds (sc1 for the granules), PD rows ahead, retired by
 //     ONE counted s_waitcnt per row.  Compute waves only store (alpha / trace / boundary granules) and never wait on vmcnt;
 //     the lanes next to the halo convert the landed granules (tag check; a stale tag falls back to a direct poll).
-#include "dag_dp.h"
-#include <stdlib.h>
+#include "dag_strip.h"
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-struct StripParams {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha; float* beta; int32_t* trace;
-    u64* halo; u32* counters;                 // counters[0] = ticket, [1] = error word, [2] = exact-fallback count
-    u32 tag_base;
-    int B, T, L, TR, NS, ndir;
-    int dbg;
-};
-
-constexpr int S2_RING = 8;
-constexpr int S2_PD = 6;                      // prefetch distance (rows) of the loader wave
-constexpr int S2_NEGSENT = -(1 << 30);     // "dead" exponent; far below any finite fp32 score
-constexpr u32 S2_SPIN_LIMIT = 1u << 22;
-constexpr float S2_LOG2E = 1.4426950408889634f;
-constexpr float S2_LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ u64 s2_gran_load(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void s2_gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void s2_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-template <int N> __device__ __forceinline__ void s2_wait_vmcnt() {
-    if constexpr (N <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else if constexpr (N == 25) asm volatile("s_waitcnt vmcnt(25)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
+// prefetch distance (rows) of this file's loader wave, which carries the halo granules next to the match rows.  Its own value, not the
+// STRIP_RING - 1 of strip_loader_wave: the further ahead of its producer a granule is requested, the likelier it lands stale and is polled for.
+constexpr int S2_PD = 6;
 
 // window element of (column c, distance d): alpha predecessor -> q = 32 + c - d ; beta successor -> q = c + d   (q in [0, 34))
 template <bool BETA> __device__ __forceinline__ constexpr int q2(int c, int d) { return BETA ? (c + d) : (32 + c - d); }
 
 template <int NT, int MODE, bool BETA>
-__device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw, int b, int s, int dirslot, int so)
+__device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw, const StripTicket& k)
 {
+    const int b = k.b, s = k.s;
     constexpr int W = 2 * NT, RL = W + 32, NCW = NT / 64, DPR = (W + 255) / 256;     // 1 KiB LDS-DMA pieces per match row
     float* Abuf = reinterpret_cast<float*>(smem_raw);          // [2][RL] a2 (MODE 0) / alpha_max (MODE 1)
     float* Pbuf = Abuf + 2 * RL;                               // [2][RL] mantissa 2^(a2 - ceil a2)
     int* Cbuf = reinterpret_cast<int*>(Pbuf + 2 * RL);         // [2][RL] exponent ceil(a2)
     float* Mring = reinterpret_cast<float*>(Cbuf + 2 * RL);    // [RING][W] match rows
-    u64* Hring = reinterpret_cast<u64*>(Mring + S2_RING * W);  // [RING][32] halo granules as landed by LDS-DMA
+    u64* Hring = reinterpret_cast<u64*>(Mring + STRIP_RING * W);  // [RING][32] halo granules as landed by LDS-DMA
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = p.T, L = p.L, TR = p.TR;
@@ -79,11 +44,10 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
     float* O = (BETA ? p.beta : p.alpha) + (size_t)b * T * L;
     const int nrows = Tb;
 
-    const bool has_producer = so > 0 && (BETA ? (j0 + W < Lb) : true);
-    const bool has_consumer = BETA ? (s > 0) : (s < p.NS - 1 && j0 + W < Lb);
-    const int prod_strip = BETA ? s + 1 : s - 1;
-    const u64* hin = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + (has_producer ? prod_strip : 0)) * (size_t)T * 32;
-    u64* hout = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + s) * (size_t)T * 32;
+    const StripHalo halo = strip_halo(p, k, BETA, W, 32, Lb);
+    const bool has_producer = halo.has_producer, has_consumer = halo.has_consumer;
+    const u64* hin = halo.in;
+    u64* hout = halo.out;
     const int halo_li0 = BETA ? W : 0;
     const int own_li0 = BETA ? 0 : 32;
 
@@ -139,7 +103,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                         float v;
                         if (!BETA) v = tile[(2 * lt + c - d + 32) * 33 + (d - 1)];
                         else { v = tile[(2 * lt + c) * 33 + (d - 1)]; if (j + c + d >= Lb) v = NEG_INF; }
-                        raw[d - 1] = (MODE == 0) ? v * S2_LOG2E : v;
+                        raw[d - 1] = (MODE == 0) ? v * LOG2E : v;
                         mx = fmaxf(mx, raw[d - 1]);
                     }
                     if (MODE == 0) {
@@ -167,12 +131,12 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
         const bool halo_lane = tid < 16;
         const int pub_c = BETA ? (2 * l) : (2 * l - (W - 32));
         const bool pub_lane = has_consumer && pub_c >= 0 && pub_c < 32;
-        s2_barrier();                            // prologue barrier: rows 0 .. PD-1 of match / halo are in the rings
+        strip_barrier();                            // prologue barrier: rows 0 .. PD-1 of match / halo are in the rings
 
         for (int it = 0; it < nrows; ++it) {
             const int t = BETA ? (Tb - 1 - it) : it;
             const int cur = it & 1, prv = cur ^ 1;
-            const int slot = it % S2_RING;
+            const int slot = it % STRIP_RING;
             const float2 mt = *reinterpret_cast<const float2*>(Mring + (size_t)slot * W + 2 * l);
             const float m2[2] = {mt.x, mt.y};
 
@@ -182,18 +146,9 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                 if (has_producer) {
                     const u32 want = p.tag_base + 1u + (u32)t;
                     const ulonglong2 gg = *reinterpret_cast<const ulonglong2*>(Hring + (size_t)slot * 32 + 2 * tid);
-                    u64 x0 = gg.x, x1 = gg.y;
-                    if ((u32)(x0 >> 32) != want || (u32)(x1 >> 32) != want) {      // DMA ran ahead of the producer: poll directly
-                        u32 spins = 0;
-                        for (;;) {
-                            x0 = s2_gran_load(hin + (size_t)t * 32 + 2 * tid);
-                            x1 = s2_gran_load(hin + (size_t)t * 32 + 2 * tid + 1);
-                            if ((u32)(x0 >> 32) == want && (u32)(x1 >> 32) == want) break;
-                            if (++spins > S2_SPIN_LIMIT) { atomicOr(&p.counters[1], 1u); break; }
-                            __builtin_amdgcn_s_sleep(1);
-                        }
-                    }
-                    hv[0] = __uint_as_float((u32)x0); hv[1] = __uint_as_float((u32)x1);
+                    u64 x[2] = {gg.x, gg.y};
+                    halo_wait<2>(hin + (size_t)t * 32 + 2 * tid, want, x, p.counters, lane);      // stale only if the DMA ran ahead of the producer
+                    hv[0] = __uint_as_float((u32)x[0]); hv[1] = __uint_as_float((u32)x[1]);
                 }
                 *reinterpret_cast<float2*>(Abuf + cur * RL + halo_li0 + 2 * tid) = make_float2(hv[0], hv[1]);
                 if (MODE == 0) {
@@ -203,7 +158,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                         const bool dead = hv[c] == NEG_INF;
                         const float cf = dead ? 0.f : ceilf(hv[c]);
                         pn[c] = __builtin_amdgcn_exp2f(hv[c] - cf);
-                        cn[c] = dead ? S2_NEGSENT : (int)cf;
+                        cn[c] = dead ? DEAD_EXP : (int)cf;
                     }
                     *reinterpret_cast<float2*>(Pbuf + cur * RL + halo_li0 + 2 * tid) = make_float2(pn[0], pn[1]);
                     *reinterpret_cast<int2*>(Cbuf + cur * RL + halo_li0 + 2 * tid) = make_int2(cn[0], cn[1]);
@@ -216,7 +171,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const bool seed = BETA ? (j + c == Lb - 1) : (j + c == 0);
-                    if (seed) a2[c] = (MODE == 0) ? m2[c] * S2_LOG2E : m2[c];
+                    if (seed) a2[c] = (MODE == 0) ? m2[c] * LOG2E : m2[c];
                 }
             } else if (MODE == 0) {
                 int cw[34];
@@ -242,9 +197,9 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                 }
                 const int hi = max(cm[0], cm[1]);
                 int refi = 0x7fffffff;
-                if (cm[0] != S2_NEGSENT) refi = cm[0];
-                if (cm[1] != S2_NEGSENT) refi = min(refi, cm[1]);
-                const bool any_live = hi != S2_NEGSENT;
+                if (cm[0] != DEAD_EXP) refi = cm[0];
+                if (cm[1] != DEAD_EXP) refi = min(refi, cm[1]);
+                const bool any_live = hi != DEAD_EXP;
                 if (!any_live) refi = 0;
                 const bool wide = (hi - refi) > 120;
                 v2f S2[2];
@@ -263,8 +218,8 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                 bool flag[2];
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const float cand = __builtin_amdgcn_logf(S[c]) + ref + lmax[c] + m2[c] * S2_LOG2E;
-                    const bool okc = cell_active(j + c, t) & (cm[c] != S2_NEGSENT);
+                    const float cand = __builtin_amdgcn_logf(S[c]) + ref + lmax[c] + m2[c] * LOG2E;
+                    const bool okc = cell_active(j + c, t) & (cm[c] != DEAD_EXP);
                     flag[c] = okc & (wide | !(S[c] >= 0x1p-97f));
                     a2[c] = (okc & !flag[c]) ? cand : NEG_INF;
                     need_fb |= flag[c];
@@ -282,7 +237,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                             for (int d = 1; d <= 32; ++d)
                                 sc = fmaf(__builtin_amdgcn_exp2f(Abuf[prv * RL + 2 * l + q2<BETA>(c, d)] - cmx), Eval(c, d), sc);
                             S[c] = sc;
-                            if (sc >= 0x1p-97f) a2[c] = __builtin_amdgcn_logf(sc) + cmx + lmax[c] + m2[c] * S2_LOG2E;
+                            if (sc >= 0x1p-97f) a2[c] = __builtin_amdgcn_logf(sc) + cmx + lmax[c] + m2[c] * LOG2E;
                         } else {
                             S[c] = 1.f;
                         }
@@ -306,7 +261,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                                     const int row = BETA ? (j + c) : (j + c - d);
                                     const bool ok = d <= TR && row >= 0 && row < L && (!BETA || j + c + d < Lb);
                                     const float raw = K[(size_t)(ok ? row : 0) * TR + (ok ? d - 1 : 0)];
-                                    lk[u] = ok ? raw * S2_LOG2E : NEG_INF;
+                                    lk[u] = ok ? raw * LOG2E : NEG_INF;
                                 }
 #pragma unroll
                                 for (int u = 0; u < 8; ++u) {
@@ -317,7 +272,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                                     mx = nm;
                                 }
                             }
-                            if (mx != NEG_INF) r = __builtin_amdgcn_logf(sum) + mx + ((c == 0) ? m2[0] : m2[1]) * S2_LOG2E;
+                            if (mx != NEG_INF) r = __builtin_amdgcn_logf(sum) + mx + ((c == 0) ? m2[0] : m2[1]) * LOG2E;
                         }
                         if (c == 0) a2[0] = r; else a2[1] = r;
                     }
@@ -367,34 +322,35 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
                     const bool dead = a2[c] == NEG_INF;
                     const float cf = dead ? 0.f : ceilf(a2[c]);
                     pn[c] = __builtin_amdgcn_exp2f(a2[c] - cf);
-                    cn[c] = dead ? S2_NEGSENT : (int)cf;
+                    cn[c] = dead ? DEAD_EXP : (int)cf;
                 }
                 *reinterpret_cast<float2*>(Pbuf + cur * RL + own_li0 + 2 * l) = make_float2(pn[0], pn[1]);
                 *reinterpret_cast<int2*>(Cbuf + cur * RL + own_li0 + 2 * l) = make_int2(cn[0], cn[1]);
             }
             *reinterpret_cast<float2*>(Abuf + cur * RL + own_li0 + 2 * l) = make_float2(a2[0], a2[1]);
             if (col_ok) {
-                const float2 o = (MODE == 0) ? make_float2(a2[0] * S2_LN2, a2[1] * S2_LN2) : make_float2(a2[0], a2[1]);
+                const float2 o = (MODE == 0) ? make_float2(a2[0] * LN2, a2[1] * LN2) : make_float2(a2[0], a2[1]);
                 *reinterpret_cast<float2*>(O + (size_t)t * L + j) = o;
                 if (MODE == 1) *reinterpret_cast<int2*>(p.trace + (size_t)b * T * L + (size_t)t * L + j) = make_int2(arg[0], arg[1]);
             }
             if (pub_lane) {
                 const u32 tag = p.tag_base + 1u + (u32)t;
-                s2_gran_store(hout + (size_t)t * 32 + pub_c, tag, a2[0]);
-                s2_gran_store(hout + (size_t)t * 32 + pub_c + 1, tag, a2[1]);
+                gran_store(hout + (size_t)t * 32 + pub_c, tag, a2[0]);
+                gran_store(hout + (size_t)t * 32 + pub_c + 1, tag, a2[1]);
             }
-            s2_barrier();
+            strip_barrier();
         }
         if (col_ok) for (int t = Tb; t < T; ++t) {
             *reinterpret_cast<float2*>(O + (size_t)t * L + j) = make_float2(NEG_INF, NEG_INF);
             if (MODE == 1) *reinterpret_cast<int2*>(p.trace + (size_t)b * T * L + (size_t)t * L + j) = make_int2(-1, -1);
         }
     } else {
-        // =========================================================== loader wave: LOADS ONLY (counted vmcnt is sound)
+        // =========================================================== loader wave: LOADS ONLY (counted vmcnt is sound).  Not strip_loader_wave:
+        // it also streams the halo granules, so its loads per row depend on has_producer, and the last piece of a 384-column row is half a wave.
         auto issue_row = [&](int itr) {
             const int t = BETA ? (Tb - 1 - itr) : itr;
             const float* rowp = M + (size_t)t * L;
-            float* mslot = Mring + (size_t)(itr % S2_RING) * W;
+            float* mslot = Mring + (size_t)(itr % STRIP_RING) * W;
 #pragma unroll
             for (int i = 0; i < DPR; ++i) {
                 const int col = j0 + i * 256 + lane * 4;
@@ -406,7 +362,7 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
             if (has_producer) {
                 // 32 granules = 256 B: lanes 0..15 carry them, the others re-read lane 0's piece into a scratch slot tail
                 const u64* g = hin + (size_t)t * 32 + 2 * (lane & 15);
-                u64* hs = Hring + (size_t)(itr % S2_RING) * 32;
+                u64* hs = Hring + (size_t)(itr % STRIP_RING) * 32;
                 if (lane < 16)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                                      (__attribute__((address_space(3))) void*)hs, 16, 0, 16 /* sc1 */);
@@ -414,19 +370,19 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
         };
         for (int pass = 0; pass < 2; ++pass) { stage_pass(pass); __syncthreads(); __syncthreads(); }
         for (int r = 0; r < S2_PD && r < nrows; ++r) issue_row(r);
-        s2_wait_vmcnt<0>();
-        s2_barrier();                            // prologue barrier
+        wait_vmcnt<0>();
+        strip_barrier();                            // prologue barrier
         for (int it = 0; it < nrows; ++it) {
             const int nx = it + S2_PD;
             if (nx < nrows) {
                 issue_row(nx);
                 // rows it+2 .. it+PD may stay in flight: (PD-1) * loads-per-row younger than row it+1's
-                if (has_producer) s2_wait_vmcnt<(S2_PD - 1) * (DPR + 1)>();
-                else s2_wait_vmcnt<(S2_PD - 1) * DPR>();
+                if (has_producer) wait_vmcnt<(S2_PD - 1) * (DPR + 1)>();
+                else wait_vmcnt<(S2_PD - 1) * DPR>();
             } else {
-                s2_wait_vmcnt<0>();
+                wait_vmcnt<0>();
             }
-            s2_barrier();
+            strip_barrier();
         }
     }
 }
@@ -434,39 +390,18 @@ __device__ __forceinline__ void strip2_body(const StripParams& p, char* smem_raw
 template <int NT, int MODE>
 __global__ __launch_bounds__(NT + 64, 3) void dag_strip2_kernel(StripParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 16-byte header (ticket); everything else starts at +16
     constexpr int W = 2 * NT;
-    u32* s_ticket = reinterpret_cast<u32*>(smem_raw);          // 16-byte header; everything else starts at +16
     const int tid = threadIdx.x;
-    if (tid == 0) *s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = *s_ticket;
-    const int per = p.ndir * p.B;
-    const int so = (int)(ticket / per);
-    const int rem = (int)(ticket % per);
-    const bool is_beta = (MODE == 0) && (p.alpha == nullptr || (p.ndir == 2 && rem >= p.B));
-    const int b = rem % p.B;
-    const int dirslot = (p.ndir == 2 && rem >= p.B) ? 1 : 0;
-    const int s = is_beta ? (p.NS - 1 - so) : so;
-    const int j0 = s * W;
-    const int T = p.T, L = p.L;
-    const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    u64* census = nullptr;
-    if (p.dbg && tid == 0) {                          // residency census of r01 (dbg != 0; the launcher passes 0): hw id + start clock per workgroup
-        census = p.halo + (size_t)p.ndir * p.B * p.NS * T * 32 + (size_t)ticket * 4;
-        u32 hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        census[0] = ((u64)xcc << 32) | hwid;
-        census[1] = __builtin_readcyclecounter();
-        census[2] = wall_clock64();
-    }
-    if (!valid || j0 >= Lb) {
+    const StripTicket k = strip_ticket_decode(strip_take_ticket(reinterpret_cast<u32*>(smem_raw), p.counters), p, p.ndir, MODE == 0);
+    const int b = k.b, T = p.T, L = p.L;
+    const int j0 = k.s * W;
+    if (strip_is_dead(p, (int)p.out_len[b], (int)p.tgt_len[b], j0)) {
+        // not strip_fill_dead: float2 stores, and the trace has to be filled with them
         if (tid < NT) {
             const int j = j0 + 2 * tid;
             if (j < L) {
-                float* O = (is_beta ? p.beta : p.alpha) + (size_t)b * T * L;
+                float* O = (k.is_beta ? p.beta : p.alpha) + (size_t)b * T * L;
                 for (int t = 0; t < T; ++t) {
                     *reinterpret_cast<float2*>(O + (size_t)t * L + j) = make_float2(NEG_INF, NEG_INF);
                     if (MODE == 1) *reinterpret_cast<int2*>(p.trace + (size_t)b * T * L + (size_t)t * L + j) = make_int2(-1, -1);
@@ -476,9 +411,8 @@ __global__ __launch_bounds__(NT + 64, 3) void dag_strip2_kernel(StripParams p)
         return;
     }
     __syncthreads();                               // everyone has read the ticket before the tile overlays the header area
-    if (MODE == 0 && is_beta) strip2_body<NT, MODE, true>(p, smem_raw + 16, b, s, dirslot, so);
-    else strip2_body<NT, MODE, false>(p, smem_raw + 16, b, s, dirslot, so);
-    if (census) census[3] = wall_clock64();
+    if (MODE == 0 && k.is_beta) strip2_body<NT, MODE, true>(p, smem_raw + 16, k);
+    else strip2_body<NT, MODE, false>(p, smem_raw + 16, k);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -487,19 +421,16 @@ __global__ __launch_bounds__(NT + 64, 3) void dag_strip2_kernel(StripParams p)
 constexpr int S2_NT = 192, S2_W = 2 * S2_NT;
 
 bool strip2_supported(int L, int TR, bool rows16) { return TR <= 32 && !(L & 3) && rows16; }
-size_t strip2_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * ((L + S2_W - 1) / S2_W) * T * 32 * sizeof(u64); }
+size_t strip2_ws_bytes(int B, int T, int L, int ndir) { return strip_halo_bytes(ndir, B, (L + S2_W - 1) / S2_W, T, 32); }
 
 template <int NT, int MODE>
 static int launch_strip2(const StripParams& p, int nwg, hipStream_t st)
 {
     constexpr int W = 2 * NT, RL = W + 32;
-    const size_t lds_main = (size_t)(6 * RL + S2_RING * W) * 4 + (size_t)S2_RING * 32 * 8;
+    const size_t lds_main = (size_t)(6 * RL + STRIP_RING * W) * 4 + (size_t)STRIP_RING * 32 * 8;
     const size_t lds_tile = (size_t)(NT + 34) * 33 * 4;
     const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    auto k = dag_strip2_kernel<NT, MODE>;
-    set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(NT + 64), lds, st, p);
-    return check_launch(MODE == 0 ? "dag_loss_fwd(strip2)" : "dag_best_alignment(strip2)");
+    return launch_strip(dag_strip2_kernel<NT, MODE>, p, nwg, NT + 64, lds, st, MODE == 0 ? "dag_loss_fwd(strip2)" : "dag_best_alignment(strip2)");
 }
 
 int launch_dag_strip2(int mode, const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
@@ -507,14 +438,10 @@ int launch_dag_strip2(int mode, const float* match, const float* links, const in
 {
     const int ndir = (mode == 0 && alpha && beta) ? 2 : 1;
     const int NS = (L + S2_W - 1) / S2_W;
-    StripParams p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
-    p.alpha = alpha; p.beta = beta; p.trace = trace;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.dbg = 0;
-    const int nwg = ndir * B * NS;
-    int rc = banded_acquire_ws(st, strip2_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha, beta, trace, B, T, L, TR, NS, ndir, L, L);
+    int rc = strip_acquire(p, strip2_ws_bytes(B, T, L, ndir), st);
     if (rc) return rc;
-    return mode == 0 ? launch_strip2<S2_NT, 0>(p, nwg, st) : launch_strip2<S2_NT, 1>(p, nwg, st);
+    return mode == 0 ? launch_strip2<S2_NT, 0>(p, ndir * B * NS, st) : launch_strip2<S2_NT, 1>(p, ndir * B * NS, st);
 }
 
 }  // namespace dsp

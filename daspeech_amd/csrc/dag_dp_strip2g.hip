@@ -2,8 +2,7 @@
 //
 // The TR <= 32 kernel (dag_dp_strip4g.hip: read its header first) keeps a lane's 4 x 32 transition weights in registers.  A 64-wide window
 // has the same 128 weights for TWO vertices, so this file is the same machine with the lane cut in half:
-//   * column strips of 512 vertices, one workgroup (4 compute waves + loader / fetch / publish helper waves) per (sample, direction, strip)
-//     for all T rows, tagged-granule hand-off of the 64 boundary columns, tickets — as strip4g;
+//   * column strips of 512 vertices, launch structure and hand-off of dag_strip.h with 64 boundary columns;
 //   * the previous row in LDS as plain values V = 2^(a2 - X) with ONE integer exponent X per group of 4 vertices (= a PAIR of lanes: the
 //     pair's maximum meets through one quad-permute), the exact log2-domain row beside it for the hand-off and the fallback paths;
 //   * a lane reads the 68-value window that starts at the 16-byte boundary under its first predecessor (17 ds_read_b128 + 17 exponents in one
@@ -15,57 +14,24 @@
 //     weights, and the exact path serves the same cells.
 // Until r06 these windows ran the log-space strips of dag_dp_banded.hip (2 x 64 v_exp per lane-row: 2.5 ms at C2 / TR = 64).
 // Replaces calculate_alpha_kernel / calculate_beta_kernel (dag_loss.cu:40-140,178-274) for 32 < translen <= 64.
-#include "dag_dp.h"
-#include <stdlib.h>
+#include "dag_strip.h"
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef float h2_v2f __attribute__((ext_vector_type(2)));
 typedef float h2_v4f __attribute__((ext_vector_type(4)));
 typedef int h2_v2i __attribute__((ext_vector_type(2)));
-
-struct H2Params {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha; float* beta;
-    u64* halo; u32* counters;                 // counters[0] = ticket, counters[1] = error word, counters[2] = exact-path cells
-    u32 tag_base;
-    int B, T, L, TR, NS, ndir;
-    int ldm, ldo;                             // row pitches (elements) of match and of alpha / beta (r06: >= L; the pad columns L .. round4(L)-1 of alpha / beta get -inf)
-};
 
 constexpr int H2_NT = 256;                    // compute lanes
 constexpr int H2_W = 2 * H2_NT;               // 512 columns per strip
 constexpr int H2_TRP = 64;                    // window / halo width
 constexpr int H2_RL = H2_W + H2_TRP;          // LDS row: strip + halo
 constexpr int H2_GL = H2_RL / 4;              // groups per LDS row
-constexpr int H2_RING = 8;
-constexpr int H2_CH = 4;                      // halo prefetch distance of the fetch wave (rows)
-constexpr int H2_NEG = -(1 << 30);            // "dead" exponent
-constexpr u32 H2_SPIN_LIMIT = 1u << 22;
-constexpr float H2_LOG2E = 1.4426950408889634f;
-constexpr float H2_LN2 = 0.6931471805599453f;
-constexpr float H2_BIAS = 120.f;
-
-__device__ __forceinline__ u64 h2_gran_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void h2_gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void h2_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// maximum with the other lane of the pair (lanes 2m, 2m+1): quad_perm [1,0,3,2]
-__device__ __forceinline__ float h2_pair_max(float v) {
-    return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false)));
-}
-
 template <bool BETA>
-__device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, int b, int s, int dirslot, int so)
+__device__ __forceinline__ void strip2g_body(const StripParams& p, char* smem_raw, const StripTicket& k)
 {
-    constexpr int W = H2_W, RL = H2_RL, GL = H2_GL, NCW = H2_NT / 64, DPR = W / 256, TRP = H2_TRP;
+    constexpr int W = H2_W, RL = H2_RL, GL = H2_GL, NCW = H2_NT / 64, TRP = H2_TRP;
+    const int b = k.b, s = k.s;
     float* Abuf = reinterpret_cast<float*>(smem_raw);          // [2][RL]  a2 = alpha * log2(e)  (exact row, log2 domain)
     float* Vbuf = Abuf + 2 * RL;                               // [2][RL]  V = 2^(a2 - X[group])
     int* Xbuf = reinterpret_cast<int*>(Vbuf + 2 * RL);         // [2][GL]  group exponents; group gi covers li 4gi..4gi+3
@@ -81,11 +47,7 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
     const int LDO = p.ldo, LPAD = min(p.ldo, (L + 3) & ~3);
     const int nrows = Tb;
 
-    const bool has_producer = so > 0 && (BETA ? (j0 + W < Lb) : true);
-    const bool has_consumer = BETA ? (s > 0) : (s < p.NS - 1 && j0 + W < Lb);
-    const int prod_strip = BETA ? s + 1 : s - 1;
-    const u64* hin = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + (has_producer ? prod_strip : 0)) * (size_t)T * TRP;
-    u64* hout = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + s) * (size_t)T * TRP;
+    const StripHalo halo = strip_halo(p, k, BETA, W, TRP, Lb);
     // LDS geometry: alpha li = col - j0 + 64 (halo [0,64)); beta li = col - j0 (halo [W, W+64))
     const int halo_li0 = BETA ? W : 0;
     const int own_li0 = BETA ? 0 : TRP;
@@ -134,7 +96,7 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
             float v;
             if (!BETA) v = tile[(2 * l + c - d + TRP) * 65 + (d - 1)];
             else { v = tile[(2 * l + c) * 65 + (d - 1)]; if (j + c + d >= Lb) v = NEG_INF; }
-            return v * H2_LOG2E;
+            return v * LOG2E;
         };
         float lmax[2], sthr[2];
         h2_v2f E2[2][34];                        // E2[c][i] = (weight of window element 2i, of 2i+1) for vertex c; 0 where the element is no predecessor
@@ -173,25 +135,25 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
         // (alpha, vertex 0) resp. 2 par + 1 + TR (beta, vertex 1)
         const int gcut = BETA ? ((2 * par + 1 + TR) >> 2) : ((TRP + 2 * par - TR) >> 2);
         __syncthreads();                         // tile consumed: the loader may start filling the ring over it
-        h2_barrier();                            // prologue barrier: match row 0 is in the ring
+        strip_barrier();                            // prologue barrier: match row 0 is in the ring
 
         for (int it = 0; it < nrows; ++it) {
             const int t = BETA ? (Tb - 1 - it) : it;
             const int cur = it & 1, prv = cur ^ 1;
             float a2[2] = {NEG_INF, NEG_INF};
             if (it == 0) {
-                const float2 mt = *reinterpret_cast<const float2*>(Mring + (size_t)(it % H2_RING) * W + 2 * l);
+                const float2 mt = *reinterpret_cast<const float2*>(Mring + (size_t)(it % STRIP_RING) * W + 2 * l);
                 const float m2[2] = {mt.x, mt.y};
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const bool seed = BETA ? (j + c == Lb - 1) : (j + c == 0);
-                    if (seed) a2[c] = m2[c] * H2_LOG2E;
+                    if (seed) a2[c] = m2[c] * LOG2E;
                 }
             } else {
                 // ---- row head: match (8 bytes), 17 group exponents, the 68-value window — one issue group, counted waits
                 h2_v2f mt; h2_v2i xa[8]; int x16; h2_v4f pv[17];
                 {
-                    const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % H2_RING) * W + 2 * l);
+                    const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % STRIP_RING) * W + 2 * l);
                     const u32 xaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Xbuf + prv * GL + (l >> 1));
                     const u32 vaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Vbuf + prv * RL + 4 * (l >> 1));
                     asm volatile("ds_read_b64 %0, %27\n\t"
@@ -231,7 +193,7 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
                 const float m2[2] = {mt.x, mt.y};
                 float base[2]; bool okc[2];
 #pragma unroll
-                for (int c = 0; c < 2; ++c) { okc[c] = cell_active(j + c, t); base[c] = lmax[c] + m2[c] * H2_LOG2E; }
+                for (int c = 0; c < 2; ++c) { okc[c] = cell_active(j + c, t); base[c] = lmax[c] + m2[c] * LOG2E; }
                 asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(xa[4]), "+v"(xa[5]), "+v"(xa[6]), "+v"(xa[7]), "+v"(x16));
                 // 26 LDS operations are in flight after the match; lgkmcnt only counts to 15: wait for "at most 15 outstanding" twice — the
                 // 17 window reads minus two — then treat the exponents as landed only once the count says so: the exponents are operations
@@ -246,12 +208,12 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
                 // predecessor of either vertex are therefore dropped from the window here: dead exponent, shifted to 0, out of the reference.
                 if (TR < 61) {
 #pragma unroll
-                    for (int g = 0; g < 17; ++g) if (BETA ? (g > gcut) : (g < gcut)) xw[g] = H2_NEG;
+                    for (int g = 0; g < 17; ++g) if (BETA ? (g > gcut) : (g < gcut)) xw[g] = DEAD_EXP;
                 }
                 int refi = xw[0];
 #pragma unroll
                 for (int g = 1; g < 17; ++g) refi = max(refi, xw[g]);
-                const bool any_live = refi != H2_NEG;
+                const bool any_live = refi != DEAD_EXP;
                 if (!any_live) refi = 0;
                 int kg[17];
 #pragma unroll
@@ -313,7 +275,7 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
                                         const int row = BETA ? (j + c) : (j + c - d);
                                         const bool ok = d <= TR && row >= 0 && row < L && (!BETA || j + c + d < Lb);
                                         const float raw = K[(size_t)(ok ? row : 0) * TR + (ok ? d - 1 : 0)];
-                                        lk[u] = ok ? raw * H2_LOG2E : NEG_INF;
+                                        lk[u] = ok ? raw * LOG2E : NEG_INF;
                                     }
 #pragma unroll
                                     for (int u = 0; u < 8; ++u) {
@@ -324,7 +286,7 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
                                         mx = nm;
                                     }
                                 }
-                                if (mx != NEG_INF) r = __builtin_amdgcn_logf(sum) + mx + (c == 0 ? m2[0] : m2[1]) * H2_LOG2E;
+                                if (mx != NEG_INF) r = __builtin_amdgcn_logf(sum) + mx + (c == 0 ? m2[0] : m2[1]) * LOG2E;
                             }
                         }
                         if (c == 0) a2[0] = r; else a2[1] = r;
@@ -334,21 +296,21 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
             // ---- write the row: LDS state for the next row, HBM output.  Group exponent X = ceil(largest of the PAIR's four) - 120.
             float vn[2]; int xn;
             {
-                const float amax = h2_pair_max(fmaxf(a2[0], a2[1]));
+                const float amax = pair_max(fmaxf(a2[0], a2[1]));
                 const bool dead = amax == NEG_INF;
-                const float cf = dead ? 0.f : ceilf(amax) - H2_BIAS;
+                const float cf = dead ? 0.f : ceilf(amax) - EXP_BIAS;
                 vn[0] = __builtin_amdgcn_exp2f(a2[0] - cf); vn[1] = __builtin_amdgcn_exp2f(a2[1] - cf);
-                xn = dead ? H2_NEG : (int)cf;
+                xn = dead ? DEAD_EXP : (int)cf;
             }
             *reinterpret_cast<float2*>(Vbuf + cur * RL + own_li0 + 2 * l) = make_float2(vn[0], vn[1]);
             if (!par) Xbuf[cur * GL + (own_li0 >> 2) + (l >> 1)] = xn;
             *reinterpret_cast<float2*>(Abuf + cur * RL + own_li0 + 2 * l) = make_float2(a2[0], a2[1]);
             if (col_ok) {
-                if (j + 1 < L) { O[(size_t)t * LDO + j] = a2[0] * H2_LN2; O[(size_t)t * LDO + j + 1] = a2[1] * H2_LN2; }
-                else O[(size_t)t * LDO + j] = a2[0] * H2_LN2;
+                if (j + 1 < L) { O[(size_t)t * LDO + j] = a2[0] * LN2; O[(size_t)t * LDO + j + 1] = a2[1] * LN2; }
+                else O[(size_t)t * LDO + j] = a2[0] * LN2;
                 if (j + 2 >= L) for (int c = L; c < LPAD; ++c) O[(size_t)t * LDO + c] = NEG_INF;       // the owner of the last column fills the pitch padding
             }
-            h2_barrier();
+            strip_barrier();
         }
         // rows the recurrence never reaches
         if (col_ok) for (int t = Tb; t < T; ++t) {
@@ -357,158 +319,60 @@ __device__ __forceinline__ void strip2g_body(const H2Params& p, char* smem_raw, 
             if (j + 2 >= L) for (int c = L; c < LPAD; ++c) O[(size_t)t * LDO + c] = NEG_INF;
         }
     } else if (wave == NCW) {
-        // =========================================================== loader wave: match rows -> LDS ring (LDS-DMA, 4 bytes per lane: rows
-        // of a dense tensor are not 16-byte aligned in general)
-        auto issue_row = [&](int itr) {
-            const int t = BETA ? (Tb - 1 - itr) : itr;
-            const float* rowp = M + (size_t)t * p.ldm;
-            float* slot = Mring + (size_t)(itr % H2_RING) * W;
-#pragma unroll
-            for (int i = 0; i < W / 64; ++i) {
-                const int col = j0 + i * 64 + lane;
-                const float* g = rowp + (col < L ? col : 0);          // out-of-range lanes re-read a valid address
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(slot + i * 64), 4, 0, 0);
-            }
-        };
+        // loader wave: 4 bytes per lane (rows of a dense tensor are not 16-byte aligned in general)
         __syncthreads();                         // link tile consumed
-        for (int r = 0; r < H2_RING - 1 && r < nrows; ++r) issue_row(r);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        h2_barrier();                            // prologue barrier
-        for (int it = 0; it < nrows; ++it) {
-            const int nx = it + H2_RING - 1;     // slot (it-1) % RING was last read during iteration it-1: free now
-            if (nx < nrows) {
-                issue_row(nx);
-                asm volatile("s_waitcnt vmcnt(48)" ::: "memory");      // rows it+2 .. it+7 may stay in flight: 6 x 8 DMAs younger than row it+1's
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            h2_barrier();
-        }
-        (void)DPR;
+        strip_loader_wave<W, 4, STRIP_RING, STRIP_RING - 1, BETA>(M, p.ldm, Mring, j0, L, nrows, lane);
     } else if (wave == NCW + 1) {
-        // =========================================================== fetch wave: neighbour strip's 64 boundary values -> LDS
-        u64 g[H2_CH];
-#pragma unroll
-        for (int k = 0; k < H2_CH; ++k) g[k] = 0;
-        auto load_row = [&](int itr) -> u64 {
-            if (itr < nrows) { const int t = BETA ? (Tb - 1 - itr) : itr; return h2_gran_load(hin + (size_t)t * TRP + lane); }
-            return 0;
-        };
-        if (has_producer) {
-#pragma unroll
-            for (int k = 0; k < H2_CH; ++k) g[k] = load_row(k);
-        }
+        // fetch wave: the halo's sixteen groups of 4 columns = quads of lanes
+        u64 g[STRIP_CH][1];
+        strip_fetch_prime<TRP, 1, STRIP_CH, BETA>(halo.in, halo.has_producer, nrows, lane, g);
         __syncthreads();                         // link tile consumed
-        h2_barrier();                            // prologue barrier
-        for (int itb = 0; itb < nrows; itb += H2_CH) {
-#pragma unroll
-            for (int k = 0; k < H2_CH; ++k) {
-                const int it = itb + k;
-                if (it >= nrows) break;
-                const int t = BETA ? (Tb - 1 - it) : it;
-                const int cur = it & 1;
-                float hv = NEG_INF;
-                if (has_producer) {
-                    const u32 want = p.tag_base + 1u + (u32)t;
-                    u64 x = g[k];
-                    u32 spins = 0;
-                    while (!__all((u32)(x >> 32) == want)) {
-                        if ((u32)(x >> 32) != want) x = h2_gran_load(hin + (size_t)t * TRP + lane);
-                        if (++spins > H2_SPIN_LIMIT) { if (lane == 0) atomicOr(&p.counters[1], 1u); break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    hv = __uint_as_float((u32)x);
-                }
-                {
-                    // the halo's sixteen groups: exponent = ceil(max of 4) by two quad-permute steps
-                    float gm = fmaxf(hv, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, hv), 0xB1, 0xF, 0xF, false)));
-                    gm = fmaxf(gm, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, gm), 0x4E, 0xF, 0xF, false)));
-                    const bool dead = gm == NEG_INF;
-                    const float cf = dead ? 0.f : ceilf(gm) - H2_BIAS;
-                    const float v = __builtin_amdgcn_exp2f(hv - cf);
-                    Abuf[cur * RL + halo_li0 + lane] = hv;
-                    Vbuf[cur * RL + halo_li0 + lane] = v;
-                    if ((lane & 3) == 0) Xbuf[cur * GL + (halo_li0 >> 2) + (lane >> 2)] = dead ? H2_NEG : (int)cf;
-                }
-                if (has_producer) g[k] = load_row(it + H2_CH);
-                h2_barrier();
-            }
-        }
+        strip_fetch_rows<TRP, 1, STRIP_CH, BETA>(p, halo.in, halo.has_producer, nrows, lane, g, [&](int it, const float (&hv)[1]) {
+            const int cur = it & 1;
+            const float gm = quad_max(hv[0]);
+            const bool dead = gm == NEG_INF;
+            const float cf = dead ? 0.f : ceilf(gm) - EXP_BIAS;
+            const float v = __builtin_amdgcn_exp2f(hv[0] - cf);
+            Abuf[cur * RL + halo_li0 + lane] = hv[0];
+            Vbuf[cur * RL + halo_li0 + lane] = v;
+            if ((lane & 3) == 0) Xbuf[cur * GL + (halo_li0 >> 2) + (lane >> 2)] = dead ? DEAD_EXP : (int)cf;
+        });
     } else {
-        // =========================================================== publish wave: 64 boundary columns -> granules
-        const bool pl = has_consumer;
-        const int pub_li0 = BETA ? 0 : (TRP + W - TRP);       // alpha: the strip's last 64 columns (li W .. W+63); beta: its first 64 (li 0 .. 63)
+        // publish wave.  alpha: the strip's last 64 columns (li W .. W+63); beta: its first 64 (li 0 .. 63)
         __syncthreads();                         // link tile consumed
-        h2_barrier();                            // prologue barrier
-        for (int it = 0; it < nrows; ++it) {
-            if (it > 0 && pl) {                  // row it-1 is complete (barrier it-1 passed); compute now writes the other buffer
-                const int tp = BETA ? (Tb - it) : (it - 1);
-                const float v = Abuf[((it - 1) & 1) * RL + pub_li0 + lane];
-                h2_gran_store(hout + (size_t)tp * TRP + lane, p.tag_base + 1u + (u32)tp, v);
-            }
-            h2_barrier();
-        }
-        if (pl && nrows > 0) {
-            const int it = nrows;
-            const int tp = BETA ? (Tb - it) : (it - 1);
-            const float v = Abuf[((it - 1) & 1) * RL + pub_li0 + lane];
-            h2_gran_store(hout + (size_t)tp * TRP + lane, p.tag_base + 1u + (u32)tp, v);
-        }
+        strip_publish_wave<TRP, 1, BETA>(p, halo.out, Abuf + (BETA ? 0 : W), RL, halo.has_consumer, nrows, lane);
     }
 }
 
-__global__ __launch_bounds__(H2_NT + 192) void dag_strip2g_kernel(H2Params p)
+__global__ __launch_bounds__(H2_NT + 192) void dag_strip2g_kernel(StripParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    u32* s_ticket = reinterpret_cast<u32*>(smem_raw);          // 16-byte header; everything else starts at +16
-    const int tid = threadIdx.x;
-    if (tid == 0) *s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = *s_ticket;
-    const int per = p.ndir * p.B;
-    const int so = (int)(ticket / per);
-    const int rem = (int)(ticket % per);
-    const bool is_beta = p.alpha == nullptr || (p.ndir == 2 && rem >= p.B);
-    const int b = rem % p.B;
-    const int dirslot = (p.ndir == 2 && rem >= p.B) ? 1 : 0;
-    const int s = is_beta ? (p.NS - 1 - so) : so;
-    const int j0 = s * H2_W;
-    const int T = p.T, L = p.L;
-    const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    if (!valid || j0 >= Lb) {                    // nothing reachable in this strip: -inf everywhere, no hand-off
-        float* O = (is_beta ? p.beta : p.alpha) + (size_t)b * T * p.ldo;
-        const int lpad = min(p.ldo, (L + 3) & ~3);
-        for (int jj = j0 + tid; jj < j0 + H2_W && jj < lpad; jj += H2_NT + 192)
-            for (int t = 0; t < T; ++t) O[(size_t)t * p.ldo + jj] = NEG_INF;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 16-byte header (ticket); everything else starts at +16
+    const StripTicket k = strip_ticket_decode(strip_take_ticket(reinterpret_cast<u32*>(smem_raw), p.counters), p, p.ndir, true);
+    const int j0 = k.s * H2_W;
+    if (strip_is_dead(p, (int)p.out_len[k.b], (int)p.tgt_len[k.b], j0)) {
+        strip_fill_dead((k.is_beta ? p.beta : p.alpha) + (size_t)k.b * p.T * p.ldo, p.ldo, p.T, j0, H2_W, min(p.ldo, (p.L + 3) & ~3), H2_NT + 192);
         return;
     }
     __syncthreads();                             // everyone has read the ticket before the tile overlays it
-    if (is_beta) strip2g_body<true>(p, smem_raw + 16, b, s, dirslot, so);
-    else strip2g_body<false>(p, smem_raw + 16, b, s, dirslot, so);
+    if (k.is_beta) strip2g_body<true>(p, smem_raw + 16, k);
+    else strip2g_body<false>(p, smem_raw + 16, k);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
 bool strip2g_supported(int L, int TR) { return TR > 32 && TR <= H2_TRP && L >= 1; }
-size_t strip2g_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * ((L + H2_W - 1) / H2_W) * T * H2_TRP * sizeof(u64); }
+size_t strip2g_ws_bytes(int B, int T, int L, int ndir) { return strip_halo_bytes(ndir, B, (L + H2_W - 1) / H2_W, T, H2_TRP); }
 
 int launch_dag_strip2g(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
                        float* alpha, float* beta, int B, int T, int L, int TR, int ldm, int ldo, hipStream_t st)
 {
     const int ndir = (alpha && beta) ? 2 : 1;
-    const int NS = (L + H2_W - 1) / H2_W;
-    H2Params p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len; p.alpha = alpha; p.beta = beta;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.ldm = ldm; p.ldo = ldo;
-    int rc = banded_acquire_ws(st, strip2g_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, (L + H2_W - 1) / H2_W, ndir, ldm, ldo);
+    int rc = strip_acquire(p, strip2g_ws_bytes(B, T, L, ndir), st);
     if (rc) return rc;
-    const size_t lds_main = (size_t)(4 * H2_RL + 2 * H2_GL + H2_RING * H2_W) * 4 + 16;
+    const size_t lds_main = (size_t)(4 * H2_RL + 2 * H2_GL + STRIP_RING * H2_W) * 4 + 16;
     const size_t lds_tile = (size_t)(H2_W + H2_TRP) * 65 * 4 + 16;
     const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    set_max_dynamic_lds((const void*)dag_strip2g_kernel, (int)lds);
-    hipLaunchKernelGGL(dag_strip2g_kernel, dim3((unsigned)(ndir * B * NS)), dim3(H2_NT + 192), lds, st, p);
-    return check_launch("dag_loss_fwd(strip2g)");
+    return launch_strip(dag_strip2g_kernel, p, ndir * B * p.NS, H2_NT + 192, lds, st, "dag_loss_fwd(strip2g)");
 }
 
 }  // namespace dsp

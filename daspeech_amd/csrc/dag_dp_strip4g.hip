@@ -1,7 +1,7 @@
 // dag_dp_strip4g.hip — banded (TR <= 32) DAG DP, K2 alpha || K3 beta in EXP SPACE with ONE EXPONENT PER LANE GROUP.
 //
-// Same launch structure as dag_dp_strip4.hip (column strips, tagged-granule hand-off, tickets, loader / fetch / publish
-// helper waves — read that header first).  What changes is the representation of the previous DP row in LDS:
+// Launch structure and hand-off: dag_strip.h (32 boundary columns, one granule per helper lane, lanes 32 .. 63 idle).  What this file is
+// about is the representation of the previous DP row in LDS, against the per-vertex form that preceded it:
 //
 //   strip4 : per VERTEX (mantissa P, exponent C)  -> per lane-row 18 ds_read_b128, a 35-op max tree, 36 sub + 36 ldexp
 //   strip4g: per LANE GROUP of 4 vertices one integer exponent X, the 4 values stored as plain f32  V = 2^(a2 - X)
@@ -15,55 +15,27 @@
 // nine group exponents: scaled values are <= 2^120 and nothing above 2^-246 of the window maximum is flushed, so a sum
 // S >= 2^-97 has lost at most 36 * 2^-126: exact to fp32.  S < 2^-97 or inf sends the cell to the register-only "medium" path
 // (own maximum, log-domain row) and then the exact log-space path as in strip4.
-#include "dag_dp.h"
+#include "dag_strip.h"
 #include <stdlib.h>
 #include <string.h>
 
 namespace dsp {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-struct GStripParams {
-    const float* match; const float* links; const int64_t* out_len; const int64_t* tgt_len;
-    float* alpha; float* beta; int32_t* trace;
-    u64* halo; u32* counters;                 // counters[0] = ticket, counters[1] = error word
-    u32 tag_base;
-    int B, T, L, TR, NS, ndir;
-    int ldm, ldo;                             // row pitch (elements) of match and of alpha / beta: >= L, multiples of 4 (r06: graphs whose length is not)
-    int dbg;
-};
-
 constexpr int G4_TRP = 32;
-constexpr int G4_RING = 8;
-constexpr int G4_CH = 4;                      // halo prefetch distance of the fetch wave (rows)
-constexpr int GNEGSENT = -(1 << 30);       // "dead" exponent; far below any finite fp32 score
-constexpr u32 G4_SPIN_LIMIT = 1u << 22;
-constexpr float G4_LOG2E = 1.4426950408889634f;
-constexpr float G4_BIAS = 120.f;              // stored / scaled values reach 2^120, a row sum of 36 stays under 2^126
-constexpr float G4_LN2 = 0.6931471805599453f;
 
-__device__ __forceinline__ u64 g4_gran_load(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void g4_gran_store(u64* p, u32 tag, float v) {
-    __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // dbg 2 (a -DDSP_PROF build run with DSP_DEBUG=prof): per-wave cycle accounting (s_memtime) of own work / barrier wait / LDS-read wait, for two workgroups
 struct G4Prof { u64 last, work, wait, rd, fma, tmid; };
 template <bool PROF>
 __device__ __forceinline__ void g4_barrier(G4Prof& pf) {
+    if (!PROF) { strip_barrier(); return; }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (PROF) {
-        const u64 t0 = __builtin_amdgcn_s_memtime();
-        pf.work += t0 - pf.last;
-        __builtin_amdgcn_s_barrier();
-        const u64 t1 = __builtin_amdgcn_s_memtime();
-        pf.wait += t1 - t0; pf.last = t1;
-    } else {
-        __builtin_amdgcn_s_barrier();
-    }
+    const u64 t0 = __builtin_amdgcn_s_memtime();
+    pf.work += t0 - pf.last;
+    __builtin_amdgcn_s_barrier();
+    const u64 t1 = __builtin_amdgcn_s_memtime();
+    pf.wait += t1 - t0; pf.last = t1;
     asm volatile("" ::: "memory");
 }
 
@@ -77,11 +49,12 @@ template <bool BETA> __device__ __forceinline__ constexpr bool gpair_live(int c,
 }
 
 template <int NT, int MODE, bool BETA, bool PROF>
-__device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_raw, int b, int s, int dirslot, int so, int profslot)
+__device__ __forceinline__ void strip4g_body(const StripParams& p, char* smem_raw, const StripTicket& k, int profslot)
 {
+    const int b = k.b, s = k.s;
     G4Prof pf; pf.last = PROF ? __builtin_amdgcn_s_memtime() : 0; pf.work = pf.wait = pf.rd = pf.fma = pf.tmid = 0;
     if (PROF && profslot >= 0 && threadIdx.x == 0) p.counters[50 + profslot * 3] = (u32)__builtin_amdgcn_s_memrealtime();
-    constexpr int W = 4 * NT, RL = W + 32, GL = NT + 8, NCW = NT / 64, DPR = W / 256;
+    constexpr int W = 4 * NT, RL = W + 32, GL = NT + 8, NCW = NT / 64;
     float* Abuf = reinterpret_cast<float*>(smem_raw);          // [2][RL]  a2 = alpha * log2(e)  (exact row, log2 domain)
     float* Vbuf = Abuf + 2 * RL;                               // [2][RL]  V = 2^(a2 - X[group])  (NaN = escaped, 0 = dead)
     int* Xbuf = reinterpret_cast<int*>(Vbuf + 2 * RL);         // [2][GL]  group exponents; group gi covers li 4gi..4gi+3
@@ -98,15 +71,10 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
     const int LDM = p.ldm, LDO = p.ldo;
     const int nrows = Tb;
 
-    const bool has_producer = so > 0 && (BETA ? (j0 + W < Lb) : true);
-    const bool has_consumer = BETA ? (s > 0) : (s < p.NS - 1 && j0 + W < Lb);
-    const int prod_strip = BETA ? s + 1 : s - 1;
-    const u64* hin = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + (has_producer ? prod_strip : 0)) * (size_t)T * G4_TRP;
-    u64* hout = p.halo + ((size_t)(dirslot * p.B + b) * p.NS + s) * (size_t)T * G4_TRP;
+    const StripHalo halo = strip_halo(p, k, BETA, W, G4_TRP, Lb);
     // LDS geometry: alpha li = col - j0 + 32 (halo [0,32)); beta li = col - j0 (halo [W, W+32))
     const int halo_li0 = BETA ? W : 0;
     const int own_li0 = BETA ? 0 : 32;
-    const int pub_li0 = BETA ? 0 : W;          // boundary columns handed to the consumer: alpha last 32, beta first 32
 
     // ---- prologue: the strip's transition rows -> LDS tile (coalesced, once), then -> registers ----
     // tile[r][d] = links[rlo + r][d] (pitch 33), -inf outside the graph / beyond TR.  The tile overlays the main-loop
@@ -130,6 +98,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
         }
     }
     __syncthreads();
+    auto bar = [&]() { g4_barrier<PROF>(pf); };   // the helper waves' row barrier
 
     if (wave < NCW) {
         // =========================================================== compute waves
@@ -157,7 +126,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                 float v;
                 if (!BETA) v = tile[(4 * l + c - d + 32) * 33 + (d - 1)];
                 else { v = tile[(4 * l + c) * 33 + (d - 1)]; if (j + c + d >= Lb) v = NEG_INF; }
-                raw[d - 1] = (MODE == 0) ? v * G4_LOG2E : v;
+                raw[d - 1] = (MODE == 0) ? v * LOG2E : v;
                 mx = fmaxf(mx, raw[d - 1]);
             }
             if (MODE == 0) {
@@ -209,14 +178,14 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
             if (PROF && profslot >= 0 && tid == 0 && it == 64) p.counters[51 + profslot * 3] = (u32)__builtin_amdgcn_s_memrealtime();
             float a2[4] = {NEG_INF, NEG_INF, NEG_INF, NEG_INF};
             float vn[4] = {0.f, 0.f, 0.f, 0.f};
-            int xn = GNEGSENT;
+            int xn = DEAD_EXP;
             if (it == 0) {
-                const float4 mt = *reinterpret_cast<const float4*>(Mring + (size_t)(it % G4_RING) * W + 4 * l);
+                const float4 mt = *reinterpret_cast<const float4*>(Mring + (size_t)(it % STRIP_RING) * W + 4 * l);
                 const float m2[4] = {mt.x, mt.y, mt.z, mt.w};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const bool seed = BETA ? (j + c == Lb - 1) : (j + c == 0);
-                    if (seed) a2[c] = m2[c] * G4_LOG2E;
+                    if (seed) a2[c] = m2[c] * LOG2E;
                 }
             } else {
                 // ---- row head: all 15 LDS reads (match, nine group exponents, the 36-value window: li 4l .. 4l+35, groups
@@ -226,7 +195,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                 // exposes six LDS round trips per row.
                 v4f mt; v2i x01, x23, x45, x67; int x8; v4f pv[9];
                 {
-                    const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % G4_RING) * W + 4 * l);
+                    const u32 maddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Mring + (size_t)(it % STRIP_RING) * W + 4 * l);
                     const u32 xaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Xbuf + prv * GL + l);
                     const u32 vaddr = (u32)(uintptr_t)(__attribute__((address_space(3))) void*)(Vbuf + prv * RL + 4 * l);
 #define G4_ROW_HEAD_READS \
@@ -266,7 +235,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     okc[c] = cell_active(j + c, t);
-                    base[c] = lmax[c] + m2[c] * G4_LOG2E;                    // log2(strongest link * emission)
+                    base[c] = lmax[c] + m2[c] * LOG2E;                    // log2(strongest link * emission)
                 }
                 // (2) group exponents landed.  Reference = largest of the nine: groups are stored with a +120 bias (see the
                 // row write), so scaled values reach 2^120 at most (sums < 2^126) and a column whose predecessors all sit up
@@ -275,7 +244,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                 asm volatile("s_waitcnt lgkmcnt(9)" : "+v"(x01), "+v"(x23), "+v"(x45), "+v"(x67), "+v"(x8));
                 const int xw[9] = {x01.x, x01.y, x23.x, x23.y, x45.x, x45.y, x67.x, x67.y, x8};
                 int refi = max(max(max(xw[0], xw[1]), max(xw[2], xw[3])), max(max(xw[4], xw[5]), max(max(xw[6], xw[7]), xw[8])));
-                const bool any_live = refi != GNEGSENT;
+                const bool any_live = refi != DEAD_EXP;
                 if (!any_live) refi = 0;
                 // group shifts X - ref <= 0, applied to every value with v_ldexp_f32: a group FACTOR 2^(X - ref) would itself
                 // flush below 2^-126 and cut the window at 126 binades although the stored values (bias +120) reach 246
@@ -407,7 +376,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                                     const int row = BETA ? (j + c) : (j + c - d);
                                     const bool ok = d <= TR && row >= 0 && row < L && (!BETA || j + c + d < Lb);
                                     const float raw = K[(size_t)(ok ? row : 0) * TR + (ok ? d - 1 : 0)];
-                                    lk[u] = ok ? raw * G4_LOG2E : NEG_INF;
+                                    lk[u] = ok ? raw * LOG2E : NEG_INF;
                                 }
 #pragma unroll
                                 for (int u = 0; u < 8; ++u) {
@@ -420,7 +389,7 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                             }
                             if (mx != NEG_INF) {
                                 const float mm = (c == 0) ? m2[0] : (c == 1) ? m2[1] : (c == 2) ? m2[2] : m2[3];
-                                r = __builtin_amdgcn_logf(sum) + mx + mm * G4_LOG2E;
+                                r = __builtin_amdgcn_logf(sum) + mx + mm * LOG2E;
                             }
                         }
                         if (c == 0) a2[0] = r; else if (c == 1) a2[1] = r; else if (c == 2) a2[2] = r; else a2[3] = r;
@@ -434,20 +403,20 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
                 // group exponent X = ceil(largest of the four) - 120, so V = 2^(a2 - X) spans [2^-126, 2^120]
                 const float amax = fmaxf(fmaxf(a2[0], a2[1]), fmaxf(a2[2], a2[3]));
                 const bool dead = amax == NEG_INF;
-                const float cf = dead ? 0.f : ceilf(amax) - G4_BIAS;
+                const float cf = dead ? 0.f : ceilf(amax) - EXP_BIAS;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float e = a2[c] - cf;
                     const float v = __builtin_amdgcn_exp2f(e);
                     vn[c] = v;                 // flushes to 0 more than 246 binades under the group maximum — as the scaling would
                 }
-                xn = dead ? GNEGSENT : (int)cf;
+                xn = dead ? DEAD_EXP : (int)cf;
             }
             *reinterpret_cast<float4*>(Vbuf + cur * RL + own_li0 + 4 * l) = make_float4(vn[0], vn[1], vn[2], vn[3]);
             Xbuf[cur * GL + (own_li0 >> 2) + l] = xn;
             *reinterpret_cast<float4*>(Abuf + cur * RL + own_li0 + 4 * l) = make_float4(a2[0], a2[1], a2[2], a2[3]);
             if (col_ok)
-                *reinterpret_cast<float4*>(O + (size_t)t * LDO + j) = make_float4(a2[0] * G4_LN2, a2[1] * G4_LN2, a2[2] * G4_LN2, a2[3] * G4_LN2);
+                *reinterpret_cast<float4*>(O + (size_t)t * LDO + j) = make_float4(a2[0] * LN2, a2[1] * LN2, a2[2] * LN2, a2[3] * LN2);
             g4_barrier<PROF>(pf);
         }
         // rows the recurrence never reaches
@@ -455,112 +424,30 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
             *reinterpret_cast<float4*>(O + (size_t)t * LDO + j) = make_float4(NEG_INF, NEG_INF, NEG_INF, NEG_INF);
         }
     } else if (wave == NCW) {
-        // =========================================================== loader wave: match rows -> LDS ring (LDS-DMA)
-        auto issue_row = [&](int itr) {
-            const int t = BETA ? (Tb - 1 - itr) : itr;
-            const float* rowp = M + (size_t)t * LDM;
-            float* slot = Mring + (size_t)(itr % G4_RING) * W;
-#pragma unroll
-            for (int i = 0; i < DPR; ++i) {
-                const int col = j0 + i * 256 + lane * 4;
-                const float* g = rowp + (col < L ? col : 0);          // out-of-range lanes re-read a valid address
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(slot + i * 256), 16, 0, 0);
-            }
-        };
+        // loader wave: 16 bytes per lane
         __syncthreads();                         // link tile consumed
-        for (int r = 0; r < G4_RING - 1 && r < nrows; ++r) issue_row(r);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        g4_barrier<PROF>(pf);                            // prologue barrier
-        for (int it = 0; it < nrows; ++it) {
-            const int nx = it + G4_RING - 1;     // slot (it-1) % RING was last read during iteration it-1: free now
-            if (nx < nrows) {
-                issue_row(nx);
-                // rows it+2 .. it+7 may stay in flight: 6*DPR DMAs younger than row it+1's
-                if (DPR == 4) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-                else if (DPR == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            g4_barrier<PROF>(pf);
-        }
+        strip_loader_wave<W, 16, STRIP_RING, STRIP_RING - 1, BETA>(M, LDM, Mring, j0, L, nrows, lane, bar);
     } else if (wave == NCW + 1) {
-        // =========================================================== fetch wave: neighbour strip's halo -> LDS
-        const bool hl = lane < G4_TRP;
-        u64 g[G4_CH];
-#pragma unroll
-        for (int k = 0; k < G4_CH; ++k) g[k] = 0;
-        // rolling prefetch: row it+CH is requested when row it has been consumed, so every request has CH row times to land
-        // (the strip-0 speed is only reached if no row head waits on a memory round trip), and a consumer settles about
-        // CH + 3 rows behind its producer.
-        auto load_row = [&](int itr) -> u64 {
-            if (itr < nrows && hl) { const int t = BETA ? (Tb - 1 - itr) : itr; return g4_gran_load(hin + (size_t)t * G4_TRP + lane); }
-            return 0;
-        };
-        if (has_producer) {
-#pragma unroll
-            for (int k = 0; k < G4_CH; ++k) g[k] = load_row(k);
-        }
+        // fetch wave: the halo's eight lane groups, exponent = ceil(max of 4) over a quad of lanes
+        u64 g[STRIP_CH][1];
+        strip_fetch_prime<G4_TRP, 1, STRIP_CH, BETA>(halo.in, halo.has_producer, nrows, lane, g);
         __syncthreads();                         // link tile consumed
-        g4_barrier<PROF>(pf);                            // prologue barrier
-        for (int itb = 0; itb < nrows; itb += G4_CH) {
-#pragma unroll
-            for (int k = 0; k < G4_CH; ++k) {
-                const int it = itb + k;
-                if (it >= nrows) break;
-                const int t = BETA ? (Tb - 1 - it) : it;
-                const int cur = it & 1;
-                float hv = NEG_INF;
-                if (has_producer && hl) {
-                    const u32 want = p.tag_base + 1u + (u32)t;
-                    u64 x = g[k];
-                    u32 spins = 0;
-                    while (!__all((u32)(x >> 32) == want)) {
-                        if ((u32)(x >> 32) != want) x = g4_gran_load(hin + (size_t)t * G4_TRP + lane);
-                        if (++spins > G4_SPIN_LIMIT) { if (lane == 0) atomicOr(&p.counters[1], 1u); break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    hv = __uint_as_float((u32)x);
-                }
-                {
-                    // the halo's eight lane groups: exponent = ceil(max of 4) by two quad-permute steps
-                    float gm = fmaxf(hv, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, hv), 0xB1, 0xF, 0xF, false)));
-                    gm = fmaxf(gm, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, gm), 0x4E, 0xF, 0xF, false)));
-                    const bool dead = gm == NEG_INF;
-                    const float cf = dead ? 0.f : ceilf(gm) - G4_BIAS;
-                    const float e = hv - cf;
-                    const float v = __builtin_amdgcn_exp2f(e);
-                    if (hl) {
-                        Abuf[cur * RL + halo_li0 + lane] = hv;
-                        Vbuf[cur * RL + halo_li0 + lane] = v;
-                        if ((lane & 3) == 0) Xbuf[cur * GL + (halo_li0 >> 2) + (lane >> 2)] = dead ? GNEGSENT : (int)cf;
-                    }
-                }
-                if (has_producer) g[k] = load_row(it + G4_CH);
-                g4_barrier<PROF>(pf);
+        strip_fetch_rows<G4_TRP, 1, STRIP_CH, BETA>(p, halo.in, halo.has_producer, nrows, lane, g, [&](int it, const float (&hv)[1]) {
+            const int cur = it & 1;
+            const float gm = quad_max(hv[0]);
+            const bool dead = gm == NEG_INF;
+            const float cf = dead ? 0.f : ceilf(gm) - EXP_BIAS;
+            const float v = __builtin_amdgcn_exp2f(hv[0] - cf);
+            if (strip_halo_lane<G4_TRP, 1>(lane)) {
+                Abuf[cur * RL + halo_li0 + lane] = hv[0];
+                Vbuf[cur * RL + halo_li0 + lane] = v;
+                if ((lane & 3) == 0) Xbuf[cur * GL + (halo_li0 >> 2) + (lane >> 2)] = dead ? DEAD_EXP : (int)cf;
             }
-        }
+        }, bar);
     } else {
-        // =========================================================== publish wave: boundary columns -> granules
-        const bool pl = has_consumer && lane < G4_TRP;
+        // publish wave.  alpha: the strip's last 32 columns (li W .. W+31); beta: its first 32
         __syncthreads();                         // link tile consumed
-        g4_barrier<PROF>(pf);                            // prologue barrier
-        for (int it = 0; it < nrows; ++it) {
-            if (it > 0 && pl) {                  // row it-1 is complete (barrier it-1 passed); compute now writes the other buffer
-                const int tp = BETA ? (Tb - it) : (it - 1);
-                const float v = Abuf[((it - 1) & 1) * RL + (BETA ? 0 : 32) + (BETA ? 0 : (W - 32)) + lane];
-                g4_gran_store(hout + (size_t)tp * G4_TRP + lane, p.tag_base + 1u + (u32)tp, v);
-            }
-            g4_barrier<PROF>(pf);
-        }
-        if (pl && nrows > 0) {
-            const int it = nrows;
-            const int tp = BETA ? (Tb - it) : (it - 1);
-            const float v = Abuf[((it - 1) & 1) * RL + (BETA ? 0 : 32) + (BETA ? 0 : (W - 32)) + lane];
-            g4_gran_store(hout + (size_t)tp * G4_TRP + lane, p.tag_base + 1u + (u32)tp, v);
-        }
-        (void)pub_li0;
+        strip_publish_wave<G4_TRP, 1, BETA>(p, halo.out, Abuf + (BETA ? 0 : W), RL, halo.has_consumer, nrows, lane, bar);
     }
     if (PROF && profslot >= 0 && threadIdx.x == 0) p.counters[52 + profslot * 3] = (u32)__builtin_amdgcn_s_memrealtime();
     if (PROF && profslot >= 0 && lane == 0) {
@@ -571,33 +458,22 @@ __device__ __forceinline__ void strip4g_body(const GStripParams& p, char* smem_r
 }
 
 template <int NT, int MODE, bool PROF>
-__global__ __launch_bounds__(NT + 192) void dag_strip4g_kernel(GStripParams p)
+__global__ __launch_bounds__(NT + 192) void dag_strip4g_kernel(StripParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int W = 4 * NT, RL = W + 32, GL = NT + 8;
-    u32* s_ticket = reinterpret_cast<u32*>(smem_raw);          // 16-byte header; everything else starts at +16
-    (void)RL; (void)GL;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 16-byte header (ticket); everything else starts at +16
+    constexpr int W = 4 * NT;
     const int tid = threadIdx.x;
-    if (tid == 0) *s_ticket = atomicAdd(&p.counters[0], 1u);
-    __syncthreads();
-    const u32 ticket = *s_ticket;
+    const u32 ticket = strip_take_ticket(reinterpret_cast<u32*>(smem_raw), p.counters);
+    const StripTicket k = strip_ticket_decode(ticket, p, p.ndir, MODE == 0);
     const int per = p.ndir * p.B;
-    const int so = (int)(ticket / per);
-    const int rem = (int)(ticket % per);
-    const bool is_beta = (MODE == 0) && (p.alpha == nullptr || (p.ndir == 2 && rem >= p.B));
-    const int b = rem % p.B;
-    const int dirslot = (p.ndir == 2 && rem >= p.B) ? 1 : 0;
-    const int s = is_beta ? (p.NS - 1 - so) : so;
-    const int j0 = s * W;
-    const int T = p.T, L = p.L;
-    const int Lb = (int)p.out_len[b], Tb = (int)p.tgt_len[b];
-    const bool valid = !(Tb <= 0 || Lb <= 0 || Tb > T || Lb > L);
-    if (!valid || j0 >= Lb) {                    // nothing reachable in this strip: -inf everywhere, no hand-off
+    const int j0 = k.s * W;
+    if (strip_is_dead(p, (int)p.out_len[k.b], (int)p.tgt_len[k.b], j0)) {
+        // vector fill, not strip_fill_dead: rows are 16-byte aligned here, one float4 per lane and row
         if (tid < NT) {
             const int j = j0 + 4 * tid;
-            if (j < L) {
-                float* O = (is_beta ? p.beta : p.alpha) + (size_t)b * T * p.ldo;
-                for (int t = 0; t < T; ++t) {
+            if (j < p.L) {
+                float* O = (k.is_beta ? p.beta : p.alpha) + (size_t)k.b * p.T * p.ldo;
+                for (int t = 0; t < p.T; ++t) {
                     *reinterpret_cast<float4*>(O + (size_t)t * p.ldo + j) = make_float4(NEG_INF, NEG_INF, NEG_INF, NEG_INF);
                 }
             }
@@ -605,8 +481,8 @@ __global__ __launch_bounds__(NT + 192) void dag_strip4g_kernel(GStripParams p)
         return;
     }
     const int profslot = !PROF ? -1 : (ticket == 0 ? 0 : (ticket == 2u * (u32)per ? 1 : -1));
-    if (MODE == 0 && is_beta) strip4g_body<NT, MODE, true, PROF>(p, smem_raw + 16, b, s, dirslot, so, profslot);
-    else strip4g_body<NT, MODE, false, PROF>(p, smem_raw + 16, b, s, dirslot, so, profslot);
+    if (MODE == 0 && k.is_beta) strip4g_body<NT, MODE, true, PROF>(p, smem_raw + 16, k, profslot);
+    else strip4g_body<NT, MODE, false, PROF>(p, smem_raw + 16, k, profslot);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -617,19 +493,16 @@ bool strip4g_supported(int L, int TR, bool rows16) { (void)L; return TR <= 32 &&
 // strip width: 1024 columns when that still yields >= ~200 workgroups, else 512
 static bool strip4g_wide(int B, int L, int ndir) { return (long)ndir * B * ((L + 1023) / 1024) >= 200; }
 static int strip4g_strips(int B, int L, int ndir) { return strip4g_wide(B, L, ndir) ? (L + 1023) / 1024 : (L + 511) / 512; }
-size_t strip4g_ws_bytes(int B, int T, int L, int ndir) { return (size_t)ndir * B * strip4g_strips(B, L, ndir) * T * G4_TRP * sizeof(u64); }
+size_t strip4g_ws_bytes(int B, int T, int L, int ndir) { return strip_halo_bytes(ndir, B, strip4g_strips(B, L, ndir), T, G4_TRP); }
 
 template <int NT, bool PROF>
-static int launch_one_g(const GStripParams& p, int nwg, hipStream_t st)
+static int launch_one_g(const StripParams& p, int nwg, hipStream_t st)
 {
     constexpr int W = 4 * NT, RL = W + 32, GL = NT + 8;
-    const size_t lds_main = (size_t)(4 * RL + 2 * GL + G4_RING * W) * 4 + 16;
+    const size_t lds_main = (size_t)(4 * RL + 2 * GL + STRIP_RING * W) * 4 + 16;
     const size_t lds_tile = (size_t)(W + 32) * 33 * 4;
     const size_t lds = (lds_main > lds_tile ? lds_main : lds_tile) + 32;
-    auto k = dag_strip4g_kernel<NT, 0, PROF>;
-    set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(NT + 192), lds, st, p);
-    return check_launch("dag_loss_fwd(strip4g)");
+    return launch_strip(dag_strip4g_kernel<NT, 0, PROF>, p, nwg, NT + 192, lds, st, "dag_loss_fwd(strip4g)");
 }
 
 int launch_dag_strip4g(const float* match, const float* links, const int64_t* out_len, const int64_t* tgt_len,
@@ -637,19 +510,13 @@ int launch_dag_strip4g(const float* match, const float* links, const int64_t* ou
 {
     const int ndir = (alpha && beta) ? 2 : 1;
     const bool wide = strip4g_wide(B, L, ndir);
-    const int NS = strip4g_strips(B, L, ndir);
-    GStripParams p;
-    p.match = match; p.links = links; p.out_len = out_len; p.tgt_len = tgt_len;
-    p.alpha = alpha; p.beta = beta; p.trace = nullptr;
-    p.B = B; p.T = T; p.L = L; p.TR = TR; p.NS = NS; p.ndir = ndir; p.ldm = ldm; p.ldo = ldo;
+    StripParams p = strip_params(match, links, out_len, tgt_len, alpha, beta, nullptr, B, T, L, TR, strip4g_strips(B, L, ndir), ndir, ldm, ldo);
 #ifdef DSP_PROF                                     // instrumentation build only (tools/prof_strip.py): nothing on the product's launch path
     { static const char* const e = getenv("DSP_DEBUG"); p.dbg = (e && !strcmp(e, "prof")) ? 2 : 0; }
-#else
-    p.dbg = 0;
 #endif
-    int rc = banded_acquire_ws(st, strip4g_ws_bytes(B, T, L, ndir), T, &p.counters, &p.halo, &p.tag_base);
+    int rc = strip_acquire(p, strip4g_ws_bytes(B, T, L, ndir), st);
     if (rc) return rc;
-    const int nwg = ndir * B * NS;
+    const int nwg = ndir * B * p.NS;
 #ifdef DSP_PROF
     if (p.dbg == 2 && wide) return launch_one_g<256, true>(p, nwg, st);
 #endif
