@@ -245,48 +245,54 @@ static int hgs_launch(const HgsParams& p, hipStream_t st)
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // One ResBlock1 unit (hifi-gan/models.py:38-42) at fp32 accuracy in ONE launch: out = scale * (x + b2 + c2(lrelu(b1 + c1(lrelu(x))))) [+ out].
-// hifigan_resunit_kernel's structure (x tile -> c1 over NT+16 intermediate columns -> intermediate in LDS -> c2 -> output tile, one LDS
+// hifigan_resunit_kernel's structure (x tile -> c1 over the intermediate columns -> intermediate in LDS -> c2 -> output tile, one LDS
 // region with three tenants in turn) with split operands: the x tile and the intermediate each live as (hi, lo) fp16 planes, the
 // intermediate is split from the fp32 accumulators exactly where the layer chain would split the fp32 tensor it stores, so the result
 // is bit-identical to the two hifigan_conv_f32 launches it replaces — without their fp32 round trip of the intermediate through HBM.
+//
+// The time tile is a pair.  NTI (template) is the width of the intermediate: it fixes the accumulators and the LDS images.  nt (per
+// launch, hgs_unit_tile) is the width a workgroup stores: output column tl needs the intermediate columns tl .. tl + 2 h2
+// (h2 = (ntaps - 1) / 2), so the intermediate starts at t0 - h2 and nt <= NTI - 2 h2 — a k = 3 unit stores NTI - 2 columns of the NTI it
+// computed, not the NTI - 16 a tap-blind tile leaves.  Per-element arithmetic and K order do not depend on where a tile starts.
 struct HgsUnitParams {
     const float* x; const _Float16* w1; const float* b1; const _Float16* w2; const float* b2; float* out;     // w1 / w2: [hi | lo] packed
-    int B, T, ntaps, dil, accumulate;
+    int B, T, nt, ntaps, dil, accumulate;
     float slope, scale;
     const int* lens; int len_mul;
 };
 
-template <int C, int NT, int WM, int WN>
-__global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_resunit_f32_kernel(HgsUnitParams p)
+template <int C, int NTI, int WM, int WN, bool TRIM>
+__global__ __launch_bounds__(512, (C == 64 ? 2 : 4)) void hifigan_resunit_f32_kernel(HgsUnitParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CH = C / 8, NC = C / 32;
-    constexpr int NTI = NT + 16;
     constexpr int MI = C / WM / 16, NI = NTI / WN / 16;
+    constexpr int NJ2 = TRIM ? NI - 1 : NI;                 // 16-column tiles of c2 per wave (TRIM: nt <= NTI - 16, the last one is not needed)
     constexpr int OPITCH = C + 4;
     static_assert(WM * WN == 8 && MI >= 1 && NI >= 1 && NTI % (WN * 16) == 0, "8 waves, intermediate tile divisible");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    static_assert(!TRIM || (WN == 1 && NI > 1), "a whole c2 tile can be left out only where one wave column spans the time tile");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (a scalar: wm, wn, co_base stay out of the VGPRs)
     const int wm = wave % WM, wn = wave / WM;
     const int lr = lane & 15, lk = lane >> 4;
-    const int b = blockIdx.z, t0 = blockIdx.x * NT;
+    const int nt = p.nt;
+    const int b = blockIdx.z, t0 = blockIdx.x * nt;
     const int h1 = p.dil * (p.ntaps - 1) / 2, h2 = (p.ntaps - 1) / 2;
-    const int R1 = NTI + 2 * h1;
-    constexpr int RM = NTI + 16;                            // intermediate rows + the slack c2's last 16 columns read (never stored)
+    const int R1 = NTI + 2 * h1;                            // x tile: rows t0 - h2 - h1 ...
+    constexpr int RM = NTI + 16;                            // intermediate rows (t0 - h2 ...) + the slack c2's last columns read (never stored)
     const float* X = p.x + (size_t)b * p.T * C;
     const int Tb = hgs_valid_len(p.lens, p.len_mul, b, p.T);
     if (t0 >= Tb) return;
     char* xhi = smem; char* xlo = smem + (size_t)R1 * C * 2;
     char* mhi = smem; char* mlo = smem + (size_t)RM * C * 2;
-    hgs_stage_tile<C, 4>(xhi, xlo, X, Tb, t0 - 8 - h1, R1, p.slope, tid);
+    hgs_stage_tile<C, 4>(xhi, xlo, X, Tb, t0 - h2 - h1, R1, p.slope, tid);
     __syncthreads();
 
     f4 accm[MI][NI], accc[MI][NI];
     const int co_base = wm * (MI * 16);
     const int nsteps = p.ntaps * NC;
     const size_t wn_elems = (size_t)nsteps * (C / 16) * 512;       // halves in the hi (and in the lo) part of a packed weight buffer
-    // NJ: 16-column tiles this wave computes (c2 needs NT of the NTI columns: with one wave column the last tile is skipped — a quarter
-    // of c2's MFMAs at C = 256, an eighth at C = 128)
-    auto conv = [&](auto njc, const _Float16* W, const char* thi, const char* tlo, int row0, int rstep) {
+    // NJ: 16-column tiles this wave computes
+    auto conv = [&](auto njc, const _Float16* W, const char* thi, const char* tlo, int rstep) {
         constexpr int NJ = decltype(njc)::value;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -304,7 +310,7 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
             const int k = step / NC, c = step - k * NC;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const int row = (wn * NI + j) * 16 + lr + row0 + k * rstep;
+                const int row = (wn * NI + j) * 16 + lr + k * rstep;
                 const size_t o = ((size_t)row * CH + hgs_swz<C>(row, c * 4 + lk)) * 16;
                 const h8 bh = *reinterpret_cast<const h8*>(thi + o);
                 const h8 bl = *reinterpret_cast<const h8*>(tlo + o);
@@ -329,7 +335,7 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
     };
 
     // ---- c1 over the NTI intermediate columns -> mid = split(lrelu(acc + b1)), zero outside [0, Tb) ----
-    conv(std::integral_constant<int, NI>{}, p.w1, xhi, xlo, 0, p.dil);
+    conv(std::integral_constant<int, NI>{}, p.w1, xhi, xlo, p.dil);
     __syncthreads();                                  // every wave is done reading the x tile: its space becomes the intermediate
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -339,7 +345,7 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int m = (wn * NI + j) * 16 + lr;
-            const int tm = t0 - 8 + m;
+            const int tm = t0 - h2 + m;
             _Float16 hv[4], lv[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -356,8 +362,8 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
     }
     __syncthreads();                                  // intermediate complete
 
-    // ---- c2 over the NT output columns ----
-    conv(std::integral_constant<int, (WN == 1 ? NT / 16 : NI)>{}, p.w2, mhi, mlo, 8 - h2, 1);
+    // ---- c2: output column tl reads the intermediate rows tl .. tl + 2 h2; the columns >= nt of its last tile read into the slack ----
+    conv(std::integral_constant<int, NJ2>{}, p.w2, mhi, mlo, 1);
     __syncthreads();                                  // every wave is done reading the intermediate: its space becomes the output tile
     float* otile = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -366,9 +372,9 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
         f4 bv = {0.f, 0.f, 0.f, 0.f};
         if (p.b2) bv = *reinterpret_cast<const f4*>(p.b2 + ml);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            if (wn * NI + j < NT / 16) {
-                const int tl = (wn * NI + j) * 16 + lr;
+        for (int j = 0; j < NJ2; ++j) {
+            const int tl = (wn * NI + j) * 16 + lr;
+            if (tl < nt) {                            // the output tile holds nt rows
                 f4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accc[i][j][e] * HGS_LO_INV + bv[e];
@@ -378,14 +384,14 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
     }
     __syncthreads();
     constexpr int CPR = C / 4, EU = 4;
-    for (int e0 = tid; e0 < NT * CPR; e0 += 512 * EU) {
+    for (int e0 = tid; e0 < nt * CPR; e0 += 512 * EU) {
         f4 r4[EU], a4[EU];
         bool live[EU];
 #pragma unroll
         for (int u = 0; u < EU; ++u) {
             const int e = e0 + u * 512;
             const int tl = e / CPR, ch = e - tl * CPR;
-            live[u] = e < NT * CPR && t0 + tl < p.T;
+            live[u] = e < nt * CPR && t0 + tl < p.T;
             const size_t o = ((size_t)b * p.T + t0 + tl) * C + ch * 4;
             r4[u] = (f4){0.f, 0.f, 0.f, 0.f}; a4[u] = (f4){0.f, 0.f, 0.f, 0.f};
             if (live[u]) r4[u] = *reinterpret_cast<const f4*>(p.x + o);              // the unit's residual is its own input
@@ -406,26 +412,67 @@ __global__ __launch_bounds__(512, ((C == 32 || C == 128) ? 4 : 2)) void hifigan_
     }
 }
 
-static size_t hgs_unit_lds(int C, int NT, int h1)
+static size_t hgs_unit_lds(int C, int NTI, int NT, int h1)
 {
-    const size_t xin = (size_t)(NT + 16 + 2 * h1) * C * 4, mid = (size_t)(NT + 32) * C * 4, ot = (size_t)NT * (C + 4) * 4;
+    const size_t xin = (size_t)(NTI + 2 * h1) * C * 4, mid = (size_t)(NTI + 16) * C * 4, ot = (size_t)NT * (C + 4) * 4;
     const size_t m = xin > mid ? xin : mid;
     return ((m > ot ? m : ot) + 255) / 256 * 256;
 }
 
-template <int C, int NT, int WM, int WN>
-static int hgs_unit_launch(const HgsUnitParams& p, hipStream_t st)
+// The time tile of a unit: nti intermediate columns (a compiled instance), nt stored ones, trim = c2 leaves its last 16-column tile out.
+// c1 costs nti / 16 column-tile steps per wave row.  c2 costs nti / 16 too, except where one wave column spans the tile (C >= 128):
+// there nt = nti - 16 saves c2 a step.  So each instance offers nt = nti - 2 h2 (all it can store) and, at C >= 128, nt = nti - 16; the
+// choice is the fewest (c1 + c2) steps per stored column among the tiles whose LDS keeps the stage's residency — the 80 KB that two
+// workgroups per CU leave each at C = 128 and C = 32; C = 256 and C = 64 have one instance, whose x and intermediate images no nt changes —
+// and among all that fit the 160 KB when none does.  Ties go to the wider instance.
+// V1: C = 256 stores 62 / 58 / 48 columns at k = 3 / 7 / 11; C = 128 stores 126 / 122 / 112 (80 at k = 11, dilation 5: the 96-column
+// instance); C = 64 and C = 32 store 256 - 2 h2 and 512 - 2 h2.
+struct HgsUnitTile { int nti, nt; bool trim; size_t lds; };
+
+static HgsUnitTile hgs_unit_tile(int C, int ntaps, int dil)
 {
-    const int h1 = p.dil * (p.ntaps - 1) / 2;
-    const size_t lds = hgs_unit_lds(C, NT, h1);
-    if (lds > 160 * 1024) { set_error("hifigan_resunit_f32: tiles need %zu bytes of LDS", lds); return DSP_EINVAL; }
-    auto k = hifigan_resunit_f32_kernel<C, NT, WM, WN>;
-    set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((p.T + NT - 1) / NT, 1, p.B), dim3(512), lds, st, p);
+    static const int i256[] = {64}, i128[] = {128, 112, 96}, i64[] = {256}, i32[] = {512};
+    const int* inst = C == 256 ? i256 : C == 128 ? i128 : C == 64 ? i64 : i32;
+    const int n_inst = C == 128 ? 3 : 1;
+    const bool one_wave_column = C >= 128;
+    const int h1 = dil * (ntaps - 1) / 2, h2 = (ntaps - 1) / 2;
+    const size_t resident = (C == 128 || C == 32) ? 80 * 1024 : 160 * 1024;
+    HgsUnitTile best = {0, 0, false, 0};
+    int best_steps = 0;
+    for (int pass = 0; pass < 2 && !best.nt; ++pass) {
+        const size_t budget = pass == 0 ? resident : 160 * 1024;
+        for (int i = 0; i < n_inst; ++i) {
+            const int nti = inst[i];
+            for (int trim = 0; trim <= (one_wave_column ? 1 : 0); ++trim) {
+                const int nt = trim ? nti - 16 : nti - 2 * h2;
+                const int steps = 2 * (nti / 16) - trim;
+                if (nt < 1 || nt + 2 * h2 > nti) continue;
+                const size_t lds = hgs_unit_lds(C, nti, nt, h1);
+                if (lds > budget) continue;
+                if (!best.nt || (long)steps * best.nt < (long)best_steps * nt) { best = {nti, nt, trim != 0, lds}; best_steps = steps; }
+            }
+        }
+    }
+    return best;                                      // nt == 0: no instance fits the LDS
+}
+
+template <int C, int NTI, int WM, int WN, bool TRIM>
+static int hgs_unit_launch(HgsUnitParams p, const HgsUnitTile& tile, hipStream_t st)
+{
+    if (tile.nti != NTI || tile.trim != TRIM || tile.nt < 1 || tile.nt + 2 * ((p.ntaps - 1) / 2) > NTI || tile.lds > 160 * 1024) {
+        set_error("hifigan_resunit_f32: tile %d / %d does not fit the instance", tile.nt, tile.nti); return DSP_EINVAL; }
+    p.nt = tile.nt;
+    auto k = hifigan_resunit_f32_kernel<C, NTI, WM, WN, TRIM>;
+    set_max_dynamic_lds((const void*)k, (int)tile.lds);
+    hipLaunchKernelGGL(k, dim3((p.T + tile.nt - 1) / tile.nt, 1, p.B), dim3(512), tile.lds, st, p);
     return check_launch("hifigan_resunit_f32");
 }
 
-static int hgs_unit_nt(int C) { return C == 32 ? 496 : C == 64 ? 240 : C == 128 ? 112 : 48; }
+template <int C, int NTI, int WM, int WN>
+static int hgs_unit_launch_trim(const HgsUnitParams& p, const HgsUnitTile& tile, hipStream_t st)
+{
+    return tile.trim ? hgs_unit_launch<C, NTI, WM, WN, true>(p, tile, st) : hgs_unit_launch<C, NTI, WM, WN, false>(p, tile, st);
+}
 
 // fp32 tap-major [ntaps][M][CI] -> (hi, lo * 2048) in the fragment order of hifigan_conv.hip's hg_pack_weights_kernel
 __global__ void hgs_pack_weights_kernel(const float* __restrict__ w, _Float16* __restrict__ oh, _Float16* __restrict__ ol, int ntaps, int M, int CI)
@@ -540,26 +587,28 @@ extern "C" int dsp_hifigan_conv_chain_f32(const dsp_hg_layer* layers, int n_laye
             if (!dsp_hifigan_resunit_f32_supported(l.CI, l.ntaps, dil) || l.M != l.CI) { set_error("hifigan_conv_chain_f32: layer %d is not a supported fused unit", i); return DSP_EINVAL; }
             HgsUnitParams u;
             u.x = (const float*)l.x; u.w1 = (const _Float16*)l.w; u.b1 = l.bias; u.w2 = (const _Float16*)l.w2; u.b2 = l.bias2; u.out = (float*)l.out;
-            u.B = B; u.T = l.T; u.ntaps = l.ntaps; u.dil = dil; u.accumulate = l.out_mode == DSP_HG_OUT_ACCUM; u.slope = l.pre_slope; u.scale = l.scale;
+            u.B = B; u.T = l.T; u.nt = 0; u.ntaps = l.ntaps; u.dil = dil; u.accumulate = l.out_mode == DSP_HG_OUT_ACCUM; u.slope = l.pre_slope; u.scale = l.scale;
             u.lens = lens; u.len_mul = mul;
             if (!u.x || !u.out || u.x == u.out) { set_error("hifigan_conv_chain_f32: null or aliased pointer in unit %d", i); return DSP_EINVAL; }
-            int rc;
-            // (tile sweep of r03, ms per 32 x 329-frame call and stage — C=256: NT 32 / 48 / 64 = 5.30 / 4.69 / 5.04; C=128 as 8x1 waves: NT 64 / 80 / 96 /
-            //  112 = 9.34 / 8.82 / 8.93 / 8.71, as 4x2 waves at 132 VGPRs and one workgroup per CU 9.8; C=64: <240,2,4> 4.40, <240,4,2> 4.63,
-            //  <176,4,2> 4.87, <112,4,2> 5.38; C=32: <496,1,8> 2.88, <496,2,4> 3.02, <240,2,4> 3.04, <240,1,8> 3.43;
-            //  r04: C=128 as 4x2 waves under the 128-VGPR bound, two workgroups per CU: 24.9 vs 21.2 ms per call — profiles/r04_vocoder_ablation.txt)
+            // The tile: hgs_unit_tile.  (Sweep of r03 with tap-blind tiles nt = nti - 16, ms per 32 x 329-frame call and stage — C=256: nt 32 / 48 / 64
+            //  = 5.30 / 4.69 / 5.04; C=128 as 8x1 waves: nt 64 / 80 / 96 / 112 = 9.34 / 8.82 / 8.93 / 8.71, as 4x2 waves at 132 VGPRs and one
+            //  workgroup per CU 9.8; C=64: <240,2,4> 4.40, <240,4,2> 4.63, <176,4,2> 4.87, <112,4,2> 5.38; C=32: <496,1,8> 2.88, <496,2,4> 3.02,
+            //  <240,2,4> 3.04, <240,1,8> 3.43; r04: C=128 as 4x2 waves under the 128-VGPR bound, two workgroups per CU: 24.9 vs 21.2 ms per call
+            //  — profiles/r04_vocoder_ablation.txt; C=256 with 32-column tiles for the wide-halo units, to fit two per CU: 21.9 vs 21.2 ms per call.
+            //  The instances below are the winners' intermediate widths, nti = nt + 16; tap-aware nt on them: profiles/r07_tap_tiles.txt)
+            const HgsUnitTile tile = hgs_unit_tile(l.CI, l.ntaps, dil);
+            hipStream_t st = as_stream(stream);
+            int rc = DSP_EINVAL;
             switch (l.CI) {
-                case 256: rc = hgs_unit_launch<256, 48, 8, 1>(u, as_stream(stream)); break;      // (32-column tiles for the wide-halo units, to fit two per CU: slower, 21.9 vs 21.2 ms per call)
-                case 128: {
-                    // two workgroups per CU need <= 80 KB each: the wide-halo units (k = 7 / 11 at dilation 3 / 5) take narrower tiles for it
-                    const int h1u = dil * (l.ntaps - 1) / 2;
-                    if (hgs_unit_lds(128, 112, h1u) <= 80 * 1024) rc = hgs_unit_launch<128, 112, 8, 1>(u, as_stream(stream));
-                    else if (hgs_unit_lds(128, 96, h1u) <= 80 * 1024) rc = hgs_unit_launch<128, 96, 8, 1>(u, as_stream(stream));
-                    else rc = hgs_unit_launch<128, 80, 8, 1>(u, as_stream(stream));
+                case 256: rc = hgs_unit_launch_trim<256, 64, 8, 1>(u, tile, st); break;
+                case 128:
+                    // two workgroups per CU need <= 80 KB each: the wide-halo units (k = 11 at dilation 4 / 5) take narrower instances for it
+                    if (tile.nti == 128) rc = hgs_unit_launch_trim<128, 128, 8, 1>(u, tile, st);
+                    else if (tile.nti == 112) rc = hgs_unit_launch_trim<128, 112, 8, 1>(u, tile, st);
+                    else rc = hgs_unit_launch_trim<128, 96, 8, 1>(u, tile, st);
                     break;
-                }
-                case 64:  rc = hgs_unit_launch<64, 240, 2, 4>(u, as_stream(stream)); break;
-                default:  rc = hgs_unit_launch<32, 496, 1, 8>(u, as_stream(stream)); break;
+                case 64:  rc = hgs_unit_launch<64, 256, 2, 4, false>(u, tile, st); break;
+                default:  rc = hgs_unit_launch<32, 512, 1, 8, false>(u, tile, st); break;
             }
             if (rc) return rc;
             continue;
@@ -573,7 +622,7 @@ extern "C" int dsp_hifigan_conv_chain_f32(const dsp_hg_layer* layers, int n_laye
 extern "C" int dsp_hifigan_resunit_f32_supported(int C, int ntaps, int dil)
 {
     if (!(C == 32 || C == 64 || C == 128 || C == 256) || ntaps < 1 || !(ntaps & 1) || ntaps > DSP_HG_MAX_TAPS || dil < 1) return 0;
-    return hgs_unit_lds(C, hgs_unit_nt(C), dil * (ntaps - 1) / 2) <= 160 * 1024;
+    return hgs_unit_tile(C, ntaps, dil).nt > 0;
 }
 
 extern "C" int dsp_hifigan_pack_weights_f32(const float* w, void* w_hi_lo, int ntaps, int M, int CI, dsp_stream_t stream)
