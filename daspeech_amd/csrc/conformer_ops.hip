@@ -96,7 +96,8 @@ extern "C" int dsp_dwconv_bn_silu(const float* x, const float* w, const float* b
 // ---- LayerNorm over the last dimension, one wave per row -----------------------------------------------------------------------
 // torch's kernel takes 19.5 us for 12800 rows x 256 (13 MB in, 13 MB out: 5 us of HBM time) and the inference pipelines call it ~100
 // times per batch.  Here a wave holds its row in registers (C/64 values per lane, 16-byte loads), mean and the variance of the
-// centred values are two wave reductions, four rows per workgroup.  Same definition as torch (biased variance, eps inside the sqrt).
+// centred values are wave reductions (the mean in two steps: sum, then the sum of what is left), four rows per workgroup.  Same definition
+// as torch (biased variance, eps inside the sqrt).
 namespace dsp {
 
 template <int NV>      // float4 per lane: C <= 256 * NV
@@ -118,13 +119,27 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     const float mean = s / (float)C;
+    // the fp32 sum of a row whose mean dwarfs its spread (mean 100, spread 0.01) rounds `mean` by about the spread itself.  The centred values
+    // are exact there, so their own mean is the rounding that was lost: one more wave reduction, and v holds x - mean from here on
+    float e = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int c = (k * 64 + lane) * 4;
+        if (c < C) {
+            v[k].x -= mean; v[k].y -= mean; v[k].z -= mean; v[k].w -= mean;
+            e += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+    const float corr = e / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int c = (k * 64 + lane) * 4;
         if (c < C) {
-            const float dx = v[k].x - mean, dy = v[k].y - mean, dz = v[k].z - mean, dw = v[k].w - mean;
-            q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+            v[k].x -= corr; v[k].y -= corr; v[k].z -= corr; v[k].w -= corr;
+            q += (v[k].x * v[k].x + v[k].y * v[k].y) + (v[k].z * v[k].z + v[k].w * v[k].w);
         }
     }
 #pragma unroll
@@ -137,8 +152,8 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict
             float4 g = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
             if (w) g = *reinterpret_cast<const float4*>(w + c);
             if (b) be = *reinterpret_cast<const float4*>(b + c);
-            *reinterpret_cast<float4*>(Y + c) = make_float4((v[k].x - mean) * rstd * g.x + be.x, (v[k].y - mean) * rstd * g.y + be.y,
-                                                            (v[k].z - mean) * rstd * g.z + be.z, (v[k].w - mean) * rstd * g.w + be.w);
+            *reinterpret_cast<float4*>(Y + c) = make_float4(v[k].x * rstd * g.x + be.x, v[k].y * rstd * g.y + be.y,
+                                                            v[k].z * rstd * g.z + be.z, v[k].w * rstd * g.w + be.w);
         }
     }
 }

@@ -183,8 +183,9 @@ __global__ __launch_bounds__(256) void posterior_kernel(const float* __restrict_
         __syncthreads();
         s = red[0];
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-        const float lse = m + __logf(s);
-        for (int j = threadIdx.x; j < L; j += blockDim.x) o[j] = __expf(a[j] + b[j] - lse);
+        // exp(x - m) / s, not exp(x - (m + log s)): at |alpha + beta| ~ 1e3 the rounding of m + log s alone is 6e-5 of every entry
+        const float inv = 1.f / s;
+        for (int j = threadIdx.x; j < L; j += blockDim.x) o[j] = __expf(a[j] + b[j] - m) * inv;
     }
 }
 
@@ -209,14 +210,15 @@ __global__ __launch_bounds__(256) void posterior_features_kernel(const float* __
         float m = NEG_INF;
         for (int j = lane; j < L; j += 64) m = fmaxf(m, a[j] + bb[j]);
         m = wave_max(m);
-        float lse = NEG_INF;
+        float lse = NEG_INF, inv = 0.f;
         if (m > NEG_INF && !isinf(m)) {
             float sum = 0.f;
             for (int j = lane; j < L; j += 64) sum += __expf(a[j] + bb[j] - m);
             sum = wave_sum(sum);
             lse = m + __logf(sum);
+            inv = 1.f / sum;                               // exp(x - m) / sum: free of the rounding of m + log(sum), see posterior_kernel
         }
-        for (int j = lane; j < L; j += 64) pr[j] = (lse == NEG_INF) ? 0.f : __expf(a[j] + bb[j] - lse);
+        for (int j = lane; j < L; j += 64) pr[j] = (lse == NEG_INF) ? 0.f : __expf(a[j] + bb[j] - m) * inv;
         if (lane == 0 && lse_out) lse_out[(size_t)b * T + t] = lse;
     }
     __syncthreads();
