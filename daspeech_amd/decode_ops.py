@@ -11,6 +11,8 @@ Host-side mirror of the reference code these replace:
                       dtype of alpha, so the double DAG chain of custom_ops/dag_double.py continues through this step; every other
                       dtype takes the fp32 kernels, as before)
   predicted_durations / bucketize_embed_add / length_regulate   fairseq/fairseq/models/text_to_speech/fastspeech2.py:98-114,169-210
+  bucketize_embed_add_autograd / length_regulate_autograd   the same two steps under autograd (csrc/tts_glue_grad.hip): fp32 / fp16 / bf16,
+                      backward kernels that add rows in a fixed order without float atomics (bit-reproducible gradients)
 No CPU fallback: GPU tensors only.
 """
 import ctypes
@@ -422,10 +424,8 @@ def bucketize_embed_add(x: Tensor, values: Tensor, bins: Tensor, emb_weight: Ten
     return out.to(x.dtype)
 
 
-def length_regulate(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tensor]:
-    """LengthRegulator.forward (fastspeech2.py:98-114): rows of x [B,N,C] repeated durations[b,t] times, zero padded to the
-    batch maximum; returns (out [B,max,C], out_lens [B] int64).  One sync for the output shape (the reference: B*N)."""
-    _gpu("length_regulate", x, durations)
+def _length_regulate(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """the two launches of the length regulator -> (out [B,max,C], out_lens [B], cum [B,N] inclusive prefix sums of the durations)"""
     xx = x.detach().contiguous()
     dur = durations.to(torch.long).contiguous()
     B, N, C = xx.shape
@@ -441,7 +441,115 @@ def length_regulate(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tensor]:
         if maxlen:
             _lib.check(lib.dsp_length_regulator_expand(_lib.ptr(xx), _code(xx), _lib.ptr(cum), _lib.ptr(out), B, N, C, maxlen,
                                                        _lib.current_stream_handle()), "dsp_length_regulator_expand")
-    return out, lens
+    return out, lens, cum
+
+
+def length_regulate(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tensor]:
+    """LengthRegulator.forward (fastspeech2.py:98-114): rows of x [B,N,C] repeated durations[b,t] times, zero padded to the
+    batch maximum; returns (out [B,max,C], out_lens [B] int64).  One sync for the output shape (the reference: B*N)."""
+    _gpu("length_regulate", x, durations)
+    return _length_regulate(x, durations)[:2]
+
+
+EMBED_GRAD_CHUNK = 64        # DSP_EMBED_GRAD_CHUNK: rows of one bucket that one wave sums in dsp_embed_grad
+
+
+class _BucketizeEmbedAddFn(torch.autograd.Function):
+    """x + emb_weight[bucketize(values, bins)] in the dtype of x (dsp_bucketize_embed_add_fwd keeps the bucket indices); the gradient of x is
+    the incoming gradient itself, the gradient of the table is dsp_embed_grad: per bucket, its rows in ascending order, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, values, bins, emb_weight):
+        xx = x.detach().contiguous()
+        v = values.detach().to(torch.float32).contiguous()
+        bn = bins.detach().to(torch.float32).contiguous()
+        em = emb_weight.detach().contiguous()
+        C = xx.shape[-1]
+        n = v.numel()
+        dev = xx.device
+        with torch.cuda.device(dev):
+            out = torch.empty_like(xx)
+            idx = torch.empty((n,), dtype=torch.int32, device=dev)
+            if n:
+                _lib.check(_lib.load().dsp_bucketize_embed_add_fwd(_lib.ptr(xx), _code(xx), _lib.ptr(v), _lib.ptr(bn), bn.numel(), _lib.ptr(em),
+                                                                   _lib.ptr(out), _lib.ptr(idx), n, C, _lib.current_stream_handle()),
+                           "dsp_bucketize_embed_add_fwd")
+        ctx.save_for_backward(idx)
+        ctx.rows, ctx.C = em.shape[0], C
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        idx, = ctx.saved_tensors
+        grad_emb = None
+        if ctx.needs_input_grad[3]:
+            n, K, C = idx.numel(), ctx.rows, ctx.C
+            dev = grad_out.device
+            if n == 0:
+                grad_emb = torch.zeros((K, C), dtype=grad_out.dtype, device=dev)
+            else:
+                g = grad_out.contiguous()
+                lib = _lib.load()
+                with torch.cuda.device(dev):
+                    grad_emb = torch.empty((K, C), dtype=g.dtype, device=dev)
+                    nbytes = int(lib.dsp_embed_grad_workspace_bytes(n, K - 1, C))
+                    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                    _lib.check(lib.dsp_embed_grad(_lib.ptr(g), _code(g), _lib.ptr(idx), _lib.ptr(grad_emb), n, K - 1, C, _lib.ptr(ws), nbytes,
+                                                  _lib.current_stream_handle()), "dsp_embed_grad")
+        return (grad_out if ctx.needs_input_grad[0] else None), None, None, grad_emb
+
+
+def bucketize_embed_add_autograd(x: Tensor, values: Tensor, bins: Tensor, emb_weight: Tensor) -> Tensor:
+    """x [...,C] + Embedding(bucketize(values [...], bins)) in the dtype of x, differentiable w.r.t. x and emb_weight [len(bins)+1, C]
+    (fastspeech2.py:169-177,207-210).  x and emb_weight share one dtype: fp32, fp16 or bf16 (float64 is refused, never narrowed — the
+    caller keeps torch ops for it).  The backward is bit-reproducible: see _BucketizeEmbedAddFn."""
+    if x.dtype != emb_weight.dtype or str(x.dtype) not in _lib.DTYPE_CODES:
+        raise RuntimeError(f"bucketize_embed_add_autograd: x and emb_weight must share one of fp32 / fp16 / bf16, got {x.dtype} and {emb_weight.dtype}")
+    _gpu("bucketize_embed_add_autograd", x, values, bins, emb_weight)
+    if (x.dim() < 1 or emb_weight.dim() != 2 or emb_weight.shape[1] != x.shape[-1] or emb_weight.shape[0] != bins.numel() + 1
+            or values.numel() * x.shape[-1] != x.numel()):
+        raise RuntimeError(f"bucketize_embed_add_autograd: shapes x {tuple(x.shape)}, values {tuple(values.shape)}, bins {tuple(bins.shape)}, "
+                           f"emb_weight {tuple(emb_weight.shape)} do not fit")
+    return _BucketizeEmbedAddFn.apply(x, values, bins, emb_weight)
+
+
+class _LengthRegulateFn(torch.autograd.Function):
+    """length_regulate with a backward: grad_x[b,t] = the sum of the gradient frames of phoneme t in ascending order
+    (dsp_length_regulator_bwd on the saved prefix sums; padding frames of grad_out are never read)."""
+
+    @staticmethod
+    def forward(ctx, x, durations):
+        out, lens, cum = _length_regulate(x, durations)
+        ctx.save_for_backward(cum)
+        ctx.dims = tuple(x.shape) + (out.shape[1],)
+        ctx.mark_non_differentiable(lens)
+        return out, lens
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_lens):
+        cum, = ctx.saved_tensors
+        B, N, C, maxlen = ctx.dims
+        dev = grad_out.device
+        if B * N == 0 or maxlen == 0:
+            return torch.zeros((B, N, C), dtype=grad_out.dtype, device=dev), None
+        g = grad_out.contiguous()
+        with torch.cuda.device(dev):
+            gx = torch.empty((B, N, C), dtype=g.dtype, device=dev)
+            _lib.check(_lib.load().dsp_length_regulator_bwd(_lib.ptr(g), _code(g), _lib.ptr(cum), _lib.ptr(gx), B, N, C, maxlen,
+                                                            _lib.current_stream_handle()), "dsp_length_regulator_bwd")
+        return gx, None
+
+
+def length_regulate_autograd(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tensor]:
+    """length_regulate, differentiable w.r.t. x [B,N,C] (fp32 / fp16 / bf16; float64 is refused, never narrowed): the two forward launches
+    of length_regulate, and dsp_length_regulator_bwd as the backward.  out_lens [B] int64 carries no gradient."""
+    _gpu("length_regulate_autograd", x, durations)
+    if x.dim() != 3 or durations.shape != x.shape[:2]:
+        raise RuntimeError(f"length_regulate_autograd: x {tuple(x.shape)} must be [B,N,C] and durations {tuple(durations.shape)} [B,N]")
+    _code(x)
+    return _LengthRegulateFn.apply(x, durations)
 
 
 def restore_valid_links(links: Tensor) -> Tensor:

@@ -158,9 +158,13 @@ class VariancePredictor(nn.Module):
 
 
 class VarianceAdaptor(nn.Module):
-    """fastspeech2.py:154-216.  Without gradient (inference, predicted or supplied durations / pitch / energy) the glue runs on the
-    HIP ops; with gradient enabled (training) it runs on differentiable torch ops so that the mel loss reaches the encoder FFT
-    layers, the adaptor and both embedding tables as in the reference."""
+    """fastspeech2.py:154-216.  The glue (bucketize + embedding add twice, length regulator) runs on the HIP ops in inference and in
+    training.  Without gradient (predicted or supplied durations / pitch / energy): the forward-only ops.  With gradient enabled on a GPU
+    tensor in fp32 / fp16 / bf16 whose dtype is that of both embedding tables: decode_ops.bucketize_embed_add_autograd and
+    length_regulate_autograd, so that the mel loss reaches the encoder FFT layers, the adaptor and both embedding tables as in the
+    reference — through backward kernels that add rows in a fixed order without float atomics (bit-reproducible gradients).  The forward
+    values are the bits of the torch formulation.  CPU tensors, float64, and an input whose dtype differs from the tables' (an fp32 model
+    under autocast) keep the differentiable torch formulation, `_forward_torch`."""
 
     def __init__(self, dim: int, hidden: int, kernel: int, n_bins: int, pitch_min: float, pitch_max: float,
                  energy_min: float, energy_max: float, dropout: float = 0.0):
@@ -173,6 +177,41 @@ class VarianceAdaptor(nn.Module):
         self.embed_pitch = nn.Embedding(n_bins, dim)
         self.embed_energy = nn.Embedding(n_bins, dim)
 
+    def _hip_autograd_serves(self, x: Tensor) -> bool:
+        return (x.is_cuda and x.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                and x.dtype == self.embed_pitch.weight.dtype == self.embed_energy.weight.dtype)
+
+    def _forward_torch(self, x: Tensor, padding_mask: Tensor, log_dur_out: Tensor, pv: Tensor, durations: Optional[Tensor],
+                       energies: Optional[Tensor], d_factor: float, e_factor: float):
+        """the glue on differentiable torch ops -> (x [B,F,C], out_lens [B], energy_out [B,N]); any device, any floating dtype"""
+        B, N, C = x.shape
+        x = x + F.embedding(torch.bucketize(pv.detach(), self.pitch_bins), self.embed_pitch.weight)
+        energy_out = self.energy_predictor(x)
+        ev = energy_out * e_factor if energies is None else energies
+        x = x + F.embedding(torch.bucketize(ev.detach(), self.energy_bins), self.embed_energy.weight)
+        if durations is None:
+            durations = torch.clamp(torch.round((torch.exp(log_dur_out.detach()) - 1) * d_factor).long(), min=0).masked_fill(padding_mask, 0)
+        out_lens = durations.sum(1)
+        maxlen = int(out_lens.max()) if B else 0
+        # length regulator as one gather: frame f of sample b comes from phoneme searchsorted(cumsum(dur), f, right)
+        cum = durations.cumsum(1)
+        frames = torch.arange(maxlen, device=x.device).unsqueeze(0).expand(B, -1)
+        src = torch.searchsorted(cum, frames.contiguous(), right=True).clamp(max=max(N - 1, 0))
+        x = x.gather(1, src.unsqueeze(-1).expand(-1, -1, C)) * (frames < out_lens.unsqueeze(1)).unsqueeze(-1).to(x.dtype)
+        return x, out_lens, energy_out
+
+    def _forward_hip(self, x: Tensor, padding_mask: Tensor, log_dur_out: Tensor, pv: Tensor, durations: Optional[Tensor],
+                     energies: Optional[Tensor], d_factor: float, e_factor: float):
+        """the same function on the differentiable HIP glue ops (GPU; fp32 / fp16 / bf16 in the dtype of both tables)"""
+        x = decode_ops.bucketize_embed_add_autograd(x, pv.detach(), self.pitch_bins, self.embed_pitch.weight)
+        energy_out = self.energy_predictor(x)
+        ev = energy_out * e_factor if energies is None else energies
+        x = decode_ops.bucketize_embed_add_autograd(x, ev.detach(), self.energy_bins, self.embed_energy.weight)
+        if durations is None:
+            durations = torch.clamp(torch.round((torch.exp(log_dur_out.detach()) - 1) * d_factor).long(), min=0).masked_fill(padding_mask, 0)
+        x, out_lens = decode_ops.length_regulate_autograd(x, durations)
+        return x, out_lens, energy_out
+
     def forward(self, x: Tensor, padding_mask: Tensor, durations: Optional[Tensor] = None, pitches: Optional[Tensor] = None,
                 energies: Optional[Tensor] = None, d_factor: float = 1.0, p_factor: float = 1.0, e_factor: float = 1.0):
         B, N, C = x.shape
@@ -181,21 +220,9 @@ class VarianceAdaptor(nn.Module):
         pv = pitch_out * p_factor if pitches is None else pitches
         if torch.is_grad_enabled() or not x.is_cuda:
             # training (teacher durations / pitch / energy, gradients into x and both embedding tables — the reference's
-            # `x + embed(bucketize(v))` and LengthRegulator are differentiable, fastspeech2.py:98-114,169-214) or CPU tensors:
-            # plain torch ops.  The HIP glue kernels below are forward-only.
-            x = x + F.embedding(torch.bucketize(pv.detach(), self.pitch_bins), self.embed_pitch.weight)
-            energy_out = self.energy_predictor(x)
-            ev = energy_out * e_factor if energies is None else energies
-            x = x + F.embedding(torch.bucketize(ev.detach(), self.energy_bins), self.embed_energy.weight)
-            if durations is None:
-                durations = torch.clamp(torch.round((torch.exp(log_dur_out.detach()) - 1) * d_factor).long(), min=0).masked_fill(padding_mask, 0)
-            out_lens = durations.sum(1)
-            maxlen = int(out_lens.max()) if B else 0
-            # length regulator as one gather: frame f of sample b comes from phoneme searchsorted(cumsum(dur), f, right)
-            cum = durations.cumsum(1)
-            frames = torch.arange(maxlen, device=x.device).unsqueeze(0).expand(B, -1)
-            src = torch.searchsorted(cum, frames.contiguous(), right=True).clamp(max=max(N - 1, 0))
-            x = x.gather(1, src.unsqueeze(-1).expand(-1, -1, C)) * (frames < out_lens.unsqueeze(1)).unsqueeze(-1).to(x.dtype)
+            # `x + embed(bucketize(v))` and LengthRegulator are differentiable, fastspeech2.py:98-114,169-214) or CPU tensors
+            glue = self._forward_hip if self._hip_autograd_serves(x) else self._forward_torch
+            x, out_lens, energy_out = glue(x, padding_mask, log_dur_out, pv, durations, energies, d_factor, e_factor)
         else:
             dur_out = decode_ops.predicted_durations(log_dur_out, padding_mask, d_factor)                     # :202-205
             x = decode_ops.bucketize_embed_add(x.reshape(B * N, C), pv.reshape(-1), self.pitch_bins, self.embed_pitch.weight).view(B, N, C)

@@ -164,6 +164,34 @@ int dsp_length_regulator_lens(const int64_t* dur, int64_t* cum, int64_t* out_len
 int dsp_length_regulator_expand(const void* x, int dtype, const int64_t* cum, void* out, int B, int N, int C, int maxlen,
                                 dsp_stream_t stream);
 
+/* F6b', F7'  the variance-adaptor glue under autograd (csrc/tts_glue_grad.hip).  x / emb / out / grad tensors share one dtype code (DSP_F32 /
+ *   DSP_F16 / DSP_BF16); every sum is accumulated in fp32 and rounded once to that dtype; every output element is written.  Both gradients
+ *   add the rows that share a destination in ASCENDING source order, one wave per destination, without float atomics: the same inputs give
+ *   the same bits on every run, whatever the grid's schedule.
+ *
+ *   dsp_bucketize_embed_add_fwd: out [n,C] = x [n,C] + emb[idx[r]] with idx [n] int32 (an output) = first index with bins[idx] >= v[r]
+ *     (torch.bucketize right=False, the search of dsp_bucketize_embed_add); v [n], bins [nb] fp32 (widened half values compare as torch
+ *     compares them), emb [nb+1,C].  The add is (float)x + (float)e rounded once: the bits of torch's add in that dtype.  Out of place.
+ *
+ *   dsp_embed_grad: grad_emb [nb+1,C] : grad_emb[k,:] = sum over the rows r with idx[r] == k of grad_out [n,C][r,:], rows in ascending r;
+ *     a bucket without a row gets exact zeros; idx values outside [0, nb] select no bucket.  The inverted index is built on the device (a
+ *     count and a stable ballot compaction per bucket, O(n * (nb+1) / 64) wave steps: meant for tables of a few hundred rows); a bucket's
+ *     list is cut into chunks of DSP_EMBED_GRAD_CHUNK rows, each summed by one wave in list order, and the bucket's chunk sums are added
+ *     in chunk order.  workspace: dsp_embed_grad_workspace_bytes(n, nb, C) bytes of device memory, 16-byte aligned (DSP_ENOSPC if smaller).
+ *
+ *   dsp_length_regulator_bwd: grad_x [B,N,C] : grad_x[b,t,:] = sum over f in [cum[b,t-1], cum[b,t]) of grad_out [B,maxlen,C][b,f,:]
+ *     (cum[b,-1] = 0), frames in ascending f; cum [B,N] int64 as dsp_length_regulator_lens wrote it, maxlen as passed to
+ *     dsp_length_regulator_expand.  NEVER READS PADDING FRAMES: frames at or beyond cum[b,N-1] (and beyond maxlen) are not touched, so
+ *     they may hold anything.  A row of zero duration is written as zeros. */
+#define DSP_EMBED_GRAD_CHUNK 64
+int dsp_bucketize_embed_add_fwd(const void* x, int dtype, const float* v, const float* bins, int nb, const void* emb, void* out, int32_t* idx,
+                                int64_t n, int C, dsp_stream_t stream);
+size_t dsp_embed_grad_workspace_bytes(int64_t n, int nb, int C);
+int dsp_embed_grad(const void* grad_out, int dtype, const int32_t* idx, void* grad_emb, int64_t n, int nb, int C,
+                   void* workspace, size_t workspace_bytes, dsp_stream_t stream);
+int dsp_length_regulator_bwd(const void* grad_out, int dtype, const int64_t* cum, void* grad_x, int B, int N, int C, int maxlen,
+                             dsp_stream_t stream);
+
 /* Conformer convolution module, eval mode (fairseq conformer_layer.py ConvolutionModule: depthwise_conv -> batch_norm -> SiLU),
  * on the channels-last tensor:   y[b,t,c] = SiLU( BN_eval( sum_k w[c,k] * x[b,t+k-(K-1)/2,c] ) ),  zero padding outside [0,T).
  *   x, y [B,T,C] fp32 (16-byte aligned, C % 4 == 0, y != x); w [C,K] fp32 (the Conv1d(C,C,K,groups=C) weight [C,1,K]);
