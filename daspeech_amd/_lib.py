@@ -88,6 +88,10 @@ SIGNATURES = {
     "dsp_embed_grad_workspace_bytes": (_c_sz, [_c_i64, _c_int, _c_int]),
     "dsp_embed_grad": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     "dsp_length_regulator_bwd": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_force_emit": (_c_int, [_c_p, _c_int, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_force_emit_bwd": (_c_int, [_c_p, _c_int, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_glance_oracle": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_glance_reveal": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
     # include/daspeech_hifigan.h
     "dsp_conv1d_split_packed_elems": (ctypes.c_long, [_c_int, _c_int, _c_int]),
     "dsp_conv1d_split_pack": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),

@@ -42,7 +42,7 @@ def get_anneal_value(anneal_params, update_num):
 
 
 # ------------------------------------------------------------------------------------------------ glancing (nat_dag_loss.py:202-264)
-GLANCE_STRATEGIES = (None, "number-random", "cmlm")
+GLANCE_STRATEGIES = decode_ops.GLANCE_STRATEGIES
 
 
 def _viterbi_path(model, logits: Tensor, tgt_tokens: Tensor, links: Tensor, output_length: Tensor, target_length: Tensor,
@@ -58,13 +58,7 @@ def _viterbi_path(model, logits: Tensor, tgt_tokens: Tensor, links: Tensor, outp
     return custom_ops.dag_best_alignment(match, links, output_length, target_length)
 
 
-def _top_scored(scores: Tensor, counts: Tensor) -> Tensor:
-    """1.0 where a position's score reaches its row's `counts[b]`-th largest score (nothing for a zero count) — the reference's
-    threshold form (nat_dag_loss.py:236-239): ties with the threshold are all kept, and a count beyond the number of aligned vertices
-    (a sample without a valid alignment: every score is the -100 fill) keeps every position."""
-    thresh = scores.sort(descending=True)[0].gather(-1, (counts - 1).clip(min=0).unsqueeze(-1)).squeeze(-1)
-    thresh = thresh.masked_fill(counts == 0, 100)
-    return (scores >= thresh.unsqueeze(-1)).to(scores.dtype)
+_top_scored = decode_ops._top_scored       # the threshold form of the reveal selection (nat_dag_loss.py:236-239), kept under its name here
 
 
 @torch.no_grad()
@@ -87,32 +81,18 @@ def glat_function(model, word_ins_out: Tensor, tgt_tokens: Tensor, prev_output_t
         raise ValueError(f"glance strategy {glance_strategy!r} (supported: {GLANCE_STRATEGIES})")
     torch_gather = torch_ops if torch_gather is None else torch_gather
     torch_align = torch_ops if torch_align is None else torch_align
-    B, L, _ = links.shape
     T = tgt_tokens.shape[1]
-    dev = tgt_tokens.device
     n_tgt = tgt_tokens.ne(model.pad).sum(1)
     n_out = prev_output_tokens.ne(model.pad).sum(1)
     guess = word_ins_out.argmax(-1)
     path = _viterbi_path(model, word_ins_out, tgt_tokens, links, n_out, n_tgt, torch_gather, torch_align)
-    on_path = path >= 0
-    oracle = tgt_tokens.gather(-1, path.clip(min=0))                       # the token each vertex is aligned to (pad-free on the path)
-    n_right = ((guess == oracle) & on_path).sum(1)
-    # vertex j emits target path[j]: the [B, T, L] emission mask, built through a scratch row for the off-path -1
-    matchmask = torch.zeros(B, T + 1, L, device=dev, dtype=torch.bool).scatter_(1, path.unsqueeze(1) + 1, 1)[:, 1:]
-    if glance_strategy is None:
-        keep_prob = ((n_tgt - n_right) / n_tgt * glat["context_p"]).unsqueeze(-1) * on_path.float()
-    else:
-        scores = torch.randn(oracle.shape, device=dev, dtype=torch.float) if noise is None else noise.to(dev, torch.float).clone()
-        scores.masked_fill_(~on_path, -100)
-        if glance_strategy == "number-random":
-            counts = ((n_tgt - n_right) * glat["context_p"] + 0.5).to(torch.long)
-        else:
-            draw = torch.rand_like(n_tgt, dtype=torch.float) if unif_n is None else unif_n.to(dev, torch.float)
-            counts = (n_tgt * draw + 0.5).to(torch.long)
-        keep_prob = _top_scored(scores, counts)
-    u = torch.rand(prev_output_tokens.shape, device=prev_output_tokens.device) if unif is None else unif.to(prev_output_tokens.device)
-    revealed = u < keep_prob
-    glanced = torch.where(revealed, oracle, prev_output_tokens)
+    # vertex j emits target path[j]: the [B, T, L] emission mask (kept for callers that read glat_info; the criteria force-emit from `path`)
+    matchmask = decode_ops.emission_mask(path, T)
+    # oracle tokens, the count of vertices already right, and which vertices are revealed: two HIP launches on GPU tensors, the torch
+    # formulation on CPU tensors — the same bits either way (decode_ops.glance_select)
+    sel = decode_ops.glance_select(tgt_tokens, path, guess, prev_output_tokens, n_tgt, glat["context_p"], glance_strategy,
+                                   noise=noise, unif=unif, unif_n=unif_n)
+    oracle, n_right, keep_prob, revealed, glanced = sel["oracle"], sel["n_right"], sel["keep_prob"], sel["revealed"], sel["glanced"]
     glat_info = {
         "glat_accu": (n_right.sum() / n_tgt.sum()).detach(),
         "glat_context_p": glat["context_p"],
@@ -168,7 +148,7 @@ class NATDAGLoss:
 
     # ---- nat_dag_loss.py:114-156 / s2s_dag_fastspeech2_loss.py:53-91
     def _dag_loss_core(self, outputs, output_masks, targets, target_masks, links, name, factor, matchmask, keep_word_mask, model,
-                       with_alpha_beta: bool):
+                       with_alpha_beta: bool, path=None):
         prelen = outputs.shape[1]
         output_length = output_masks.sum(dim=-1)
         target_length = target_masks.sum(dim=-1)
@@ -185,9 +165,13 @@ class NATDAGLoss:
                 custom_ops.set_lazy_softmax(prev_mode)
         match_all = match_all.transpose(1, 2)                                                   # [B,T,L]: no copy (fp32: rows pitched to 4; float64: dense)
         if matchmask is not None and not self.cfg.no_force_emit:                                # force-emit (:130-132)
-            glat_prev_mask = keep_word_mask.unsqueeze(1)
-            match_all = match_all.masked_fill(glat_prev_mask, 0) + \
-                match_all.masked_fill(~matchmask, float("-inf")).masked_fill(~glat_prev_mask, 0).detach()
+            if path is not None and decode_ops.force_emit_served(match_all, path, keep_word_mask):
+                # one pass over [B,T,L] from the two [B,L] vectors that determine the mask; the result keeps the gather's row pitch
+                match_all = decode_ops.force_emit(match_all, path, keep_word_mask)
+            else:                                                                               # no `path` (an external matchmask), unserved tensors
+                glat_prev_mask = keep_word_mask.unsqueeze(1)
+                match_all = match_all.masked_fill(glat_prev_mask, 0) + \
+                    match_all.masked_fill(~matchmask, float("-inf")).masked_fill(~glat_prev_mask, 0).detach()
         nvalidtokens = output_masks.sum()
         alpha = beta = None
         if with_alpha_beta:
@@ -211,8 +195,9 @@ class NATDAGLoss:
         return True
 
     def _compute_dag_loss(self, outputs, output_masks, targets, target_masks, links, label_smoothing=0.0, name="loss", factor=1.0,
-                          matchmask=None, keep_word_mask=None, model=None):
-        return self._dag_loss_core(outputs, output_masks, targets, target_masks, links, name, factor, matchmask, keep_word_mask, model, False)[0]
+                          matchmask=None, keep_word_mask=None, model=None, path=None):
+        return self._dag_loss_core(outputs, output_masks, targets, target_masks, links, name, factor, matchmask, keep_word_mask, model, False,
+                                   path=path)[0]
 
     def _glat_args(self):
         if self.glat_p == 0:
@@ -241,7 +226,8 @@ class NATDAGLoss:
         _losses = self._compute_dag_loss(
             outputs["word_ins"].get("out"), prev_output_tokens.ne(self._pad(model)), outputs["word_ins"].get("tgt"),
             outputs["word_ins"].get("mask", None), outputs["links"], name="dag-loss", factor=1,
-            matchmask=outputs.get("matchmask", None), keep_word_mask=outputs.get("keep_word_mask", None), model=model)
+            matchmask=outputs.get("matchmask", None), keep_word_mask=outputs.get("keep_word_mask", None), model=model,
+            path=outputs.get("path", None))
         loss = _losses["loss"]
         sample_size = 1
         logging_output = {
@@ -274,8 +260,9 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
         return not (self.cfg.training_strategy == "argmax" and not self.cfg.argmax_on_logits)
 
     def _compute_dag_loss_with_alpha_beta(self, outputs, output_masks, targets, target_masks, links, label_smoothing=0.0, name="loss",
-                                          factor=1.0, matchmask=None, keep_word_mask=None, model=None):
-        return self._dag_loss_core(outputs, output_masks, targets, target_masks, links, name, factor, matchmask, keep_word_mask, model, True)
+                                          factor=1.0, matchmask=None, keep_word_mask=None, model=None, path=None):
+        return self._dag_loss_core(outputs, output_masks, targets, target_masks, links, name, factor, matchmask, keep_word_mask, model, True,
+                                   path=path)
 
     def forward(self, model, sample, reduce=True):
         src_tokens, src_lengths = sample["net_input"]["src_tokens"], sample["net_input"]["src_lengths"]
@@ -290,7 +277,8 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
         dag_loss, alpha, beta = self._compute_dag_loss_with_alpha_beta(
             outputs["word_ins"].get("out"), prev_output_tokens.ne(self._pad(model)), outputs["word_ins"].get("tgt"),
             outputs["word_ins"].get("mask", None), outputs["links"], name="dag-loss", factor=1,
-            matchmask=outputs.get("matchmask", None), keep_word_mask=outputs.get("keep_word_mask", None), model=model)
+            matchmask=outputs.get("matchmask", None), keep_word_mask=outputs.get("keep_word_mask", None), model=model,
+            path=outputs.get("path", None))
         features = outputs["word_ins"]["features"]                                                           # B x L x D
         if self.cfg.training_strategy == "argmax":
             # z_i = v_{a*_i}, a* = the Viterbi alignment of (y, x)   (:213-251)

@@ -13,7 +13,11 @@ Host-side mirror of the reference code these replace:
   predicted_durations / bucketize_embed_add / length_regulate   fairseq/fairseq/models/text_to_speech/fastspeech2.py:98-114,169-210
   bucketize_embed_add_autograd / length_regulate_autograd   the same two steps under autograd (csrc/tts_glue_grad.hip): fp32 / fp16 / bf16,
                       backward kernels that add rows in a fixed order without float atomics (bit-reproducible gradients)
-No CPU fallback: GPU tensors only.
+  force_emit / glance_select   DASpeech/criterions/nat_dag_loss.py:130-132,223-255 — the glancing step of DAG training (csrc/glance.hip):
+                      force-emit of the revealed vertices in one pass from `path` / `keep_word_mask`, with its gradient, and the reveal
+                      selection by an exact radix select; these two keep their torch formulation for CPU tensors and unserved inputs
+                      (set_glance_hip(False): always), with the same bits
+No CPU fallback elsewhere: GPU tensors only.
 """
 import ctypes
 from typing import Optional, Tuple
@@ -550,6 +554,187 @@ def length_regulate_autograd(x: Tensor, durations: Tensor) -> Tuple[Tensor, Tens
         raise RuntimeError(f"length_regulate_autograd: x {tuple(x.shape)} must be [B,N,C] and durations {tuple(durations.shape)} [B,N]")
     _code(x)
     return _LengthRegulateFn.apply(x, durations)
+
+
+# ------------------------------------------------------------------------------------------------ glancing (csrc/glance.hip)
+GLANCE_HIP = True          # set_glance_hip(False): force_emit / glance_select keep their torch formulations on every input
+GLANCE_MAX_L = 16000       # DSP_GLANCE_MAX_L: the longest graph whose score row dsp_glance_reveal holds in one workgroup's LDS
+GLANCE_STRATEGIES = (None, "number-random", "cmlm")
+_F64_CODE = 3              # DSP_F64: taken by dsp_force_emit / dsp_force_emit_bwd only (DTYPE_CODES keeps no double entry)
+
+
+def set_glance_hip(on: bool) -> bool:
+    """Switch the HIP glancing ops (force_emit, glance_select) on or off; returns the previous setting.  Off: the torch formulations run, on
+    GPU tensors too — the tests and tools/glance_bench.py compare the two in one process."""
+    global GLANCE_HIP
+    old, GLANCE_HIP = GLANCE_HIP, bool(on)
+    return old
+
+
+def emission_mask(path: Tensor, T: int) -> Tensor:
+    """[B,T,L] bool: vertex j emits target path[b,j] (nat_dag_loss.py:225), built through a scratch row for the off-path -1"""
+    B, L = path.shape
+    return torch.zeros(B, T + 1, L, device=path.device, dtype=torch.bool).scatter_(1, path.unsqueeze(1) + 1, 1)[:, 1:]
+
+
+def _force_emit_torch(match_all: Tensor, path: Tensor, revealed: Tensor) -> Tensor:
+    """the criterion's expression (nat_dag_loss.py:130-132) with the emission mask rebuilt from the path"""
+    matchmask = emission_mask(path, match_all.shape[1])
+    glat_prev_mask = revealed.unsqueeze(1)
+    return match_all.masked_fill(glat_prev_mask, 0) + \
+        match_all.masked_fill(~matchmask, float("-inf")).masked_fill(~glat_prev_mask, 0).detach()
+
+
+def force_emit_served(match_all: Tensor, path: Tensor, revealed: Tensor) -> bool:
+    """True when force_emit runs dsp_force_emit on these tensors: the switch is on, GPU tensors of one device, match_all [B,T,L] fp32 or
+    float64 with unit stride along L (any row pitch, any base), path [B,L] int64, revealed [B,L] bool, nothing empty."""
+    if not GLANCE_HIP or match_all.dim() != 3 or match_all.dtype not in (torch.float32, torch.float64):
+        return False
+    B, T, L = match_all.shape
+    if not (match_all.is_cuda and path.device == match_all.device and revealed.device == match_all.device):
+        return False
+    if tuple(path.shape) != (B, L) or tuple(revealed.shape) != (B, L) or path.dtype != torch.long or revealed.dtype != torch.bool:
+        return False
+    return B * T * L > 0 and B < 65536 and match_all.stride(2) == 1
+
+
+class _ForceEmitFn(torch.autograd.Function):
+    """dsp_force_emit / dsp_force_emit_bwd.  fp32: result and gradient are [B,T,L] views of buffers with rows pitched to a multiple of 4 (what
+    the DP ops and the gather's backward take without a copy); float64: dense."""
+
+    @staticmethod
+    def _empty(B, T, L, like):
+        if like.dtype == torch.float32:
+            from .custom_ops.dag_loss import _pitched_empty, _round4
+            return _pitched_empty(B, T, L, like.device), _round4(L)
+        return torch.empty((B, T, L), dtype=like.dtype, device=like.device), L
+
+    @staticmethod
+    def forward(ctx, match_all, path, revealed):
+        m = match_all.detach()
+        B, T, L = m.shape
+        p = path.contiguous()
+        rv = revealed.contiguous()
+        with torch.cuda.device(m.device):
+            out, ldo = _ForceEmitFn._empty(B, T, L, m)
+            _lib.check(_lib.load().dsp_force_emit(_lib.ptr(m), 0 if m.dtype == torch.float32 else _F64_CODE, m.stride(0), m.stride(1), _lib.ptr(p),
+                                                  _lib.ptr(rv.view(torch.uint8)), _lib.ptr(out), ldo, B, T, L, _lib.current_stream_handle()),
+                       "dsp_force_emit")
+        ctx.save_for_backward(rv)
+        ctx.dims = (B, T, L)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        rv, = ctx.saved_tensors
+        B, T, L = ctx.dims
+        g = grad_out.detach()
+        with torch.cuda.device(g.device):
+            gm, ldg = _ForceEmitFn._empty(B, T, L, g)
+            _lib.check(_lib.load().dsp_force_emit_bwd(_lib.ptr(g), 0 if g.dtype == torch.float32 else _F64_CODE, g.stride(0), g.stride(1), g.stride(2),
+                                                      _lib.ptr(rv.view(torch.uint8)), _lib.ptr(gm), ldg, B, T, L, _lib.current_stream_handle()),
+                       "dsp_force_emit_bwd")
+        return gm, None, None
+
+
+def force_emit(match_all: Tensor, path: Tensor, revealed: Tensor) -> Tensor:
+    """Force-emit of the glanced vertices (nat_dag_loss.py:130-132), out of place: a revealed vertex j (revealed [B,L] bool) may emit only the
+    target it is aligned to, out[b,t,j] = match_all[b,t,j] if t == path[b,j] else -inf (path [B,L] int64, -1 = not aligned: a column of -inf);
+    every other vertex keeps its column.  Values are copied.  Differentiable w.r.t. match_all: revealed columns get no gradient.
+    Inputs that force_emit_served accepts take one pass of dsp_force_emit (fp32 result with pitched rows, which dag_loss / dag_best_alignment
+    take without a copy; float64 dense); CPU tensors, fp16 / bf16, other strides and set_glance_hip(False) keep the torch expression."""
+    if force_emit_served(match_all, path, revealed):
+        return _ForceEmitFn.apply(match_all, path, revealed)
+    return _force_emit_torch(match_all, path, revealed)
+
+
+def _top_scored(scores: Tensor, counts: Tensor) -> Tensor:
+    """1.0 where a position's score reaches its row's `counts[b]`-th largest score (nothing for a zero count) — the reference's
+    threshold form (nat_dag_loss.py:236-239): ties with the threshold are all kept, and a count beyond the number of aligned vertices
+    (a sample without a valid alignment: every score is the -100 fill) keeps every position."""
+    thresh = scores.sort(descending=True)[0].gather(-1, (counts - 1).clip(min=0).unsqueeze(-1)).squeeze(-1)
+    thresh = thresh.masked_fill(counts == 0, 100)
+    return (scores >= thresh.unsqueeze(-1)).to(scores.dtype)
+
+
+def _glance_served(tgt_tokens, path, guess, prev_output_tokens, unif) -> bool:
+    if not GLANCE_HIP or not tgt_tokens.is_cuda or tgt_tokens.dim() != 2 or path.dim() != 2:
+        return False
+    B, L = path.shape
+    if not (1 <= L <= GLANCE_MAX_L and B >= 1 and tgt_tokens.shape[1] >= 1):
+        return False
+    for t in (tgt_tokens, path, guess, prev_output_tokens):
+        if t.device != tgt_tokens.device or t.dtype != torch.long:
+            return False
+    if tuple(guess.shape) != (B, L) or tuple(prev_output_tokens.shape) != (B, L) or tgt_tokens.shape[0] != B:
+        return False
+    return unif is None or (unif.dtype == torch.float32 and tuple(unif.shape) == (B, L))
+
+
+@torch.no_grad()
+def glance_select(tgt_tokens: Tensor, path: Tensor, guess: Tensor, prev_output_tokens: Tensor, n_tgt: Tensor, context_p: float,
+                  glance_strategy: Optional[str] = None, noise: Tensor = None, unif: Tensor = None, unif_n: Tensor = None):
+    """The per-vertex work of the glancing (nat_dag_loss.py:223-255) once the alignment is known -> dict(oracle [B,L] int64 the token each vertex
+    is aligned to, n_right [B] int64 aligned vertices already predicted right, keep_prob [B,L] fp32, revealed [B,L] bool, glanced [B,L]
+    int64 = revealed ? oracle : prev_output_tokens).  tgt_tokens [B,T], path [B,L] (-1 off the alignment), guess [B,L] the arg-max tokens,
+    n_tgt [B] target lengths.  glance_strategy / noise / unif / unif_n as criterions.glat_function (draws are taken on the device, in the
+    reference's order, when None).  No gradient.
+    GPU tensors with L <= GLANCE_MAX_L: two launches (dsp_glance_oracle, dsp_glance_reveal — an exact selection of the threshold score instead
+    of a sort); the per-sample float scalars (the counts, the probability of strategy None) stay torch expressions, so their bits are
+    torch's.  CPU tensors, longer graphs, a replayed `unif` that is not fp32 and set_glance_hip(False) keep the torch formulation; both give
+    the same bits."""
+    if glance_strategy not in GLANCE_STRATEGIES:
+        raise ValueError(f"glance strategy {glance_strategy!r} (supported: {GLANCE_STRATEGIES})")
+    dev = tgt_tokens.device
+    u = None if unif is None else unif.to(prev_output_tokens.device)
+    hip = _glance_served(tgt_tokens, path, guess, prev_output_tokens, u)
+    B, L = path.shape
+    on_path = None
+    if hip:
+        lib = _lib.load()
+        tgt, pth, gs, prev = tgt_tokens.contiguous(), path.contiguous(), guess.contiguous(), prev_output_tokens.contiguous()
+        with torch.cuda.device(dev):
+            oracle = torch.empty((B, L), dtype=torch.long, device=dev)
+            n_right = torch.empty((B,), dtype=torch.long, device=dev)
+            _lib.check(lib.dsp_glance_oracle(_lib.ptr(tgt), _lib.ptr(pth), _lib.ptr(gs), _lib.ptr(oracle), _lib.ptr(n_right), B, tgt.shape[1], L,
+                                             _lib.current_stream_handle()), "dsp_glance_oracle")
+    else:
+        on_path = path >= 0
+        oracle = tgt_tokens.gather(-1, path.clip(min=0))                   # the token each vertex is aligned to (pad-free on the path)
+        n_right = ((guess == oracle) & on_path).sum(1)
+    scores = counts = prob = None
+    if glance_strategy is None:
+        prob = (n_tgt - n_right) / n_tgt * context_p
+    else:
+        scores = torch.randn(oracle.shape, device=dev, dtype=torch.float) if noise is None else noise.to(dev, torch.float)
+        if glance_strategy == "number-random":
+            counts = ((n_tgt - n_right) * context_p + 0.5).to(torch.long)
+        else:
+            draw = torch.rand_like(n_tgt, dtype=torch.float) if unif_n is None else unif_n.to(dev, torch.float)
+            counts = (n_tgt * draw + 0.5).to(torch.long)
+    if u is None:
+        u = torch.rand(prev_output_tokens.shape, device=prev_output_tokens.device)
+    if hip and (counts is not None or prob.dtype == torch.float32):
+        param = (prob if counts is None else counts).contiguous()
+        sc = None if scores is None else scores.contiguous()
+        u = u.contiguous()
+        with torch.cuda.device(dev):
+            keep_prob = torch.empty((B, L), dtype=torch.float32, device=dev)
+            revealed = torch.empty((B, L), dtype=torch.bool, device=dev)
+            glanced = torch.empty((B, L), dtype=torch.long, device=dev)
+            _lib.check(lib.dsp_glance_reveal(_lib.ptr(sc), _lib.ptr(param), 0 if counts is None else 1, _lib.ptr(u), _lib.ptr(pth), _lib.ptr(oracle),
+                                             _lib.ptr(prev), _lib.ptr(keep_prob), _lib.ptr(revealed.view(torch.uint8)), _lib.ptr(glanced), B, L,
+                                             _lib.current_stream_handle()), "dsp_glance_reveal")
+    else:
+        on_path = path >= 0 if on_path is None else on_path
+        if counts is None:
+            keep_prob = prob.unsqueeze(-1) * on_path.float()
+        else:
+            keep_prob = _top_scored(scores.clone().masked_fill_(~on_path, -100), counts)
+        revealed = u < keep_prob
+        glanced = torch.where(revealed, oracle, prev_output_tokens)
+    return {"oracle": oracle, "n_right": n_right, "keep_prob": keep_prob, "revealed": revealed, "glanced": glanced}
 
 
 def restore_valid_links(links: Tensor) -> Tensor:

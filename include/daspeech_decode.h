@@ -192,6 +192,46 @@ int dsp_embed_grad(const void* grad_out, int dtype, const int32_t* idx, void* gr
 int dsp_length_regulator_bwd(const void* grad_out, int dtype, const int64_t* cum, void* grad_x, int B, int N, int C, int maxlen,
                              dsp_stream_t stream);
 
+/* G1, G2  the glancing step of DAG training (csrc/glance.hip; DASpeech/criterions/nat_dag_loss.py:130-132 and :223-255).
+ *
+ *   dsp_force_emit: force-emit of the revealed vertices, out of place, one read and one write of [B,T,L]:
+ *       out[b,t,j] = match[b,t,j]                                  where revealed[b,j] == 0
+ *       out[b,t,j] = t == path[b,j] ? match[b,t,j] : -inf          where revealed[b,j] != 0   (path[b,j] = -1: a column of -inf)
+ *     Values are copied, never recomputed.  dtype DSP_F32 or DSP_F64 (a code these two entry points alone take).  match [B,T,L] with unit
+ *     stride along L, `st` elements between rows and `sb` between samples (any values: the gather's pitched view, a dense tensor, a
+ *     misaligned view); path [B,L] int64, revealed [B,L] bytes, both contiguous; out [B,T,L] with row pitch ldo >= L and samples T*ldo
+ *     apart.  16-byte accesses where base and pitches allow them (fp32: base % 16 == 0, st % 4 == 0, sb % 4 == 0), element accesses
+ *     otherwise and for the last L % 4 columns of a row.  Only columns < L are read or written: pitch padding may hold anything and stays
+ *     untouched.
+ *
+ *   dsp_force_emit_bwd: its gradient, grad_match[b,t,j] = revealed[b,j] ? 0 : grad_out[b,t,j].  grad_out [B,T,L] with ANY element strides
+ *     (sb, st, sl >= 0; 0 = a broadcast dimension); grad_match as `out` above (row pitch ldg).
+ *
+ *   dsp_glance_oracle: oracle[b,j] = tgt[b, max(path[b,j], 0)] and n_right[b] = #{ j : path[b,j] >= 0 and guess[b,j] == oracle[b,j] } (an
+ *     integer count).  tgt [B,T], path / guess / oracle [B,L], n_right [B], all int64 contiguous.  One workgroup per sample.
+ *
+ *   dsp_glance_reveal: per vertex  keep_prob [B,L] fp32, revealed [B,L] bytes (0 / 1) = unif < keep_prob, glanced [B,L] int64 =
+ *     revealed ? oracle : prev.  unif [B,L] fp32; path, oracle, prev [B,L] int64.
+ *       mode DSP_GLANCE_PROB:  param = prob [B] fp32;  keep_prob[b,j] = prob[b] * (path[b,j] >= 0 ? 1 : 0)   (the IEEE product)
+ *       mode DSP_GLANCE_COUNT: param = counts [B] int64, scores [B,L] fp32.  Scores of vertices with path < 0 count as -100.  keep_prob is 1
+ *         where the score is >= the row's counts[b]-th largest score and 0 elsewhere: ties with the threshold are all kept, the
+ *         comparison is IEEE (-0.0 ties +0.0); counts[b] == 0 compares against 100 (keeps nothing); counts[b] beyond the number of
+ *         aligned vertices reaches the -100 fill and keeps the whole row (counts beyond L act as L, below 0 as 1).  Scores must not be NaN.
+ *         The threshold comes from an exact radix select over the row held in LDS (no sort; integer histograms: the same bits on every
+ *         run), which bounds the row: 1 <= L <= DSP_GLANCE_MAX_L in both modes. */
+#define DSP_F64 3
+#define DSP_GLANCE_MAX_L 16000
+#define DSP_GLANCE_PROB 0
+#define DSP_GLANCE_COUNT 1
+int dsp_force_emit(const void* match, int dtype, int64_t sb, int64_t st, const int64_t* path, const unsigned char* revealed, void* out,
+                   int64_t ldo, int B, int T, int L, dsp_stream_t stream);
+int dsp_force_emit_bwd(const void* grad_out, int dtype, int64_t sb, int64_t st, int64_t sl, const unsigned char* revealed, void* grad_match,
+                       int64_t ldg, int B, int T, int L, dsp_stream_t stream);
+int dsp_glance_oracle(const int64_t* tgt, const int64_t* path, const int64_t* guess, int64_t* oracle, int64_t* n_right, int B, int T, int L,
+                      dsp_stream_t stream);
+int dsp_glance_reveal(const float* scores, const void* param, int mode, const float* unif, const int64_t* path, const int64_t* oracle,
+                      const int64_t* prev, float* keep_prob, unsigned char* revealed, int64_t* glanced, int B, int L, dsp_stream_t stream);
+
 /* Conformer convolution module, eval mode (fairseq conformer_layer.py ConvolutionModule: depthwise_conv -> batch_norm -> SiLU),
  * on the channels-last tensor:   y[b,t,c] = SiLU( BN_eval( sum_k w[c,k] * x[b,t+k-(K-1)/2,c] ) ),  zero padding outside [0,T).
  *   x, y [B,T,C] fp32 (16-byte aligned, C % 4 == 0, y != x); w [C,K] fp32 (the Conv1d(C,C,K,groups=C) weight [C,1,K]);
