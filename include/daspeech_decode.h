@@ -326,7 +326,10 @@ int dsp_relpos_attention(const float* q, const float* k, const float* v, long ld
  * samples N*ldq / M*ldk / M*ldv apart: the slices of a fused q|k|v projection are served without a copy), key_pad_mask [B,M] bytes or
  * NULL, out [B,N,H*dk] contiguous.  dk = 64 or 128.  A sample whose keys are all masked gets NaN rows, as torch's soft-max does.
  * q_lens [B] (device int32) or NULL: queries at or after q_lens[b] + q_slack are padding no valid output depends on; their 32-query
- * groups are not computed and their output rows are written as zeros (see dsp_conv1d_split_ragged). */
+ * groups are not computed and their output rows are written as zeros (see dsp_conv1d_split_ragged).
+ * Range (this entry point and dsp_relpos_attention): q, k, v and the position projection are split into fp16 hi / lo parts as in
+ * dsp_conv1d_split, so every entry — the rows of masked keys included, which are staged like any other before their weight becomes
+ * exp(-inf) = 0 — must stay inside the fp16 range (|x| <= 65504); finite padding rows inside it cannot reach a valid query. */
 int dsp_attention_split(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const unsigned char* key_pad_mask,
                         float* out, int B, int N, int M, int H, int DK, float scale, const int* q_lens, int q_slack, dsp_stream_t stream);
 
