@@ -113,6 +113,11 @@ SIGNATURES = {
                                      _c_int, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p]),
     "dsp_layer_norm": (_c_int, [_c_p, _c_p, _c_p, ctypes.c_float, _c_p, ctypes.c_long, _c_int, _c_p]),
     "dsp_dwconv_bn_silu": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_dwconv_bn_silu_train_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "dsp_dwconv_bn_silu_train_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_float, _c_p, _c_p, _c_p, _c_p, _c_sz,
+                                              _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_dwconv_bn_silu_train_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz,
+                                              _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_hifigan_conv": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_int),
                                   ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_hifigan_conv_chain": (_c_int, [_c_p, _c_int, _c_int, _c_p]),

@@ -17,6 +17,10 @@ Host-side mirror of the reference code these replace:
                       force-emit of the revealed vertices in one pass from `path` / `keep_word_mask`, with its gradient, and the reveal
                       selection by an exact radix select; these two keep their torch formulation for CPU tensors and unserved inputs
                       (set_glance_hip(False): always), with the same bits
+  dwconv_bn_silu_autograd   fairseq/fairseq/modules/conformer_layer.py ConvolutionModule (depthwise_conv -> batch_norm -> SiLU) in TRAINING mode,
+                      under autograd on the channels-last tensor (csrc/conformer_train.hip): fp32 / fp16 / bf16, batch statistics and the
+                      running-buffer update, a backward whose reductions run in a fixed order without float atomics; ConformerLayer keeps
+                      its torch lines where dwconv_bn_silu_autograd_served says no (set_conv_module_hip(False): always)
 No CPU fallback elsewhere: GPU tensors only.
 """
 import ctypes
@@ -900,6 +904,129 @@ def dwconv_bn_silu(x: Tensor, conv_weight: Tensor, bn: "torch.nn.BatchNorm1d") -
         _lib.check(lib.dsp_dwconv_bn_silu(_lib.ptr(xf), _lib.ptr(wt), _lib.ptr(bw), _lib.ptr(bb), _lib.ptr(bm), _lib.ptr(bv), float(bn.eps),
                                           _lib.ptr(y), B, T, C, K, _lib.current_stream_handle()), "dsp_dwconv_bn_silu")
     return y.to(x.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ convolution module under autograd (csrc/conformer_train.hip)
+CONV_MODULE_HIP = True       # set_conv_module_hip(False): ConformerLayer keeps its torch lines in training on every input
+CONVMOD_TIME_TILE = 8        # DSP_CONVMOD_TIME_TILE: frames per thread
+CONVMOD_CHUNK_TILES = 16     # DSP_CONVMOD_CHUNK_TILES: time tiles per reduction chunk (one workspace partial each)
+CONVMOD_KERNEL_SIZES = (3, 7, 15, 31)
+
+
+def set_conv_module_hip(on: bool) -> bool:
+    """Switch the HIP convolution-module operator of ConformerLayer's training branch on or off; returns the previous setting.  Off:
+    dwconv_bn_silu_autograd_served answers False and the torch lines run — the tests and tools/convmod_bench.py compare the two in one process."""
+    global CONV_MODULE_HIP
+    old, CONV_MODULE_HIP = CONV_MODULE_HIP, bool(on)
+    return old
+
+
+def _bn_tensors(bn):
+    return [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+
+
+def dwconv_bn_silu_autograd_served(x: Tensor, conv: "torch.nn.Conv1d", bn: "torch.nn.BatchNorm1d") -> bool:
+    """True when dwconv_bn_silu_autograd serves ConformerLayer's training branch on these arguments: the switch is on, autocast off, x a
+    contiguous GPU tensor [B,T,C] in fp32 / fp16 / bf16 with B*T >= 2 and C a multiple of the channels in 16 bytes (4, or 8 for the 16-bit
+    dtypes: a lane owns one 16-byte group), conv the depthwise Conv1d(C, C, K, padding=(K-1)//2, groups=C, bias=False) with K in 3 / 7 / 15 /
+    31 and the dtype of x, bn an affine BatchNorm1d(C) in training mode with a momentum, its parameters and buffers all in that dtype or all
+    in fp32.  Everything else (eval mode with gradients, autocast, float64, CPU) keeps the torch formulation."""
+    if not CONV_MODULE_HIP or torch.is_autocast_enabled():
+        return False
+    if not (x.is_cuda and x.dim() == 3 and x.is_contiguous() and str(x.dtype) in _lib.DTYPE_CODES):
+        return False
+    B, T, C = x.shape
+    if B * T < 2 or B * T > (1 << 24) or C % (16 // x.element_size()) or C < 1:
+        return False
+    w = conv.weight
+    K = conv.kernel_size[0]
+    if (w.dtype != x.dtype or w.device != x.device or K not in CONVMOD_KERNEL_SIZES or tuple(w.shape) != (C, 1, K) or conv.bias is not None
+            or conv.stride[0] != 1 or conv.dilation[0] != 1 or conv.groups != C or conv.padding != ((K - 1) // 2,)
+            or getattr(conv, "padding_mode", "zeros") != "zeros"):
+        return False
+    if not (bn.training and bn.affine and bn.momentum is not None and bn.num_features == C):
+        return False
+    ts = _bn_tensors(bn)
+    return all(t.device == x.device for t in ts) and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts))
+
+
+class _DwconvBnSiluTrainFn(torch.autograd.Function):
+    """dsp_dwconv_bn_silu_train_fwd / _bwd.  Saved for the backward: x, the weights, gamma, beta and the fp32 batch mean / invstd — z is
+    recomputed from x.  The running buffers are updated in place by the forward (the batch statistics never visit the host)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, momentum, eps):
+        xx = x.detach().contiguous()
+        B, T, C = xx.shape
+        wt = w.detach().reshape(C, -1).contiguous()
+        K = wt.shape[1]
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        lib = _lib.load()
+        dev = xx.device
+        with torch.cuda.device(dev):
+            y = torch.empty_like(xx)
+            mean = torch.empty((C,), dtype=torch.float32, device=dev)
+            invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+            if B:
+                nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                _lib.check(lib.dsp_dwconv_bn_silu_train_fwd(_lib.ptr(xx), _lib.ptr(wt), _lib.ptr(g), _lib.ptr(b), _lib.ptr(running_mean),
+                                                            _lib.ptr(running_var), float(momentum), float(eps), _lib.ptr(y), _lib.ptr(mean),
+                                                            _lib.ptr(invstd), _lib.ptr(ws), nbytes, _code(xx), _code(g), B, T, C, K,
+                                                            _lib.current_stream_handle()), "dsp_dwconv_bn_silu_train_fwd")
+        ctx.save_for_backward(xx, wt, g, b, mean, invstd)
+        ctx.wshape = tuple(w.shape)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        xx, wt, g, b, mean, invstd = ctx.saved_tensors
+        B, T, C = xx.shape
+        K = wt.shape[1]
+        need = ctx.needs_input_grad
+        gy = grad_y.contiguous()
+        lib = _lib.load()
+        dev = xx.device
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(xx) if need[0] else None
+            dw = torch.empty_like(wt) if need[1] else None
+            dg = torch.empty_like(g) if need[2] else None
+            db = torch.empty_like(b) if need[3] else None
+            if B and any(need[:4]):
+                nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                _lib.check(lib.dsp_dwconv_bn_silu_train_bwd(_lib.ptr(xx), _lib.ptr(wt), _lib.ptr(g), _lib.ptr(b), _lib.ptr(mean), _lib.ptr(invstd),
+                                                            _lib.ptr(gy), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(dg), _lib.ptr(db), _lib.ptr(ws), nbytes,
+                                                            _code(xx), _code(g), B, T, C, K, _lib.current_stream_handle()),
+                           "dsp_dwconv_bn_silu_train_bwd")
+        return dx, (None if dw is None else dw.view(ctx.wshape)), dg, db, None, None, None, None
+
+
+def dwconv_bn_silu_autograd(x: Tensor, conv_weight: Tensor, bn: "torch.nn.BatchNorm1d") -> Tensor:
+    """SiLU(BatchNorm_train(depthwise_conv1d(x))) on channels-last x [B,T,C] — the middle of the Conformer convolution module in training
+    mode, differentiable w.r.t. x, conv_weight [C,1,K], bn.weight and bn.bias (include/daspeech_decode.h: dsp_dwconv_bn_silu_train_fwd /
+    _bwd).  Batch statistics over all B*T frames (no padding mask, as the reference); bn.running_mean / running_var / num_batches_tracked
+    are updated as nn.BatchNorm1d updates them, and left alone with track_running_stats=False.  fp32 / fp16 / bf16 (float64 is refused,
+    never narrowed); the BatchNorm tensors in the dtype of x or all in fp32.  Bit-reproducible forward and backward."""
+    ts = [conv_weight] + _bn_tensors(bn)
+    if (str(x.dtype) not in _lib.DTYPE_CODES or conv_weight.dtype != x.dtype or bn.weight is None or bn.bias is None
+            or not (all(t.dtype == x.dtype for t in ts[1:]) or all(t.dtype == torch.float32 for t in ts[1:]))):
+        raise RuntimeError("dwconv_bn_silu_autograd: expected GPU tensors with x and conv_weight in one of fp32 / fp16 / bf16 and the BatchNorm "
+                           f"parameters and buffers in that dtype or all in fp32, got {x.dtype}, {conv_weight.dtype} and "
+                           f"{[str(t.dtype) for t in ts[1:]]}")
+    _gpu("dwconv_bn_silu_autograd", x, *ts)
+    K = conv_weight.shape[-1]
+    if (x.dim() != 3 or tuple(conv_weight.shape) != (x.shape[2], 1, K) or K not in CONVMOD_KERNEL_SIZES or bn.num_features != x.shape[2]
+            or x.shape[2] % (16 // x.element_size()) or not 2 <= x.shape[0] * x.shape[1] <= (1 << 24) or bn.momentum is None):
+        raise RuntimeError(f"dwconv_bn_silu_autograd: x {tuple(x.shape)} / conv_weight {tuple(conv_weight.shape)} are not served (x [B,T,C] with "
+                           "B*T >= 2 and C a multiple of the channels in 16 bytes, conv_weight [C,1,K] with K in 3 / 7 / 15 / 31, a momentum)")
+    track = bn.running_mean is not None and bn.running_var is not None
+    y = _DwconvBnSiluTrainFn.apply(x, conv_weight, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+                                   bn.momentum, bn.eps)
+    if track and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return y
 
 
 class SplitConv1d:

@@ -237,8 +237,13 @@ class ConformerLayer(nn.Module):
             # the two pointwise (kernel 1) convolutions are GEMMs on the [B,T,C] layout the layer already has: F.linear on the
             # checkpoint's [out, in, 1] weights instead of Conv1d, which MIOpen runs as im2col + GEMM between two transposes
             y = F.glu(F.linear(c["layer_norm"](x), c["pointwise_conv1"].weight.squeeze(-1)), dim=-1)
-            y = F.silu(c["batch_norm"](c["depthwise_conv"](y.transpose(1, 2))))
-            x = x + _drop(F.linear(y.transpose(1, 2), c["pointwise_conv2"].weight.squeeze(-1)), p, tr)  # :100
+            if decode_ops.dwconv_bn_silu_autograd_served(y, c["depthwise_conv"], c["batch_norm"]):
+                # depthwise conv + batch-statistics BN + SiLU and their backward as HIP passes over [B,T,C] (csrc/conformer_train.hip): no transposes
+                y = decode_ops.dwconv_bn_silu_autograd(y, c["depthwise_conv"].weight, c["batch_norm"])
+                x = x + _drop(F.linear(y, c["pointwise_conv2"].weight.squeeze(-1)), p, tr)              # :100
+            else:
+                y = F.silu(c["batch_norm"](c["depthwise_conv"](y.transpose(1, 2))))
+                x = x + _drop(F.linear(y.transpose(1, 2), c["pointwise_conv2"].weight.squeeze(-1)), p, tr)  # :100
             x = ffn(self.ffn2, x)
             return self.final_layer_norm(x)
         # pre-norm blocks with their LayerNorms folded into the kernels around them (eval): ffn1 (LayerNorm while staging) -> attention (its

@@ -239,6 +239,37 @@ int dsp_glance_reveal(const float* scores, const void* param, int mode, const fl
 int dsp_dwconv_bn_silu(const float* x, const float* w, const float* bn_w, const float* bn_b, const float* bn_mean,
                        const float* bn_var, float eps, float* y, int B, int T, int C, int K, dsp_stream_t stream);
 
+/* The same three steps in TRAINING mode, under autograd (csrc/conformer_train.hip): batch statistics, running-buffer update, backward.
+ *   With N = B*T, P = (K-1)/2, zero padding outside [0,T), no padding mask (the reference's ConvolutionModule takes none):
+ *     z = depthwise(x);  mean[c], var[c] (biased) over the N values of channel c;  invstd = 1/sqrt(var + eps);  zh = (z - mean) * invstd;
+ *     u = gamma*zh + beta;  y = u*sigmoid(u);  running_mean <- (1-momentum)*running_mean + momentum*mean;
+ *     running_var <- (1-momentum)*running_var + momentum*var*N/(N-1)        (num_batches_tracked is the caller's)
+ *   backward from grad_y:  du = grad_y * s*(1 + u*(1-s)), s = sigmoid(u);  dbeta = sum du;  dgamma = sum du*zh;
+ *     dz = gamma*invstd*(du - dbeta/N - zh*dgamma/N);  dx[b,t,c] = sum_k w[c,k]*dz[b,t-k+P,c];  dw[c,k] = sum_{b,t} dz[b,t,c]*x[b,t+k-P,c].
+ *   x, y, grad_y, dx [B,T,C] and w, dw [C,K] share the dtype code act_dtype (DSP_F32 / DSP_F16 / DSP_BF16); gamma, beta, the running
+ *   buffers, dgamma and dbeta [C] share bn_dtype (act_dtype, or DSP_F32); save_mean / save_invstd [C] are fp32 (forward outputs, backward
+ *   inputs).  All arithmetic is fp32, the statistics included; every output is rounded once to its dtype.  x / y / grad_y / dx 16-byte
+ *   aligned, C a multiple of the channels in 16 bytes (4 or 8), K in {3, 7, 15, 31}, 2 <= B*T <= 2^24.
+ *   EVERY OUTPUT ELEMENT IS WRITTEN.  Every reduction over N is two-stage: one partial per chunk of DSP_CONVMOD_CHUNK_TILES time tiles
+ *   (DSP_CONVMOD_TIME_TILE frames each, tiles numbered sample by sample) reduced in a fixed order inside one workgroup, then the partials
+ *   added in ASCENDING chunk order; the variance from (count, mean, M2) triples of centred values, never from E[z^2] - mean^2.  NO FLOAT
+ *   ATOMICS and no hand-off between workgroups: the same inputs give the same bits on every call.
+ *   running_mean / running_var may be NULL (not tracked); each of dx / dw / dgamma / dbeta may be NULL: only what is asked for is computed,
+ *   and leaving one out does not change the bits of the others.  workspace: dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K) bytes of
+ *   device memory, 16-byte aligned, for either call (contents need not survive between them; DSP_ENOSPC if smaller); host arithmetic only,
+ *   0 for B == 0, monotone in every argument, a multiple of 16.  z is never stored (recomputed from x where needed); dz is kept in fp32 in
+ *   the backward's workspace.  Bad sizes, null or aliased pointers, misalignment: DSP_EINVAL before any launch; B == 0: DSP_OK. */
+#define DSP_CONVMOD_TIME_TILE 8
+#define DSP_CONVMOD_CHUNK_TILES 16
+size_t dsp_dwconv_bn_silu_train_workspace_bytes(int B, int T, int C, int K);
+int dsp_dwconv_bn_silu_train_fwd(const void* x, const void* w, const void* gamma, const void* beta, void* running_mean, void* running_var,
+                                 float momentum, float eps, void* y, float* save_mean, float* save_invstd, void* workspace,
+                                 size_t workspace_bytes, int act_dtype, int bn_dtype, int B, int T, int C, int K, dsp_stream_t stream);
+int dsp_dwconv_bn_silu_train_bwd(const void* x, const void* w, const void* gamma, const void* beta, const float* save_mean,
+                                 const float* save_invstd, const void* grad_y, void* dx, void* dw, void* dgamma, void* dbeta,
+                                 void* workspace, size_t workspace_bytes, int act_dtype, int bn_dtype, int B, int T, int C, int K,
+                                 dsp_stream_t stream);
+
 /* fp32-accurate Conv1d ("same" padding, stride 1) on the fp16 matrix cores by operand splitting (x = xh + xl/2048, w = wh + wl/2048;
  * the products xh.wh, xh.wl, xl.wh are exact in the fp32 accumulator, the dropped xl.wl term is 2^-22 relative) — for the
  * FastSpeech2 FFT feed-forward convolutions (fairseq fastspeech2.py:42-63), which MIOpen runs at 60-70 TFLOP/s in fp32.
