@@ -29,8 +29,10 @@
 // L2: a workgroup reads 64 KB of fragments per tile and nothing of it twice, so reuse has to come from its neighbours — with B % 8 == 0 an
 // XCD keeps whole samples, its resident workgroups are neighbouring owner tiles of one sample, and they all walk the partner tiles from the
 // same end (lock-step for a dense window): L2 hit rate 3 % -> 85-90 %, STATS 1.98 -> 1.41 ms at the C2 shape.
-// Same arithmetic as extract_links.hip (same masks, same -inf conventions, same `stats` layout), so the two families are interchangeable
-// per call (tests compare them element by element, and both with torch autograd / the fp64 oracle).
+// Same arithmetic as extract_links.hip (same masks, same -inf conventions, same `stats` layout, grad_links ignored wherever the link is -inf),
+// so the two families are interchangeable per call.  tests/test_gpu_decode_ops.py compares the families element by element and with torch
+// autograd on the device; tests/test_gpu_links_regimes.py holds each family on its own to a float64 CPU reference, per sample and head, at
+// the tile, length and dispatch edges and under peaked scores, wide-ranged and non-finite (beyond the graph) gradients.
 #include "dag_dp.h"
 #include <atomic>
 #include "../../include/daspeech_decode.h"
@@ -248,8 +250,10 @@ __global__ __launch_bounds__(512) void xl_mfma_kernel(XmParams p)
                 const int off = ok ? (i * TR + d) * 4 : 0;
                 const float lk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_lk, off, 0, 0));
                 const float gv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_gg, off, 0, 0));
-                // links log2(e); a -inf link (or a slot outside the band) becomes +3e38: exp2(s2 + ca - 3e38) = 0, its share A is 0 without a test
-                r_lkv[it] = (ok && lk != NEG_INF) ? lk * LOG2E : 3.0e38f; r_gv[it] = ok ? gv : 0.f;
+                // links log2(e); a -inf link (or a slot outside the band) becomes +3e38: exp2(s2 + ca - 3e38) = 0, and its gradient is taken away here,
+                // as extract_links.hip selects it away: a NaN or an infinity in grad_links beyond the graph would survive the product with that 0
+                const bool live = ok && lk != NEG_INF;
+                r_lkv[it] = live ? lk * LOG2E : 3.0e38f; r_gv[it] = live ? gv : 0.f;
             }
             if constexpr (TRANSPOSED) {
                 if (tid < 256) {
