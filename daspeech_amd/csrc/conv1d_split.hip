@@ -28,7 +28,9 @@ struct CsParams {
     const float* ln_w; const float* ln_b; float ln_eps;   // LayerNorm of the input rows while they are staged (256-channel one-tap layers: the row sits in half a wave)
     int kparts, tap_groups; float* part;          // split-K: kparts = nslices * tap_groups workgroups per output tile, raw partial sums to part [kparts][B][T][M]
     const int* lens; int slack;                   // ragged batch: rows >= lens[b] + slack of sample b are padding nobody reads — their
-};                                                // tiles are not computed, the output rows are written as zeros
+                                                  // tiles are not computed, the output rows are written as zeros
+    int mper;                                     // output tiles per workgroup: blockIdx.y owns tiles [y * mper, (y + 1) * mper) of the row tile it
+};                                                // staged ONCE (cs_plan; 1 for multi-slice and split-K launches)
 
 template <int CI, int MT, int NT, int WM, int WN>
 __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
@@ -42,10 +44,14 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
     const int wm = wave % WM, wn = wave / WM;
     const int lr = lane & 15, lk = lane >> 4;
     const int kp = p.kparts > 1 ? (int)(blockIdx.y % p.kparts) : 0;
-    const int b = blockIdx.z, t0 = blockIdx.x * NT, m0 = (p.kparts > 1 ? (int)(blockIdx.y / p.kparts) : (int)blockIdx.y) * MT;
+    const int b = blockIdx.z, t0 = blockIdx.x * NT;
+    // the workgroup's output tiles m_begin .. m_end - 1: the staged rows serve all of them
+    const int m_begin = p.kparts > 1 ? (int)(blockIdx.y / p.kparts) : (int)blockIdx.y * p.mper;
+    const int m_end = min(m_begin + (p.kparts > 1 ? 1 : p.mper), (p.M + MT - 1) / MT);
     if (p.lens && t0 >= p.lens[b] + p.slack) {          // a tile of padding rows (block-uniform): zeros, so that they stay finite
         if (p.accumulate) return;
-        const int cw = min(MT, p.M - m0) >> 2;          // float4 columns of this tile
+        const int m0 = m_begin * MT;
+        const int cw = min((m_end - m_begin) * MT, p.M - m0) >> 2;      // float4 columns of this range of tiles
         const int rows = min(NT, p.T - t0);
         float* dst = p.kparts > 1 ? p.part + ((size_t)kp * p.B + b) * p.T * p.M : p.out + (size_t)b * p.T * p.ldo;     // split-K: the partial sums are zero
         const size_t ld = p.kparts > 1 ? (size_t)p.M : (size_t)p.ldo;
@@ -61,16 +67,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
     char* tl = cs_smem + (size_t)R * CI * 2;              // lo tile
     const float* X = p.x + (size_t)b * p.T * p.ldx;
 
-    cs_f4 acc0[MI][NI], acc1[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) { acc0[i][j] = (cs_f4){0.f, 0.f, 0.f, 0.f}; acc1[i][j] = (cs_f4){0.f, 0.f, 0.f, 0.f}; }
-    const int co_base = m0 + wm * (MI * 16);
     const int tl_base = wn * (NI * 16);
     const int Mt = (p.M + 15) >> 4;
     using BF = SplitBFrag<CI>;
-    const int tile0 = co_base >> 4;
     const uint32_t lane_off = (uint32_t)lane * 16u;
     const int row_l = tl_base + lr;                       // the lane's row of column tile 0, before the tap's shift
     // split-K: this workgroup owns ONE input slice and one group of taps (short sequences: a 1024 -> 256, K = 9 layer on 61 positions
@@ -82,11 +81,23 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
         k_lo = (kp % p.tap_groups) * tpg; k_hi = min(p.ntaps, k_lo + tpg);
     }
     const int sb = k_lo * NC, nsteps = (k_hi - k_lo) * NC;
+    // ---- the output tiles of this workgroup, one after the other.  More than one only where the staged rows are the whole reduction
+    //      (one slice, no split-K): they are staged before the first tile and are read-only from that barrier on, so every later tile
+    //      starts from zero accumulators, runs the K loop from its own weight fragments and leaves through the epilogue, without a barrier.
+    for (int mi = m_begin; mi < m_end; ++mi) {
+    const int co_base = mi * MT + wm * (MI * 16);
+    const int tile0 = co_base >> 4;
+    cs_f4 acc0[MI][NI], acc1[MI][NI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j) { acc0[i][j] = (cs_f4){0.f, 0.f, 0.f, 0.f}; acc1[i][j] = (cs_f4){0.f, 0.f, 0.f, 0.f}; }
     // input slices of CI channels one after the other through the same LDS tiles; the accumulators stay in registers
     for (int sl = sl_lo; sl < sl_hi; ++sl) {
     const float* Xs = X + (size_t)sl * CI;
     const _Float16* WH = p.wh + (size_t)sl * p.wslice;
     const _Float16* WL = p.wl + (size_t)sl * p.wslice;
+    if (mi == m_begin) {                                  // (several slices: one output tile)
     if (sl > sl_lo) __syncthreads();                      // every wave is done with the previous slice's tiles
     // ---- stage: rows t0-P .. t0+NT-1+P, zero outside [0,T); split into hi / lo*2^11.  All of a lane's row chunks (R*CH/512 <= 10) are
     //      requested together, UNCONDITIONALLY from a clamped row: predicated loads wait for one another (r01h s_memtime accounting: 10 k
@@ -148,6 +159,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
         }
     }
     __syncthreads();
+    }
 
     // addresses: split_frag.h.  Weights: scalar pointers to the wave's M tiles of step sb, one step's stride apart; load_a takes the steps in
     // order.  (A tile past M reads tile 0: its rows are never stored.)
@@ -200,8 +212,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
         }
     }
 
-    }
+    }     // slices
 
+    int t0i = t0;                                         // (opaque: the rows' output addresses are formed here, per tile, not kept across the K loop)
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(t0i));
+#endif
     if (p.kparts > 1) {                                   // raw partial sums; bias, activation, residual: cs_reduce_kernel
         float* P = p.part + ((size_t)kp * p.B + b) * p.T * p.M;
 #pragma unroll
@@ -210,7 +226,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
             if (co >= p.M) continue;
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
-                const int t = t0 + tl_base + j * 16 + lr;
+                const int t = t0i + tl_base + j * 16 + lr;
                 if (t >= p.T) continue;
                 *reinterpret_cast<float4*>(P + (size_t)t * p.M + co) = make_float4(acc0[i][j][0] + acc1[i][j][0] * (1.f / 2048.f), acc0[i][j][1] + acc1[i][j][1] * (1.f / 2048.f),
                                                                                  acc0[i][j][2] + acc1[i][j][2] * (1.f / 2048.f), acc0[i][j][3] + acc1[i][j][3] * (1.f / 2048.f));
@@ -230,7 +246,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
         }
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const int t = t0 + tl_base + j * 16 + lr;
+            const int t = t0i + tl_base + j * 16 + lr;
             if (t >= p.T) continue;
             float* O = p.out + ((size_t)b * p.T + t) * p.ldo + co;
             float v[4];
@@ -260,6 +276,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
             *reinterpret_cast<float4*>(O) = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
+    }     // output tiles
 }
 
 // fp32 weight [ntaps][M][CI] (tap-major) -> hi / lo fp16 in fragment order [ntaps][CI/32][ceil(M/16)][64][8] (see hifigan_conv.hip)
@@ -307,14 +324,123 @@ __global__ __launch_bounds__(256) void cs_reduce_kernel(const float* __restrict_
     }
 }
 
+// ---- launch plan: which instance, how the rows are tiled, which output tiles a workgroup owns.  Host arithmetic only (no device call:
+//      dsp_conv1d_split_plan answers without a GPU).
+enum CsInst { CS_256_256_128 = 0, CS_256_128_64, CS_256_256_64, CS_512_256_32, CS_512_256_64x16, CS_512_256_64, CS_128_128_256, CS_NONE };
+// per_cu: workgroups a CU holds (registers and the one-tap LDS tiles); batch_rows: dense one-tap launches may tile the B * T rows as one
+// sequence (not <256,128,64>: its 12 us launches did not get shorter with 198 workgroups instead of 256, profiles/r09_stage_once.txt)
+struct CsInstInfo { int MT, NT, per_cu; bool batch_rows; };
+static const CsInstInfo cs_inst_info[CS_NONE] = {{256, 128, 1, true}, {128, 64, 2, false}, {256, 64, 1, true}, {256, 32, 1, true}, {256, 64, 1, true},
+                                                 {256, 64, 1, true}, {128, 256, 1, true}};
+
+static CsInst cs_pick(int B, int T, int CI, int nslices, int M, int ntaps, long kmul, bool has_ln)
+{
+    if (has_ln) return CS_256_256_64;                          // the instance that carries the staged LayerNorm
+    switch (CI) {
+        case 256: {
+            // 128-row tiles (8 time sub-tiles per wave, one workgroup per CU) when they fill the chip, 64-row tiles (two per CU) for the
+            // narrow layers: 256 -> 256 projections on 12.6 k rows are 99 workgroups at 128 rows
+            const long wgs128 = (long)((T + 127) / 128) * ((M + 255) / 256) * B * kmul;
+            if (wgs128 >= 256) return CS_256_256_128;
+            // under-filled launches (the Conformer's 256 -> 256 projections on 4.4 k positions: 69 workgroups of 256 output channels) take
+            // 128-channel output tiles: twice the workgroups at 124 VGPRs, two per CU (the 256-channel tile needs 188: one per CU).
+            // Acoustic stage 14.60 -> 14.25 ms; applied to every 64-row launch: 14.47 (the input tile is staged twice)
+            const long wgs64 = (long)((T + 63) / 64) * ((M + 255) / 256) * B * kmul;
+            if (wgs64 < 150) return CS_256_128_64;
+            return CS_256_256_64;
+        }
+        case 512: {
+            // (r03: a 512-wide Linear layer run as two 256-wide slices — 65 KB tiles, two workgroups per CU — is no faster: 14.59 vs 14.55 ms of
+            //  GPU time per acoustic batch.)
+            // launches that would leave CUs idle with 64-frame tiles (the Conformer's 2048 -> 256 on 4.4 k positions: 69 workgroups)
+            // take 32-frame tiles, two workgroups per CU: 52.7 -> 36.7 us; where the 64-frame tiles fill the chip they are 10-20 % faster
+            // (at 192 workgroups the 64-frame tiles still win: 34.3 vs 38.9 us for 1024 -> 256 on 10.6 k positions; 128-channel tiles: no gain)
+            const long wgs64 = (long)((T + 63) / 64) * ((M + 255) / 256) * B * kmul;
+            if (ntaps <= 9 && wgs64 < 128) return CS_512_256_32;
+            // r05: one-tap, one-slice layers (the NAT decoder's 512 -> 512 / 1536 / 2048 projections) as 16-wave workgroups, 16 output channels per
+            // wave: four waves per SIMD under the one resident workgroup (122 VGPRs), bit-identical results, 5-8 % faster (tools/cs_var_bench.py:
+            // 39.8 -> 36.7, 98.7 -> 91.4, 116.6 -> 108.6 us; 512 output channels per workgroup: 2.2 x slower (spills), 8 x 2 waves: +18 %;
+            // multi-slice and K = 9 layers: no difference; the 256-wide instances: no gain at 64 rows, +20 % at 128 rows)
+            if (ntaps == 1 && nslices == 1 && kmul == 1) return CS_512_256_64x16;
+            return CS_512_256_64;
+        }
+        case 128: return CS_128_128_256;
+    }
+    return CS_NONE;
+}
+
+struct CsPlan { CsInst inst; int B, T, row_tiles, m_tiles, ranges, mper; };
+
+// The instance comes from the caller's (B, T), as it always has.  Then:
+//  * a dense one-tap, one-slice layer is a GEMM over the B * T rows (the ABI has no batch stride: sample b starts at row b * T), so its
+//    rows may be tiled as ONE sequence of B * T: no partial tile per sample (T = 197 - 200 in 64-row tiles: 128 tiles for 99 tiles' worth).
+//    Taken where the traced time drops: the launch then fits one round of resident workgroups, or needs fewer rounds than before
+//    (256 -> 768 with the staged LayerNorm: 384 and 300 workgroups are both two rounds, 27.8 us either way: tiled per sample as before);
+//  * where the staged rows are the whole reduction (one slice, no split-K; any number of taps) a workgroup runs a contiguous range of
+//    output tiles from the rows it staged once.  Ranges per row tile (equal lengths: a divisor of the tile count): the number with the
+//    fewest K-steps on a CU's critical path, rounds of resident workgroups x (staging, counted as one tap's K loop, + the range's
+//    tiles x taps); among equals the most ranges.  Measured per layer in profiles/r09_stage_once.txt: the 512-wide decoder layers run
+//    every output tile of a row tile in one workgroup (224 workgroups, one round), 256 -> 1024, K = 9 two tiles (staging is 1 / 37 of a
+//    tile's work: the round count decides), the short 256-wide layers one tile per workgroup as before.
+static CsPlan cs_plan(int B, int T, int CI, int nslices, int M, int ntaps, bool has_lens, int tap_groups, bool has_ln, int n_cus)
+{
+    CsPlan pl;
+    const long kmul = tap_groups > 0 ? (long)nslices * tap_groups : 1;
+    pl.inst = cs_pick(B, T, CI, nslices, M, ntaps, kmul, has_ln);
+    pl.B = B; pl.T = T; pl.row_tiles = 0; pl.m_tiles = 0; pl.ranges = 0; pl.mper = 1;
+    if (pl.inst == CS_NONE) return pl;
+    const CsInstInfo& ii = cs_inst_info[pl.inst];
+    const bool whole = nslices == 1 && kmul == 1;            // one staged tile serves the whole reduction
+    const size_t lds = (size_t)2 * (ii.NT + ntaps - 1) * CI * 2;
+    const long resident = (long)(n_cus > 0 ? n_cus : 1) * (lds * ii.per_cu > 160 * 1024 ? 1 : ii.per_cu);
+    pl.m_tiles = (M + ii.MT - 1) / ii.MT;
+    pl.row_tiles = ((T + ii.NT - 1) / ii.NT) * B;
+    pl.ranges = pl.m_tiles;
+    if (!whole) return pl;
+    // ranges for a number of row tiles -> rounds of resident workgroups the launch then takes
+    auto choose = [&](long row_tiles, int& ranges) -> long {
+        long best = -1, rounds = 0;
+        for (int r = 1; r <= pl.m_tiles; ++r) {
+            if (pl.m_tiles % r) continue;
+            const long rd = (row_tiles * r + resident - 1) / resident, cost = rd * (1 + (long)(pl.m_tiles / r) * ntaps);
+            if (best < 0 || cost <= best) { best = cost; ranges = r; rounds = rd; }
+        }
+        return rounds;
+    };
+    const long rounds = choose(pl.row_tiles, pl.ranges);
+    if (ntaps == 1 && !has_lens && ii.batch_rows && (long)B * T <= 0x7fffffffL) {
+        const long flat_tiles = ((long)B * T + ii.NT - 1) / ii.NT;
+        int ranges_flat = 1;
+        const long rounds_flat = choose(flat_tiles, ranges_flat);
+        if (rounds_flat == 1 || rounds_flat < rounds) { pl.T = B * T; pl.B = 1; pl.row_tiles = (int)flat_tiles; pl.ranges = ranges_flat; }
+    }
+    pl.mper = pl.m_tiles / pl.ranges;
+    return pl;
+}
+
+static int cs_cus_override = 0;                      // dsp_conv1d_split_plan_cus: plan launches as for a device of this many CUs (0: ask the device)
+
+static int cs_device_cus()
+{
+    if (cs_cus_override > 0) return cs_cus_override;
+    static int cached[64] = {0};
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
+    if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); return 256; }
+    if (dev >= 0 && dev < 64) cached[dev] = cus;
+    return cus;
+}
+
 template <int CI, int MT, int NT, int WM, int WN>
-static int cs_launch(const CsParams& p, hipStream_t st)
+static int cs_launch(const CsParams& p, const CsPlan& pl, hipStream_t st)
 {
     const size_t lds = (size_t)2 * (NT + p.ntaps - 1) * CI * 2;
     if (lds > 160 * 1024) { set_error("conv1d_split: tiles need %zu bytes of LDS", lds); return DSP_EINVAL; }
     auto k = conv1d_split_kernel<CI, MT, NT, WM, WN>;
     set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((p.T + NT - 1) / NT, ((p.M + MT - 1) / MT) * (p.kparts > 1 ? p.kparts : 1), p.B), dim3(WM * WN * 64), lds, st, p);
+    // p.B / p.T are the plan's (one sequence of B * T rows for a dense one-tap layer)
+    hipLaunchKernelGGL(k, dim3((p.T + NT - 1) / NT, p.kparts > 1 ? pl.m_tiles * p.kparts : pl.ranges, p.B), dim3(WM * WN * 64), lds, st, p);
     return check_launch("conv1d_split");
 }
 
@@ -357,42 +483,42 @@ static int cs_run(const float* x, long ldx, const void* w_hi, const void* w_lo, 
     if (ln_w && (!ln_b || CI != 256 || nslices != 1 || ntaps != 1 || tap_groups > 0 || (((uintptr_t)ln_w | (uintptr_t)ln_b) & 15))) {
         set_error("conv1d_split: the staged LayerNorm needs a one-tap layer over exactly 256 input channels"); return DSP_EINVAL; }
     p.kparts = tap_groups > 0 ? nslices * tap_groups : 1; p.tap_groups = tap_groups > 0 ? tap_groups : 1; p.part = part;
-    const long kmul = p.kparts;                              // workgroups per output tile
     if (res && (((uintptr_t)res & 15) || ldr < M || (ldr & 3))) { set_error("conv1d_split: residual must be 16-byte aligned with row stride >= M"); return DSP_EINVAL; }
     hipStream_t st = as_stream(stream);
-    if (ln_w) return cs_launch<256, 256, 64, 8, 1>(p, st);      // the instance that carries the staged LayerNorm
-    switch (CI) {
-        case 256: {
-            // 128-row tiles (8 time sub-tiles per wave, one workgroup per CU) when they fill the chip, 64-row tiles (two per CU) for the
-            // narrow layers: 256 -> 256 projections on 12.6 k rows are 99 workgroups at 128 rows
-            const long wgs128 = (long)((T + 127) / 128) * ((M + 255) / 256) * B * kmul;
-            if (wgs128 >= 256) return cs_launch<256, 256, 128, 8, 1>(p, st);
-            // under-filled launches (the Conformer's 256 -> 256 projections on 4.4 k positions: 69 workgroups of 256 output channels) take
-            // 128-channel output tiles: twice the workgroups at 124 VGPRs, two per CU (the 256-channel tile needs 188: one per CU).
-            // Acoustic stage 14.60 -> 14.25 ms; applied to every 64-row launch: 14.47 (the input tile is staged twice)
-            const long wgs64 = (long)((T + 63) / 64) * ((M + 255) / 256) * B * kmul;
-            if (wgs64 < 150) return cs_launch<256, 128, 64, 8, 1>(p, st);
-            return cs_launch<256, 256, 64, 8, 1>(p, st);
-        }
-        case 512: {
-            // (r03: a 512-wide Linear layer run as two 256-wide slices — 65 KB tiles, two workgroups per CU — is no faster: 14.59 vs 14.55 ms of
-            //  GPU time per acoustic batch.)
-            // launches that would leave CUs idle with 64-frame tiles (the Conformer's 2048 -> 256 on 4.4 k positions: 69 workgroups)
-            // take 32-frame tiles, two workgroups per CU: 52.7 -> 36.7 us; where the 64-frame tiles fill the chip they are 10-20 % faster
-            // (at 192 workgroups the 64-frame tiles still win: 34.3 vs 38.9 us for 1024 -> 256 on 10.6 k positions; 128-channel tiles: no gain)
-            const long wgs64 = (long)((T + 63) / 64) * ((M + 255) / 256) * B * kmul;
-            if (ntaps <= 9 && wgs64 < 128) return cs_launch<512, 256, 32, 8, 1>(p, st);
-            // r05: one-tap, one-slice layers (the NAT decoder's 512 -> 512 / 1536 / 2048 projections) as 16-wave workgroups, 16 output channels per
-            // wave: four waves per SIMD under the one resident workgroup (122 VGPRs), bit-identical results, 5-8 % faster (tools/cs_var_bench.py:
-            // 39.8 -> 36.7, 98.7 -> 91.4, 116.6 -> 108.6 us; 512 output channels per workgroup: 2.2 x slower (spills), 8 x 2 waves: +18 %;
-            // multi-slice and K = 9 layers: no difference; the 256-wide instances: no gain at 64 rows, +20 % at 128 rows)
-            if (ntaps == 1 && nslices == 1 && kmul == 1) return cs_launch<512, 256, 64, 16, 1>(p, st);
-            return cs_launch<512, 256, 64, 8, 1>(p, st);
-        }
-        case 128: return cs_launch<128, 128, 256, 4, 2>(p, st);
+    const CsPlan pl = cs_plan(B, T, CI, nslices, M, ntaps, lens != nullptr, tap_groups, ln_w != nullptr, cs_device_cus());
+    p.B = pl.B; p.T = pl.T; p.mper = pl.mper;
+    switch (pl.inst) {
+        case CS_256_256_128: return cs_launch<256, 256, 128, 8, 1>(p, pl, st);
+        case CS_256_128_64: return cs_launch<256, 128, 64, 8, 1>(p, pl, st);
+        case CS_256_256_64: return cs_launch<256, 256, 64, 8, 1>(p, pl, st);
+        case CS_512_256_32: return cs_launch<512, 256, 32, 8, 1>(p, pl, st);
+        case CS_512_256_64x16: return cs_launch<512, 256, 64, 16, 1>(p, pl, st);
+        case CS_512_256_64: return cs_launch<512, 256, 64, 8, 1>(p, pl, st);
+        case CS_128_128_256: return cs_launch<128, 128, 256, 4, 2>(p, pl, st);
+        case CS_NONE: break;
     }
     set_error("conv1d_split: unsupported slice width %d (128, 256, 512; wider inputs are nslices slices)", CI);
     return DSP_EINVAL;
+}
+
+// Plan every later launch of this process as for a device of n_cus CUs; 0 returns to the device's own count.  The results do not depend
+// on it (tests run the output-tile loop at shapes that would otherwise give every tile its own workgroup).  Returns the previous value.
+extern "C" int dsp_conv1d_split_plan_cus(int n_cus)
+{
+    const int old = cs_cus_override;
+    cs_cus_override = n_cus > 0 ? n_cus : 0;
+    return old;
+}
+
+extern "C" int dsp_conv1d_split_plan(int B, int T, int CI, int nslices, int M, int ntaps, int has_lens, int has_ln, int tap_groups, int n_cus, int out[6])
+{
+    if (!out || B < 1 || T < 1 || M < 4 || ntaps < 1 || nslices < 1 || tap_groups < 0 || n_cus < 1) { set_error("conv1d_split_plan: bad arguments"); return DSP_EINVAL; }
+    if (has_ln && (CI != 256 || nslices != 1 || ntaps != 1 || tap_groups > 0)) { set_error("conv1d_split_plan: the staged LayerNorm needs a one-tap layer over 256 channels"); return DSP_EINVAL; }
+    const CsPlan pl = cs_plan(B, T, CI, nslices, M, ntaps, has_lens != 0, tap_groups, has_ln != 0, n_cus);
+    if (pl.inst == CS_NONE) { set_error("conv1d_split_plan: unsupported slice width %d", CI); return DSP_EINVAL; }
+    out[0] = pl.T; out[1] = pl.row_tiles; out[2] = pl.m_tiles; out[3] = pl.ranges;
+    out[4] = cs_inst_info[pl.inst].MT; out[5] = cs_inst_info[pl.inst].NT;
+    return DSP_OK;
 }
 
 extern "C" int dsp_conv1d_split(const float* x, long ldx, const void* w_hi, const void* w_lo, const float* bias, float* out, long ldo,

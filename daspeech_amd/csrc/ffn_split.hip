@@ -312,12 +312,17 @@ extern "C" int dsp_ffn_split(const float* x, long ldx, const float* ln_w, const 
     p.x = x; p.ldx = ldx; p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps; p.has_ln = ln_w != nullptr;
     p.w1h = (const _Float16*)w1_hi; p.w1l = (const _Float16*)w1_lo; p.b1 = b1;
     p.w2h = (const _Float16*)w2_hi; p.w2l = (const _Float16*)w2_lo; p.w2slice = dsp_conv1d_split_packed_elems(1, C, 512);
-    p.part = (float*)workspace; p.B = B; p.T = T; p.H = H; p.act = act; p.G = ff_groups(B, T, H);
+    // The module is a row-wise map and the ABI has no batch stride (sample b starts at row b * T of x, out and res), so the rows are
+    // tiled as ONE sequence of B * T: no partial tile per sample (T = 197 - 200: 128 tiles for 99 tiles' worth of rows).  The partial
+    // sums keep their [G][B * T][C] layout, and G still comes from the caller's (B, T): the fixed-order sum over the groups is the same.
+    const long rows_all = (long)B * T;
+    if (rows_all > 0x7fffffffL) { set_error("ffn_split: B * T = %ld rows", rows_all); return DSP_EINVAL; }
+    p.part = (float*)workspace; p.B = 1; p.T = (int)rows_all; p.H = H; p.act = act; p.G = ff_groups(B, T, H);
     hipStream_t st = as_stream(stream);
     const size_t lds = (size_t)4 * 64 * 256 * 2;
     auto k = ffn_split_kernel<256, 64>;
     set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3((T + 63) / 64, p.G, B), dim3(512), lds, st, p);
+    hipLaunchKernelGGL(k, dim3((p.T + 63) / 64, p.G, 1), dim3(512), lds, st, p);
     int rc = check_launch("ffn_split");
     if (rc != DSP_OK) return rc;
     const long n = (long)B * T * C;

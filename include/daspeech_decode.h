@@ -290,6 +290,15 @@ int dsp_conv1d_split(const float* x, long ldx, const void* w_hi, const void* w_l
 int dsp_conv1d_split_residual(const float* x, long ldx, const void* w_hi, const void* w_lo, const float* bias, const float* res, long ldr,
                               float alpha, float* out, long ldo, int B, int T, int CI, int nslices, int M, int ntaps, int relu,
                               dsp_stream_t stream);
+/* Launch shape (the result does not depend on it, bit for bit): a workgroup stages one tile of input rows and runs a contiguous range
+ * of output-channel tiles from it where the staged rows are the whole reduction (one slice, no split-K); a dense one-tap, one-slice
+ * layer tiles its rows as one sequence of B * T, which is what [B,T,.] with row strides and no batch stride is.  The library exports
+ * the choice as a host-only question, kept out of this header's declarations (tests pin it; it needs no GPU):
+ *   int dsp_conv1d_split_plan(int B, int T, int CI, int nslices, int M, int ntaps, int has_lens, int has_ln, int tap_groups, int n_cus,
+ *                             int out[6])   -> rows per launch, row tiles, output tiles, ranges of output tiles per row tile,
+ *                                              output-tile width, row-tile height;  tap_groups = 0: no split-K.
+ *   int dsp_conv1d_split_plan_cus(int n_cus) -> plans every later launch as for a device of n_cus CUs (0: the device's own count);
+ *                                              returns the previous setting. */
 
 
 /* the same for a ragged batch: lens [B] (device, int32) are the samples' valid lengths; a time tile that starts at or after
