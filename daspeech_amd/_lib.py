@@ -28,6 +28,7 @@ SIGNATURES = {
                                              _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_logsoftmax_gather_bwd_lazy": (_c_int, [_c_p, _c_int, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,
                                                 _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_logsoftmax_gather_plan": (_c_int, [_c_int] * 9 + [_c_p]),
     "dsp_logsoftmax_gather_f64": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,
                                            _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_logsoftmax_gather_bwd_f64": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,

@@ -628,111 +628,126 @@ __global__ __launch_bounds__(256) void lsg_bwd_reg_kernel(
     }
 }
 
-template <typename T>
-static int launch_fwd(void* logits, const int64_t* idx, int64_t isb, int64_t isj, int64_t iss, float* match,
-                      int64_t osb, int64_t osj, int64_t oss, int B, int L, int V, int S, int ws, hipStream_t st, float* stats = nullptr)
+// ---- launch plan: which instance serves a shape.  Pure host arithmetic (no device call), shared by the launchers below and by
+// dsp_logsoftmax_gather_plan, so that a test can ask on a machine without a GPU what a shape will run.
+enum { LSG_FWD_GENERIC = 0, LSG_FWD_REG = 1, LSG_FWD_REGL = 2, LSG_FWD_REGL_WIDE = 3, LSG_BWD_GENERIC = 4, LSG_BWD_REG = 5, LSG_BWD_REG_WIDE = 6 };
+struct LsgPlan { int family, vec, nv, rt, grid; size_t lds; };
+
+static inline int lsg_nv(int nvec) { return nvec <= 8 ? (nvec <= 2 ? 2 : nvec <= 4 ? 4 : nvec <= 6 ? 6 : 8) : (nvec <= 10 ? 10 : nvec <= 12 ? 12 : nvec <= 14 ? 14 : 16); }
+static inline int lsg_grid(int B, int L, int RT, long cap) { const long nt = (long)B * ((L + RT - 1) / RT); return (int)(nt < cap ? nt : cap); }
+
+// esize = sizeof(T), aligned16 = the base pointer is on a 16-byte boundary.  DSP_EINVAL (with the error text set) where no kernel serves S.
+static int lsg_plan_fwd(int esize, int B, int L, int V, int S, bool aligned16, LsgPlan& p)
 {
-    constexpr int N = Vec<T>::N;
-    const bool vec = (V % N == 0) && ((uintptr_t)logits % 16 == 0);
+    const int N = 16 / esize;
+    const bool vec = (V % N == 0) && aligned16;
     int RT = 16;
     while (RT > 1 && (size_t)S * RT * 4 > 60 * 1024) RT >>= 1;
     if ((size_t)S * RT * 4 > 150 * 1024) { set_error("logsoftmax_gather: S=%d too large for LDS staging", S); return DSP_EINVAL; }
     if (RT > L) { RT = 1; while (RT * 2 <= L) RT *= 2; }
-    const size_t lds = (16 + (size_t)S * RT) * sizeof(float);
-    const long ntiles = (long)B * ((L + RT - 1) / RT);
-    const int grid = (int)(ntiles < 2048 ? ntiles : 2048);
-    // register-resident variant when the row fits NV x 256 sixteen-byte vectors
+    // register-resident variants when the row fits NV x 256 sixteen-byte vectors
     const int nvec = (V + 256 * N - 1) / (256 * N);
-    if (vec && sizeof(T) == 4 && nvec > 8 && nvec <= 16 && S <= 8 * 256) {      // (half precision: 128 elements per lane — the generic kernel is faster, 3.6 vs 1.9-2.3 TB/s)
-        // wide rows (8 192 < V <= 16 384 fp32, 16 384 < V <= 32 768 half precision): the LDS-gather kernel with 16 vectors per lane and one row ahead
+    // wide rows (8 192 < V <= 16 384 fp32): 10-16 vectors per lane and one row ahead.  (half precision: 128 elements per lane — the generic
+    // kernel is faster, 3.6 vs 1.9-2.3 TB/s)
+    const bool wide = vec && esize == 4 && nvec > 8 && nvec <= 16 && S <= 8 * 256;
+    const bool narrow = vec && nvec <= 8 && S <= 8 * 256;
+    if (wide || narrow) {
+        // LDS-gather variant: row image V * sizeof(T) + stage [S][RTg] must leave two workgroups per CU
         int RTg = 16;
-        while (RTg > 1 && (size_t)V * sizeof(T) + (32 + (size_t)S * RTg) * 4 > 78 * 1024) RTg >>= 1;
-        const size_t ldsg = (size_t)V * sizeof(T) + (32 + (size_t)S * RTg) * 4;
+        while (RTg > 1 && (size_t)V * esize + (32 + (size_t)S * RTg) * 4 > 78 * 1024) RTg >>= 1;
+        const size_t ldsg = (size_t)V * esize + (32 + (size_t)S * RTg) * 4;
         if (ldsg <= 78 * 1024 && L >= RTg && (S * RTg) % 4 == 0) {
-            auto kg = nvec <= 10 ? lsg_fwd_regl_kernel<T, 10, false> : nvec <= 12 ? lsg_fwd_regl_kernel<T, 12, false> : nvec <= 14 ? lsg_fwd_regl_kernel<T, 14, false>
-                                                                                                                       : lsg_fwd_regl_kernel<T, 16, false>;
-            const long nt = (long)B * ((L + RTg - 1) / RTg);
-            const int gridg = (int)(nt < 4096 ? nt : 4096);
-            set_max_dynamic_lds((const void*)kg, (int)ldsg);
-            hipLaunchKernelGGL(kg, dim3(gridg), dim3(256), ldsg, st, (T*)logits, idx, isb, isj, iss, match, osb, osj, oss, B, L, V, S, RTg, ws, stats);
-            return check_launch("logsoftmax_gather(reg, LDS gather, wide rows)");
+            p = LsgPlan{wide ? LSG_FWD_REGL_WIDE : LSG_FWD_REGL, 1, lsg_nv(nvec), RTg, lsg_grid(B, L, RTg, 4096), ldsg};
+            return DSP_OK;
         }
     }
-    if (vec && nvec <= 8 && S <= 8 * 256) {
-        auto kr = nvec <= 2 ? lsg_fwd_reg_kernel<T, 2> : (nvec <= 4 ? lsg_fwd_reg_kernel<T, 4> : nvec <= 6 ? lsg_fwd_reg_kernel<T, 6> : lsg_fwd_reg_kernel<T, 8>);
-        {
-            // LDS-gather variant: row image V * sizeof(T) + stage [S][RTg] must leave two workgroups per CU
-            int RTg = 16;
-            while (RTg > 1 && (size_t)V * sizeof(T) + (32 + (size_t)S * RTg) * 4 > 78 * 1024) RTg >>= 1;
-            const size_t ldsg = (size_t)V * sizeof(T) + (32 + (size_t)S * RTg) * 4;
-            if (ldsg <= 78 * 1024 && L >= RTg && (S * RTg) % 4 == 0) {
-                auto kg = nvec <= 2 ? lsg_fwd_regl_kernel<T, 2> : (nvec <= 4 ? lsg_fwd_regl_kernel<T, 4> : nvec <= 6 ? lsg_fwd_regl_kernel<T, 6> : lsg_fwd_regl_kernel<T, 8>);
-                const long nt = (long)B * ((L + RTg - 1) / RTg);
-                const int gridg = (int)(nt < 4096 ? nt : 4096);
-                if (ldsg > 48 * 1024) set_max_dynamic_lds((const void*)kg, (int)ldsg);
-                hipLaunchKernelGGL(kg, dim3(gridg), dim3(256), ldsg, st, (T*)logits, idx, isb, isj, iss, match, osb, osj, oss,
-                                   B, L, V, S, RTg, ws, stats);
-                return check_launch("logsoftmax_gather(reg, LDS gather)");
-            }
-        }
-        int RTr = RT, gridr = grid;
-        // storing the softmax makes the launch a 1:1 read/write stream: two resident workgroups per CU (64 KB of stage per
-        // workgroup at RT = 32) sustain 4.9 TB/s, four only 4.1 TB/s (sweep in tools/k1_bench.py, r01)
-        if (ws && (size_t)S * 32 * 4 <= 96 * 1024 && L >= 32) { RTr = 32; const long nt = (long)B * ((L + 31) / 32); gridr = (int)(nt < 4096 ? nt : 4096); }
-        const size_t ldsr = (32 + (size_t)S * RTr) * sizeof(float);
-        if (ldsr > 48 * 1024) set_max_dynamic_lds((const void*)kr, (int)ldsr);
-        hipLaunchKernelGGL(kr, dim3(gridr), dim3(256), ldsr, st, (T*)logits, idx, isb, isj, iss, match, osb, osj, oss,
-                           B, L, V, S, RTr, ws, stats);
-        return check_launch("logsoftmax_gather(reg)");
+    if (narrow) {       // gathers from global memory: reached only by L below the LDS-gather kernel's row tile (the row image is <= 32 KB here)
+        p = LsgPlan{LSG_FWD_REG, 1, lsg_nv(nvec), RT, lsg_grid(B, L, RT, 2048), (32 + (size_t)S * RT) * sizeof(float)};
+        return DSP_OK;
     }
-    auto k = vec ? lsg_fwd_kernel<T, true> : lsg_fwd_kernel<T, false>;
-    if (lds > 48 * 1024) set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, (T*)logits, idx, isb, isj, iss, match, osb, osj, oss,
-                       B, L, V, S, RT, ws, stats);
-    return check_launch("logsoftmax_gather");
+    p = LsgPlan{LSG_FWD_GENERIC, vec ? 1 : 0, 0, RT, lsg_grid(B, L, RT, 2048), (16 + (size_t)S * RT) * sizeof(float)};
+    return DSP_OK;
+}
+
+static int lsg_plan_bwd(int esize, int B, int L, int V, int S, bool aligned16, LsgPlan& p)
+{
+    const int N = 16 / esize;
+    const bool vec = (V % N == 0) && aligned16;
+    const size_t lds = (16 + (size_t)V) * sizeof(float);
+    if (lds > 160 * 1024) { set_error("logsoftmax_gather_bwd: V=%d exceeds the LDS row image (max ~40k)", V); return DSP_EINVAL; }
+    const int nvec = (V + 256 * N - 1) / (256 * N);
+    if (vec && esize == 4 && nvec > 8 && nvec <= 16) {  // wide rows (8 192 < V <= 16 384 fp32): 10-16 vectors per lane, one row ahead (r05)
+        int RT = 16;
+        while (RT > 1 && (16 + (size_t)V + (size_t)S * RT) * sizeof(float) > 76 * 1024) RT >>= 1;
+        const size_t ldsr = (16 + (size_t)V + (size_t)S * RT) * sizeof(float);
+        if (ldsr <= 76 * 1024 && L >= RT) { p = LsgPlan{LSG_BWD_REG_WIDE, 1, lsg_nv(nvec), RT, lsg_grid(B, L, RT, 4096), ldsr}; return DSP_OK; }
+    }
+    {
+        constexpr int RT = 16;
+        const size_t ldsr = (16 + (size_t)V + (size_t)S * RT) * sizeof(float);
+        if (vec && nvec <= 8 && ldsr <= 76 * 1024 && L >= RT) {     // two workgroups per CU
+            p = LsgPlan{LSG_BWD_REG, 1, lsg_nv(nvec), RT, lsg_grid(B, L, RT, 4096), ldsr};
+            return DSP_OK;
+        }
+    }
+    p = LsgPlan{LSG_BWD_GENERIC, vec ? 1 : 0, 0, 1, lsg_grid(B, L, 1, 2048), lds};      // one row per workgroup trip
+    return DSP_OK;
+}
+
+template <typename T>
+static int launch_fwd(void* logits, const int64_t* idx, int64_t isb, int64_t isj, int64_t iss, float* match,
+                      int64_t osb, int64_t osj, int64_t oss, int B, int L, int V, int S, int ws, hipStream_t st, float* stats = nullptr)
+{
+    LsgPlan p;
+    if (int rc = lsg_plan_fwd((int)sizeof(T), B, L, V, S, (uintptr_t)logits % 16 == 0, p)) return rc;
+    using K = decltype(&lsg_fwd_kernel<T, true>);
+    K k = nullptr;
+    const char* what = "logsoftmax_gather";
+    if (p.family == LSG_FWD_REGL_WIDE) {
+        if constexpr (sizeof(T) == 4)
+            k = p.nv == 10 ? lsg_fwd_regl_kernel<T, 10, false> : p.nv == 12 ? lsg_fwd_regl_kernel<T, 12, false> : p.nv == 14 ? lsg_fwd_regl_kernel<T, 14, false>
+                                                                                                                      : lsg_fwd_regl_kernel<T, 16, false>;
+        what = "logsoftmax_gather(reg, LDS gather, wide rows)";
+    } else if (p.family == LSG_FWD_REGL) {
+        k = p.nv == 2 ? lsg_fwd_regl_kernel<T, 2> : (p.nv == 4 ? lsg_fwd_regl_kernel<T, 4> : p.nv == 6 ? lsg_fwd_regl_kernel<T, 6> : lsg_fwd_regl_kernel<T, 8>);
+        what = "logsoftmax_gather(reg, LDS gather)";
+    } else if (p.family == LSG_FWD_REG) {
+        k = p.nv == 2 ? lsg_fwd_reg_kernel<T, 2> : (p.nv == 4 ? lsg_fwd_reg_kernel<T, 4> : p.nv == 6 ? lsg_fwd_reg_kernel<T, 6> : lsg_fwd_reg_kernel<T, 8>);
+        what = "logsoftmax_gather(reg)";
+    } else {
+        k = p.vec ? lsg_fwd_kernel<T, true> : lsg_fwd_kernel<T, false>;
+    }
+    if (!k) { set_error("logsoftmax_gather: no kernel for the planned instance"); return DSP_EINVAL; }
+    if (p.lds > 48 * 1024 || p.family == LSG_FWD_REGL_WIDE) set_max_dynamic_lds((const void*)k, (int)p.lds);
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(256), p.lds, st, (T*)logits, idx, isb, isj, iss, match, osb, osj, oss, B, L, V, S, p.rt, ws, stats);
+    return check_launch(what);
 }
 
 template <typename T, bool LAZY>
 static int launch_bwd(void* sm, const int64_t* idx, int64_t isb, int64_t isj, int64_t iss, const float* g,
                       int64_t gsb, int64_t gsj, int64_t gss, int B, int L, int V, int S, hipStream_t st, const float* stats)
 {
-    constexpr int N = Vec<T>::N;
-    const bool vec = (V % N == 0) && ((uintptr_t)sm % 16 == 0);
-    const size_t lds = (16 + (size_t)V) * sizeof(float);
-    if (lds > 160 * 1024) { set_error("logsoftmax_gather_bwd: V=%d exceeds the LDS row image (max ~40k)", V); return DSP_EINVAL; }
-    const long nrows = (long)B * L;
-    const int nvec = (V + 256 * N - 1) / (256 * N);
-    if (vec && sizeof(T) == 4 && nvec > 8 && nvec <= 16) {  // wide rows (8 192 < V <= 16 384 fp32): 10-16 vectors per lane, one row ahead (r05)
-        int RT = 16;
-        while (RT > 1 && (16 + (size_t)V + (size_t)S * RT) * sizeof(float) > 76 * 1024) RT >>= 1;
-        const size_t ldsr = (16 + (size_t)V + (size_t)S * RT) * sizeof(float);
-        if (ldsr <= 76 * 1024 && L >= RT) {
-            auto kr = nvec <= 10 ? lsg_bwd_reg_kernel<T, 10, LAZY, 3, false> : nvec <= 12 ? lsg_bwd_reg_kernel<T, 12, LAZY, 3, false>
-                    : nvec <= 14 ? lsg_bwd_reg_kernel<T, 14, LAZY, 3, false> : lsg_bwd_reg_kernel<T, 16, LAZY, 3, false>;
-            const long nt = (long)B * ((L + RT - 1) / RT);
-            const int gridr = (int)(nt < 4096 ? nt : 4096);
-            set_max_dynamic_lds((const void*)kr, (int)ldsr);
-            hipLaunchKernelGGL(kr, dim3(gridr), dim3(256), ldsr, st, (T*)sm, idx, isb, isj, iss, g, gsb, gsj, gss, B, L, V, S, RT, stats);
-            return check_launch("logsoftmax_gather_bwd(reg, wide rows)");
-        }
+    LsgPlan p;
+    if (int rc = lsg_plan_bwd((int)sizeof(T), B, L, V, S, (uintptr_t)sm % 16 == 0, p)) return rc;
+    if (p.family == LSG_BWD_GENERIC) {
+        auto k = p.vec ? lsg_bwd_kernel<T, true, LAZY> : lsg_bwd_kernel<T, false, LAZY>;
+        if (p.lds > 48 * 1024) set_max_dynamic_lds((const void*)k, (int)p.lds);
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(256), p.lds, st, (T*)sm, idx, isb, isj, iss, g, gsb, gsj, gss, B, L, V, S, stats);
+        return check_launch("logsoftmax_gather_bwd");
     }
-    {
-        constexpr int RT = 16;
-        const size_t ldsr = (16 + (size_t)V + (size_t)S * RT) * sizeof(float);
-        if (vec && nvec <= 8 && ldsr <= 76 * 1024 && L >= RT) {     // two workgroups per CU
-            auto kr = nvec <= 2 ? lsg_bwd_reg_kernel<T, 2, LAZY> : (nvec <= 4 ? lsg_bwd_reg_kernel<T, 4, LAZY> : nvec <= 6 ? lsg_bwd_reg_kernel<T, 6, LAZY> : lsg_bwd_reg_kernel<T, 8, LAZY>);
-            const long nt = (long)B * ((L + RT - 1) / RT);
-            const int gridr = (int)(nt < 4096 ? nt : 4096);
-            if (ldsr > 48 * 1024) set_max_dynamic_lds((const void*)kr, (int)ldsr);
-            hipLaunchKernelGGL(kr, dim3(gridr), dim3(256), ldsr, st, (T*)sm, idx, isb, isj, iss, g, gsb, gsj, gss, B, L, V, S, RT, stats);
-            return check_launch("logsoftmax_gather_bwd(reg)");
-        }
+    using K = decltype(&lsg_bwd_reg_kernel<T, 2, LAZY>);
+    K kr = nullptr;
+    if (p.family == LSG_BWD_REG_WIDE) {
+        if constexpr (sizeof(T) == 4)
+            kr = p.nv == 10 ? lsg_bwd_reg_kernel<T, 10, LAZY, 3, false> : p.nv == 12 ? lsg_bwd_reg_kernel<T, 12, LAZY, 3, false>
+               : p.nv == 14 ? lsg_bwd_reg_kernel<T, 14, LAZY, 3, false> : lsg_bwd_reg_kernel<T, 16, LAZY, 3, false>;
+    } else {
+        kr = p.nv == 2 ? lsg_bwd_reg_kernel<T, 2, LAZY> : (p.nv == 4 ? lsg_bwd_reg_kernel<T, 4, LAZY> : p.nv == 6 ? lsg_bwd_reg_kernel<T, 6, LAZY> : lsg_bwd_reg_kernel<T, 8, LAZY>);
     }
-    const int grid = (int)(nrows < 2048 ? nrows : 2048);
-    auto k = vec ? lsg_bwd_kernel<T, true, LAZY> : lsg_bwd_kernel<T, false, LAZY>;
-    if (lds > 48 * 1024) set_max_dynamic_lds((const void*)k, (int)lds);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, (T*)sm, idx, isb, isj, iss, g, gsb, gsj, gss, B, L, V, S, stats);
-    return check_launch("logsoftmax_gather_bwd");
+    if (!kr) { set_error("logsoftmax_gather_bwd: no kernel for the planned instance"); return DSP_EINVAL; }
+    if (p.lds > 48 * 1024 || p.family == LSG_BWD_REG_WIDE) set_max_dynamic_lds((const void*)kr, (int)p.lds);
+    hipLaunchKernelGGL(kr, dim3(p.grid), dim3(256), p.lds, st, (T*)sm, idx, isb, isj, iss, g, gsb, gsj, gss, B, L, V, S, p.rt, stats);
+    return check_launch(p.family == LSG_BWD_REG_WIDE ? "logsoftmax_gather_bwd(reg, wide rows)" : "logsoftmax_gather_bwd(reg)");
 }
 
 }  // namespace dsp
@@ -812,4 +827,28 @@ extern "C" int dsp_logsoftmax_gather_bwd_lazy(void* logits_inout, int dtype, con
     }
     set_error("logsoftmax_gather_bwd_lazy: unsupported dtype code %d", dtype);
     return DSP_EINVAL;
+}
+
+// Which instance a launch of the four entry points above would run: host arithmetic only, no device call.
+//   backward 0: dsp_logsoftmax_gather / _stats, 1: dsp_logsoftmax_gather_bwd / _bwd_lazy;  aligned16: the [B,L,V] buffer starts on a 16-byte boundary
+//   out[0] family (0 forward generic, 1 forward registers, 2 forward registers + LDS gather, 3 the same for wide rows, 4 backward generic,
+//          5 backward registers, 6 backward registers for wide rows; -1: B or L is 0, nothing is launched)
+//   out[1] 16-byte vector accesses (1) or peeled scalar head / tail (0);  out[2] vectors per lane NV (0: generic);  out[3] rows per tile;
+//   out[4] workgroups;  out[5] dynamic LDS bytes.
+// write_softmax and lazy select the forward's mode and the backward's LAZY instantiation; neither changes the family or its tiling.
+extern "C" int dsp_logsoftmax_gather_plan(int backward, int dtype, int B, int L, int V, int S, int aligned16, int write_softmax, int lazy, int* out)
+{
+    using namespace dsp;
+    (void)write_softmax; (void)lazy;
+    if (!out) { set_error("logsoftmax_gather_plan: null pointer"); return DSP_EINVAL; }
+    if (B < 0 || L < 0 || V <= 0 || S < 0) { set_error("logsoftmax_gather_plan: bad sizes B=%d L=%d V=%d S=%d", B, L, V, S); return DSP_EINVAL; }
+    if (dtype != DSP_F32 && dtype != DSP_F16 && dtype != DSP_BF16) { set_error("logsoftmax_gather_plan: unsupported dtype code %d", dtype); return DSP_EINVAL; }
+    out[0] = -1; out[1] = out[2] = out[3] = out[4] = out[5] = 0;
+    if (B == 0 || L == 0) return DSP_OK;
+    LsgPlan p;
+    const int esize = dtype == DSP_F32 ? 4 : 2;
+    const int rc = backward ? lsg_plan_bwd(esize, B, L, V, S, aligned16 != 0, p) : lsg_plan_fwd(esize, B, L, V, S, aligned16 != 0, p);
+    if (rc) return rc;
+    out[0] = p.family; out[1] = p.vec; out[2] = p.nv; out[3] = p.rt; out[4] = p.grid; out[5] = (int)p.lds;
+    return DSP_OK;
 }

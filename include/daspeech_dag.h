@@ -78,6 +78,20 @@ int dsp_logsoftmax_gather_bwd_lazy(void* logits_inout, int dtype,
                                    const float* g, int64_t g_sb, int64_t g_sj, int64_t g_ss,
                                    const float* row_stats, int B, int L, int V, int S, dsp_stream_t stream);
 
+/* Which kernel instance the four K1 entry points above would launch for a shape: host arithmetic only, no device call (the launchers ask
+ *   the same function).  backward: 0 = dsp_logsoftmax_gather / _stats, 1 = dsp_logsoftmax_gather_bwd / _bwd_lazy.  aligned16: the [B,L,V]
+ *   buffer starts on a 16-byte boundary.  write_softmax / lazy name the forward's mode and the backward's instantiation; neither changes the
+ *   family or its tiling.
+ *   out[0]  family: 0 forward generic, 1 forward register-resident, 2 forward register-resident with the gather from LDS, 3 the same for wide
+ *           rows (one row ahead), 4 backward generic (a row per workgroup trip), 5 backward register-resident, 6 the same for wide rows;
+ *           -1 when B or L is 0 (nothing is launched)
+ *   out[1]  1: 16-byte vector accesses over the whole row, 0: scalar head / tail around an aligned body
+ *   out[2]  16-byte vectors per lane of the register-resident instance (2, 4, 6, 8; wide rows 10, 12, 14, 16), 0 for the generic kernels
+ *   out[3]  rows per tile;  out[4] workgroups;  out[5] dynamic LDS bytes.
+ *   Returns DSP_EINVAL exactly where the launch would (forward: S beyond the LDS staging; backward: V beyond the LDS row image). */
+int dsp_logsoftmax_gather_plan(int backward, int dtype, int B, int L, int V, int S,
+                               int aligned16, int write_softmax, int lazy, int out[6]);
+
 /* K1 and its backward in DOUBLE precision (csrc/logsoftmax_gather_f64.hip) — the reference dispatches its gather for double as well
  *   (logsoftmax_gather.cu:46-58,340-347: `selected_result` is at::kDouble).  Every intermediate is a double, accurate exp / log only.
  *   logits    [B,L,V] contiguous doubles (8-byte aligned; rows of an odd V are served with 16-byte loads after one peeled element).
