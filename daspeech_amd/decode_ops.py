@@ -21,9 +21,16 @@ Host-side mirror of the reference code these replace:
                       under autograd on the channels-last tensor (csrc/conformer_train.hip): fp32 / fp16 / bf16, batch statistics and the
                       running-buffer update, a backward whose reductions run in a fixed order without float atomics; ConformerLayer keeps
                       its torch lines where dwconv_bn_silu_autograd_served says no (set_conv_module_hip(False): always)
+  residual_dropout_layer_norm_autograd   the residual sites of the layers in TRAINING mode, s = residual + alpha * dropout(h [+ bias]); y = LayerNorm(s)
+                      (fairseq conformer_layer.py:254-281, transformer_layer.py:467-511, fastspeech2.py:42-95), under autograd
+                      (csrc/residual_norm_train.hip): fp32 / fp16 / bf16, the mask recomputed from a Philox counter keyed by the default CUDA
+                      generator, column sums in a fixed order without float atomics; ConformerLayer / NATDecoderLayer / FFTLayer keep their
+                      torch lines where residual_dropout_layer_norm_served says no (set_residual_norm_hip(False): always);
+                      residual_dropout_layer_norm_checked / _sites_served are internal to those layers (no argument checks: not an API)
 No CPU fallback elsewhere: GPU tensors only.
 """
 import ctypes
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -1027,6 +1034,247 @@ def dwconv_bn_silu_autograd(x: Tensor, conv_weight: Tensor, bn: "torch.nn.BatchN
     if track and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return y
+
+
+# ------------------------------------------------------------------------------------------------ residual + dropout + LayerNorm under autograd (csrc/residual_norm_train.hip)
+RESIDUAL_NORM_HIP = True     # set_residual_norm_hip(False): the layers keep their torch lines in training on every input
+RESNORM_CHUNK_ROWS = 32      # DSP_RESNORM_CHUNK_ROWS: rows per reduction chunk of the backward (one workspace partial each)
+RESNORM_MAX_C = 2048
+
+
+def set_residual_norm_hip(on: bool) -> bool:
+    """Switch the HIP residual + dropout + LayerNorm operator of the training branches (ConformerLayer, NATDecoderLayer, FastSpeech2 FFTLayer)
+    on or off; returns the previous setting.  Off: residual_dropout_layer_norm_served answers False and the torch lines run."""
+    global RESIDUAL_NORM_HIP
+    old, RESIDUAL_NORM_HIP = RESIDUAL_NORM_HIP, bool(on)
+    return old
+
+
+def dropout_threshold(p: float) -> int:
+    """thr = ceil(p * 2^24), in double: an element is kept when the top 24 bits of its Philox word are >= thr (p = 0: 0, everything kept)"""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability has to be in [0, 1), got {p}")
+    return min(int(math.ceil(float(p) * 16777216.0)), 1 << 24)
+
+
+def _reserve_dropout_stream(device) -> Tuple[int, int]:
+    """(seed, offset) of the default CUDA generator of `device` for one masked call, and the generator's offset moved on by 4 (torch's own
+    kernels keep it a multiple of 4).  Host operations only: no launch, no sync.  The same generator state gives the same pair, so
+    torch.cuda.manual_seed / set_rng_state reproduce and restore the masks."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[idx]
+    seed, offset = int(gen.initial_seed()), int(gen.get_offset())
+    gen.set_offset(offset + 4)
+    return seed & 0xFFFFFFFFFFFFFFFF, offset
+
+
+def dropout_keep_mask(seed: int, offset: int, p: float, shape, device) -> Tensor:
+    """The keep mask (bool, `shape`) that residual_dropout_layer_norm_autograd applies for (seed, offset, p) to a contiguous tensor of that
+    shape (dsp_dropout_keep_mask): for tests and diagnostics — the operator itself stores no mask."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("dropout_keep_mask: expected a GPU device (HIP op, no CPU path)")
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        out = torch.empty(tuple(shape), dtype=torch.uint8, device=device)
+        _lib.check(lib.dsp_dropout_keep_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), dropout_threshold(p), _lib.ptr(out), out.numel(),
+                                             _lib.current_stream_handle()), "dsp_dropout_keep_mask")
+    return out.view(torch.bool)
+
+
+def _resnorm_params_ok(x, ln, bias) -> bool:
+    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
+    if w is None or b is None or tuple(ln.normalized_shape) != (x.shape[-1],):
+        return False
+    ts = [w, b] + ([] if bias is None else [bias])
+    return (all(t.device == x.device and tuple(t.shape) == (x.shape[-1],) for t in ts)
+            and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts)))
+
+
+def _resnorm_shape_ok(x) -> bool:
+    C = x.shape[-1] if x.dim() >= 1 else 0
+    return x.dim() >= 2 and C >= 1 and C % (16 // x.element_size()) == 0 and C <= RESNORM_MAX_C and 1 <= x.numel() // C <= (1 << 24)
+
+
+def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln: "torch.nn.LayerNorm", *, bias: Optional[Tensor] = None) -> bool:
+    """True when residual_dropout_layer_norm_autograd serves a training branch on these arguments: the switch is on, autocast off, residual
+    (and h, when given: same shape, dtype and device) a contiguous GPU tensor [..., C] in fp32 / fp16 / bf16 with C a multiple of the elements
+    in 16 bytes, C <= 2048 and at most 2^24 rows, ln an affine LayerNorm(C) whose weight and bias (and `bias`) are in that dtype or all in
+    fp32, and the current stream not capturing a graph (the random offset is reserved on the host).  Everything else keeps the torch lines."""
+    if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
+        return False
+    x = residual
+    if not (x.is_cuda and x.is_contiguous() and str(x.dtype) in _lib.DTYPE_CODES and _resnorm_shape_ok(x)):
+        return False
+    if h is not None and not (h.is_cuda and h.is_contiguous() and h.dtype == x.dtype and h.shape == x.shape and h.device == x.device):
+        return False
+    if not _resnorm_params_ok(x, ln, bias if h is not None else None):
+        return False
+    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
+    """residual_dropout_layer_norm_served(x, x, ln, bias=bias) for every (ln, bias) of `sites` — the residual sites of ONE layer, whose block
+    outputs have the shape, dtype and device of the layer input x — with the questions about x, the switch, autocast and the stream asked
+    once: a layer asks this once per forward, and the step follows the host time of these sites."""
+    if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
+        return False
+    dt = x.dtype
+    if not (x.is_cuda and dt in _RN_CODES and x.is_contiguous() and _resnorm_shape_ok(x)):
+        return False
+    C, dev, f32 = x.shape[-1], x.device, torch.float32
+    for ln, bias in sites:
+        w, b = ln.weight, ln.bias
+        if w is None or b is None or len(ln.normalized_shape) != 1 or ln.normalized_shape[0] != C:
+            return False
+        pd = w.dtype
+        if (pd != dt and pd != f32) or b.dtype != pd or w.device != dev or b.device != dev:
+            return False
+        if bias is not None and (bias.dtype != pd or bias.device != dev or bias.dim() != 1 or bias.shape[0] != C):
+            return False
+    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+_RN_CODES ={torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # _lib.DTYPE_CODES by dtype object: no str() on the per-site path
+
+
+def _rn_launch_ctx(dev):
+    """(device index of dev, whether dev has to be made current first).  The residual sites are ~100 calls a training step and the step is
+    launch bound: the raw stream handle instead of a Stream object, and no device guard when the device is the current one already."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    return idx, idx != torch.cuda.current_device()
+
+
+class _ResidualNormTrainFn(torch.autograd.Function):
+    """dsp_resnorm_train_fwd / _bwd.  Saved for the backward: s (an output; the residual itself when h is None), the fp32 row statistics and
+    gamma — no mask: the backward draws it again from (seed, offset, thr)."""
+
+    @staticmethod
+    def forward(ctx, h, residual, bias, gamma, beta, eps, alpha, p, seed, offset):
+        C = residual.shape[-1]
+        R = residual.numel() // C
+        has_h = h is not None
+        has_bias = has_h and bias is not None
+        thr = dropout_threshold(p) if (has_h and p > 0.0) else 0
+        scale = 1.0 / (1.0 - p) if thr else 1.0
+        lib = _lib.load()
+        dev = residual.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            y = torch.empty_like(residual)
+            s = torch.empty_like(residual) if has_h else None
+            stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
+            rc = lib.dsp_resnorm_train_fwd(h.data_ptr() if has_h else None, residual.data_ptr(), bias.data_ptr() if has_bias else None,
+                                           gamma.data_ptr(), beta.data_ptr(), eps, alpha, scale, thr, seed, offset,
+                                           s.data_ptr() if has_h else None, y.data_ptr(), stats.data_ptr(), _RN_CODES[residual.dtype],
+                                           _RN_CODES[gamma.dtype], R, C, torch._C._cuda_getCurrentRawStream(idx))
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_resnorm_train_fwd")
+        ctx.save_for_backward(s if has_h else residual, stats, gamma)
+        ctx.call = (alpha, scale, thr, seed, offset, has_h, has_bias)
+        ctx.set_materialize_grads(False)
+        if has_h:
+            return s, y
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        s, stats, g = ctx.saved_tensors
+        alpha, scale, thr, seed, offset, has_h, has_bias = ctx.call
+        ds, dy = grads if has_h else (None, grads[0])
+        need = ctx.needs_input_grad
+        if ds is None and dy is None:
+            return (None,) * 10
+        C = s.shape[-1]
+        R = s.numel() // C
+        if ds is not None and not ds.is_contiguous():
+            ds = ds.contiguous()
+        if dy is not None and not dy.is_contiguous():
+            dy = dy.contiguous()
+        lib = _lib.load()
+        dev = s.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            want_dh, want_dres = has_h and need[0], need[1]
+            shared = want_dh and want_dres and thr == 0 and alpha == 1.0      # dh equals dresidual: one tensor for both
+            dres = torch.empty_like(s) if want_dres else None
+            dh = torch.empty_like(s) if (want_dh and not shared) else None
+            dbias = torch.empty_like(g) if (has_bias and need[2]) else None
+            dgamma = torch.empty_like(g) if need[3] else None
+            dbeta = torch.empty_like(g) if need[4] else None
+            if dy is None:                                                 # y was not used: its parameters get zeros, not stale memory
+                for t in (dgamma, dbeta):
+                    if t is not None:
+                        t.zero_()
+            kg, kb = (dgamma, dbeta) if dy is not None else (None, None)
+            sums = kg is not None or kb is not None or dbias is not None
+            nbytes = int(lib.dsp_resnorm_train_workspace_bytes(R, C)) if sums else 0
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+            rc = 0
+            if dh is not None or dres is not None or sums:
+                ptr = lambda t: None if t is None else t.data_ptr()
+                rc = lib.dsp_resnorm_train_bwd(ptr(dy), ptr(ds), s.data_ptr(), stats.data_ptr(), g.data_ptr(), alpha, scale, thr, seed, offset,
+                                               ptr(dh), ptr(dres), ptr(dbias), ptr(kg), ptr(kb), ptr(ws), nbytes, _RN_CODES[s.dtype],
+                                               _RN_CODES[g.dtype], R, C, torch._C._cuda_getCurrentRawStream(idx))
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_resnorm_train_bwd")
+        return (dres if shared else dh), dres, dbias, dgamma, dbeta, None, None, None, None, None
+
+
+def residual_dropout_layer_norm_checked(h, residual, ln, bias=None, alpha=1.0, p=0.0, training=True, return_sum=True):
+    """INTERNAL to the package's layers: residual_dropout_layer_norm_autograd WITHOUT its argument checks, valid only on arguments that
+    residual_dropout_layer_norm_served / _sites_served accepted (~100 sites a training step, and the step is launch bound).  The kernels
+    trust what they are handed: any other caller uses residual_dropout_layer_norm_autograd."""
+    if h is None:
+        return _ResidualNormTrainFn.apply(None, residual, None, ln.weight, ln.bias, ln.eps, 1.0, 0.0, 0, 0)
+    if not h.is_contiguous():                  # the served rule looked at the residual; a block's output is contiguous, a view of it is copied
+        h = h.contiguous()
+    p_eff = float(p) if training else 0.0
+    seed, offset = _reserve_dropout_stream(residual.device) if p_eff > 0.0 else (0, 0)
+    out = _ResidualNormTrainFn.apply(h, residual, bias, ln.weight, ln.bias, ln.eps, float(alpha), p_eff, seed, offset)
+    return out if return_sum else out[1]
+
+
+def residual_dropout_layer_norm_autograd(h: Optional[Tensor], residual: Tensor, ln: "torch.nn.LayerNorm", *, bias: Optional[Tensor] = None,
+                                         alpha: float = 1.0, p: float = 0.0, training: bool = True, return_sum: bool = True):
+    """s = residual + alpha * dropout(h [+ bias], p);  y = ln(s)  — differentiable w.r.t. h, residual, bias, ln.weight and ln.bias
+    (include/daspeech_decode.h: dsp_resnorm_train_fwd / _bwd).  Returns (s, y), or y alone with return_sum=False or h None (a plain
+    LayerNorm under autograd: s would be the residual itself).  The LayerNorm sees s as stored (rounded to the dtype), as torch's does.
+    Dropout is active with `training and p > 0`: the mask comes from a counter-based Philox stream keyed by the default CUDA generator of the
+    tensors' device (seed, offset), whose offset such a call advances by 4 — the same generator state gives the same mask, successive calls
+    differ, torch.cuda.set_rng_state restores the stream; calls with p = 0 do not touch the generator.  The masks are not torch's F.dropout
+    masks.  fp32 / fp16 / bf16 (float64 is refused, never narrowed); ln.weight, ln.bias and bias in the dtype of the data or all in fp32.
+    Bit-reproducible forward and backward."""
+    name = "residual_dropout_layer_norm_autograd"
+    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
+    data = [residual] + ([] if h is None else [h])
+    params = [t for t in (w, b, bias if h is not None else None) if t is not None]
+    if (str(residual.dtype) not in _lib.DTYPE_CODES or any(t.dtype != residual.dtype for t in data) or w is None or b is None
+            or not (all(t.dtype == residual.dtype for t in params) or all(t.dtype == torch.float32 for t in params))):
+        raise RuntimeError(f"{name}: expected GPU tensors with h and residual in one of fp32 / fp16 / bf16 and an affine LayerNorm whose weight and "
+                           f"bias (and `bias`) are in that dtype or all in fp32, got {[str(t.dtype) for t in data]} and "
+                           f"{[str(t.dtype) for t in params]}")
+    _gpu(name, *data, *params)
+    if (not _resnorm_shape_ok(residual) or (h is not None and h.shape != residual.shape) or tuple(ln.normalized_shape) != (residual.shape[-1],)
+            or any(tuple(t.shape) != (residual.shape[-1],) for t in params) or any(t.device != residual.device for t in params + data)
+            or not 0.0 <= p < 1.0):
+        raise RuntimeError(f"{name}: residual {tuple(residual.shape)} / h {None if h is None else tuple(h.shape)} / LayerNorm "
+                           f"{tuple(ln.normalized_shape)} / p {p} are not served ([..., C] with C a multiple of the elements in 16 bytes, "
+                           f"C <= {RESNORM_MAX_C}, 1 <= rows <= 2^24, h of the shape of residual, LayerNorm(C), 0 <= p < 1)")
+    return residual_dropout_layer_norm_checked(None if h is None else h.contiguous(), residual.contiguous(), ln, bias, alpha, p, training, return_sum)
 
 
 class SplitConv1d:

@@ -224,11 +224,39 @@ class ConformerLayer(nn.Module):
         L_ = decode_ops.linear                 # fp32-accurate split GEMMs (bias, SiLU, scale and residual in their epilogues) in eval-mode
         return L_(L_(decode_ops.layer_norm(x, m["layer_norm"]), m["w_1"], act="silu"), m["w_2"], residual=x, alpha=0.5)      # fp32 inference, torch otherwise
 
+    def _resnorm_served(self, x):
+        """one question per forward for the four wired sites (their LayerNorm and the bias that rides in the operator)"""
+        return decode_ops.residual_dropout_layer_norm_sites_served(x, (
+            (self.self_attn_layer_norm, self.ffn1["w_2"].bias), (self.conv_module["layer_norm"], None), (self.ffn2["layer_norm"], None),
+            (self.final_layer_norm, self.ffn2["w_2"].bias)))
+
+    def _forward_train_resnorm(self, x, pos, pad_mask):
+        """The training branch with every `x = x + alpha * dropout(block(LayerNorm(x)))` boundary as one HIP operator (csrc/residual_norm_train.hip):
+        the residual add, the dropout and the NEXT block's LayerNorm in one pass that returns both the sum and its norm; the bias of each
+        w_2 rides in the operator, so that Linear runs without it and its bias gradient is one of the operator's column sums."""
+        c, p, tr = self.conv_module, self.p, self.training
+        rn = decode_ops.residual_dropout_layer_norm_checked
+
+        def ffn(m, y):                              # conformer_layer.py:140-146 up to w_2's product: dropout1 after the activation
+            return F.linear(_drop(F.silu(m["w_1"](y)), p, tr), m["w_2"].weight)
+        y = self.ffn1["layer_norm"](x)             # a LayerNorm alone: the operator's h = None form is slower than torch's here (DESIGN §8)
+        x, y = rn(ffn(self.ffn1, y), x, self.self_attn_layer_norm, bias=self.ffn1["w_2"].bias, alpha=0.5, p=p, training=tr)
+        x, y = rn(self.self_attn(y, pos, pad_mask), x, c["layer_norm"], p=p, training=tr)                 # :267
+        y = F.glu(F.linear(y, c["pointwise_conv1"].weight.squeeze(-1)), dim=-1)
+        if decode_ops.dwconv_bn_silu_autograd_served(y, c["depthwise_conv"], c["batch_norm"]):
+            y = decode_ops.dwconv_bn_silu_autograd(y, c["depthwise_conv"].weight, c["batch_norm"])
+        else:
+            y = F.silu(c["batch_norm"](c["depthwise_conv"](y.transpose(1, 2)))).transpose(1, 2)
+        x, y = rn(F.linear(y, c["pointwise_conv2"].weight.squeeze(-1)), x, self.ffn2["layer_norm"], p=p, training=tr)      # :100
+        return rn(ffn(self.ffn2, y), x, self.final_layer_norm, bias=self.ffn2["w_2"].bias, alpha=0.5, p=p, training=tr, return_sum=False)
+
     def forward(self, x, pos, pad_mask):
         c = self.conv_module
         if self.training or torch.is_grad_enabled():
-            # training: plain torch ops only (the step is host-launch bound: every helper indirection and extra view costs)
             p, tr = self.p, self.training
+            if self._resnorm_served(x):                # the block boundaries as HIP operators (GPU, fp32 / fp16 / bf16, no autocast)
+                return self._forward_train_resnorm(x, pos, pad_mask)
+            # otherwise plain torch ops only (the step is host-launch bound: every helper indirection and extra view costs)
 
             def ffn(m, x):                          # conformer_layer.py:140-146: dropout1 after the activation, dropout2 after w_2
                 return x + 0.5 * _drop(m["w_2"](_drop(F.silu(m["w_1"](m["layer_norm"](x))), p, tr)), p, tr)
@@ -339,6 +367,14 @@ class NATDecoderLayer(nn.Module):
     def forward(self, x, self_pad, enc, enc_pad, lens=None, enc_lens=None):
         if self.training or torch.is_grad_enabled():
             p, tr = self.p, self.training                                                 # transformer_layer.py:467,497,507,511
+            rn = decode_ops.residual_dropout_layer_norm_checked
+            if decode_ops.residual_dropout_layer_norm_sites_served(x, ((self.self_attn_layer_norm, None), (self.encoder_attn_layer_norm, None),
+                                                                       (self.final_layer_norm, self.fc2.bias))):
+                # each post-norm site (residual add, dropout, LayerNorm) as one HIP operator (csrc/residual_norm_train.hip); fc2's bias rides in it
+                x = rn(self.self_attn(x, x, self_pad), x, self.self_attn_layer_norm, p=p, training=tr, return_sum=False)
+                x = rn(self.encoder_attn(x, enc, enc_pad), x, self.encoder_attn_layer_norm, p=p, training=tr, return_sum=False)
+                h = F.linear(_drop(F.gelu(self.fc1(x)), self.p_act, tr), self.fc2.weight)
+                return rn(h, x, self.final_layer_norm, bias=self.fc2.bias, p=p, training=tr, return_sum=False)
             x = self.self_attn_layer_norm(x + _drop(self.self_attn(x, x, self_pad), p, tr))
             x = self.encoder_attn_layer_norm(x + _drop(self.encoder_attn(x, enc, enc_pad), p, tr))
             return self.final_layer_norm(x + _drop(self.fc2(_drop(F.gelu(self.fc1(x)), self.p_act, tr)), p, tr))

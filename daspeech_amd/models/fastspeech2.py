@@ -104,7 +104,12 @@ class _ConvFFN(nn.Module):
             if self._split is not None:
                 return _dops.layer_norm(self._split[1](self._split[0](x, relu=True, lens=lens, slack=slack), residual=x, lens=lens, slack=slack),
                                         self.layer_norm)
-        return self.layer_norm(_drop(self.ffn(x.transpose(1, 2)).transpose(1, 2), self.p, self.training) + x)
+        h = self.ffn(x.transpose(1, 2)).transpose(1, 2)
+        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(None, x, self.layer_norm):
+            # dropout, residual add and LayerNorm as one HIP operator (csrc/residual_norm_train.hip) on the channels-last copy of the
+            # convolution's output; the Conv1d bias stays in the convolution
+            return _dops.residual_dropout_layer_norm_checked(h.contiguous(), x, self.layer_norm, p=self.p, training=self.training, return_sum=False)
+        return self.layer_norm(_drop(h, self.p, self.training) + x)
 
 
 class FFTLayer(nn.Module):
@@ -117,8 +122,13 @@ class FFTLayer(nn.Module):
     def forward(self, x: Tensor, padding_mask: Optional[Tensor] = None, lens: Optional[Tensor] = None, slack: int = 0) -> Tensor:
         """lens [B] int32 + slack (eval-mode inference on the GPU only): rows from lens[b] + slack on are padding that no valid frame of
         the model's output depends on; the matrix-core kernels skip their tiles and return zeros there."""
-        from ..decode_ops import layer_norm as _ln
-        x = _ln(self.self_attn(x, padding_mask, lens, slack, residual=x), self.layer_norm)
+        from .. import decode_ops as _dops
+        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(x, x, self.layer_norm):
+            # residual add and LayerNorm (no dropout at this site) as one HIP operator under autograd (csrc/residual_norm_train.hip)
+            x = _dops.residual_dropout_layer_norm_checked(self.self_attn(x, padding_mask, lens, slack), x, self.layer_norm,
+                                                         training=self.training, return_sum=False)
+        else:
+            x = _dops.layer_norm(self.self_attn(x, padding_mask, lens, slack, residual=x), self.layer_norm)
         return self.ffn(x, lens, slack)
 
 

@@ -270,6 +270,40 @@ int dsp_dwconv_bn_silu_train_bwd(const void* x, const void* w, const void* gamma
                                  void* workspace, size_t workspace_bytes, int act_dtype, int bn_dtype, int B, int T, int C, int K,
                                  dsp_stream_t stream);
 
+/* Residual + dropout + LayerNorm under autograd (csrc/residual_norm_train.hip): the residual sites of the training step,
+ *     s = residual + alpha * dropout(h [+ bias]);   y = LayerNorm(s)
+ *   on contiguous channels-last tensors of R rows (the product of the leading dimensions) and C columns.  Per row, in fp32:
+ *     z = h + bias (bias may be NULL);  d = keep ? z * keep_scale : 0;  s = residual + alpha * d, ROUNDED to the data dtype and written;
+ *     mean and rstd = 1/sqrt(var + eps) (biased variance) of the rounded s — what a LayerNorm applied to the stored s sees, and what lets the
+ *     backward rebuild xhat = (s - mean) * rstd from the saved s;  y = gamma * xhat + beta;  stats[r] = (mean, rstd), fp32 [R,2].
+ *   h == NULL: s = residual, nothing is written to `s` (may be NULL), the call is a plain LayerNorm under autograd (the first norm of a block).
+ *   The mask is counter-based and never stored: with e = r*C + c, the four words of Philox4x32-10 with key (seed lo, seed hi) and counter
+ *   (g lo, g hi, offset lo, offset hi), g = e >> 2, serve elements 4g .. 4g+3 in order, and keep <=> (word >> 8) >= thr, where the caller
+ *   computes thr = ceil(p * 2^24) in double and keep_scale = 1/(1-p).  thr == 0: no dropout — no mask path at all, keep_scale is not read.
+ *   dsp_dropout_keep_mask writes the same mask of n elements as bytes (1 = keep), for tests and diagnostics.
+ *   backward from dy and / or ds (either may be NULL: that output was not used; without dy neither s, stats nor gamma is read and they may be
+ *   NULL too, dgamma and dbeta are then zeros) with the saved s and stats and the same
+ *   (alpha, keep_scale, thr, seed, offset):   dxhat = dy * gamma;   g = ds + rstd * (dxhat - mean_c(dxhat) - xhat * mean_c(dxhat * xhat));
+ *     dresidual = g;  dh = alpha * keep * keep_scale * g;  dgamma = sum_r dy * xhat;  dbeta = sum_r dy;  dbias = sum_r dh (before rounding).
+ *   h, residual, s, y, dy, ds, dh, dresidual share the dtype code act_dtype (DSP_F32 / DSP_F16 / DSP_BF16); gamma, beta, bias, dgamma, dbeta,
+ *   dbias [C] share param_dtype (act_dtype, or DSP_F32).  All 16-byte aligned, C a multiple of the elements in 16 bytes (4 or 8), C <= 2048,
+ *   R <= 2^24.  EVERY OUTPUT ELEMENT IS WRITTEN.  The column sums are two-stage: one fp32 partial per chunk of DSP_RESNORM_CHUNK_ROWS rows,
+ *   reduced in a fixed order inside one workgroup, then the partials added in ASCENDING chunk order.  NO FLOAT ATOMICS and no hand-off
+ *   between workgroups: the same inputs give the same bits on every call.  Each of dh / dresidual / dbias / dgamma / dbeta may be NULL, and
+ *   leaving one out does not change the bits of the others (dbias without dh is served: with thr == 0 and alpha == 1, dh equals dresidual).
+ *   workspace (backward, needed when a column sum is asked for): dsp_resnorm_train_workspace_bytes(R, C) bytes of device memory, 16-byte
+ *   aligned (DSP_ENOSPC if smaller); host arithmetic only, 0 for an empty problem, monotone in each argument, a multiple of 16.
+ *   Bad sizes, null or aliased pointers, misalignment: DSP_EINVAL before any launch; R == 0: DSP_OK. */
+#define DSP_RESNORM_CHUNK_ROWS 32
+size_t dsp_resnorm_train_workspace_bytes(int64_t R, int C);
+int dsp_resnorm_train_fwd(const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps, float alpha,
+                          float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* s, void* y, float* stats, int act_dtype,
+                          int param_dtype, int64_t R, int C, dsp_stream_t stream);
+int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha, float keep_scale,
+                          unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dresidual, void* dbias, void* dgamma, void* dbeta,
+                          void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream);
+int dsp_dropout_keep_mask(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, dsp_stream_t stream);
+
 /* fp32-accurate Conv1d ("same" padding, stride 1) on the fp16 matrix cores by operand splitting (x = xh + xl/2048, w = wh + wl/2048;
  * the products xh.wh, xh.wl, xl.wh are exact in the fp32 accumulator, the dropped xl.wl term is 2^-22 relative) — for the
  * FastSpeech2 FFT feed-forward convolutions (fairseq fastspeech2.py:42-63), which MIOpen runs at 60-70 TFLOP/s in fp32.
