@@ -16,6 +16,7 @@
 // writes one fp32 partial per column for its chunk of DSP_RESNORM_CHUNK_ROWS rows, and rn_bwd_merge_kernel adds the chunks in ASCENDING
 // order.  No float atomics, no hand-off between workgroups inside a launch: same inputs, same bits.
 #include "common.h"
+#include "philox.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -80,31 +81,6 @@ __device__ __forceinline__ void st_param(void* p, int pdtype, int c, float v)
     if (pdtype == DSP_F32) ((float*)p)[c] = v;
     else if (pdtype == DSP_F16) ((__half*)p)[c] = __float2half(v);
     else ((__hip_bfloat16*)p)[c] = __float2bfloat16(v);
-}
-
-// ---- Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four words
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// keep flags of the V elements from element e on (e a multiple of 4)
-template <int V> __device__ __forceinline__ void keep_flags(uint64_t e, uint64_t seed, uint64_t offset, uint32_t thr, bool (&keep)[V])
-{
-#pragma unroll
-    for (int j = 0; j < V / 4; ++j) {
-        const uint64_t g = (e >> 2) + j;
-        uint32_t w[4];
-        philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) keep[4 * j + i] = (w[i] >> 8) >= thr;
-    }
 }
 
 // sum over the W lanes of a row (W a power of two): a butterfly, every lane gets the same bits

@@ -27,6 +27,12 @@ Host-side mirror of the reference code these replace:
                       generator, column sums in a fixed order without float atomics; ConformerLayer / NATDecoderLayer / FFTLayer keep their
                       torch lines where residual_dropout_layer_norm_served says no (set_residual_norm_hip(False): always);
                       residual_dropout_layer_norm_checked / _sites_served are internal to those layers (no argument checks: not an API)
+  relpos_attention_autograd   fairseq espnet_multihead_attention.py RelPositionMultiHeadedAttention between the projections and linear_out, in
+                      TRAINING mode under autograd (csrc/relpos_attention_train.hip): fp16 / bf16, scores + relative shift + mask + soft-max +
+                      dropout + value product in one launch, a backward that recomputes the probabilities (no [B,h,T,T] tensor is kept) and
+                      sums in a fixed order without float atomics; RelPosSelfAttention keeps its torch lines where
+                      relpos_attention_autograd_served says no (set_relpos_attention_hip(False): always); relpos_attention_checked is
+                      internal to that layer
 No CPU fallback elsewhere: GPU tensors only.
 """
 import ctypes
@@ -1275,6 +1281,171 @@ def residual_dropout_layer_norm_autograd(h: Optional[Tensor], residual: Tensor, 
                            f"{tuple(ln.normalized_shape)} / p {p} are not served ([..., C] with C a multiple of the elements in 16 bytes, "
                            f"C <= {RESNORM_MAX_C}, 1 <= rows <= 2^24, h of the shape of residual, LayerNorm(C), 0 <= p < 1)")
     return residual_dropout_layer_norm_checked(None if h is None else h.contiguous(), residual.contiguous(), ln, bias, alpha, p, training, return_sum)
+
+
+# ------------------------------------------------------------------------------------------------ relative-position attention under autograd (csrc/relpos_attention_train.hip)
+RELPOS_ATTENTION_HIP = True   # set_relpos_attention_hip(False): RelPosSelfAttention keeps its torch lines in training on every input
+RELPOS_TRAIN_MAX_T = 2048     # DSP_RELPOS_TRAIN_MAX_T
+_RA_CODES = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def set_relpos_attention_hip(on: bool) -> bool:
+    """Switch the HIP relative-position attention of RelPosSelfAttention's training branch on or off; returns the previous setting.
+    Off: relpos_attention_autograd_served answers False and the torch lines run."""
+    global RELPOS_ATTENTION_HIP
+    old, RELPOS_ATTENTION_HIP = RELPOS_ATTENTION_HIP, bool(on)
+    return old
+
+
+def _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) -> Optional[str]:
+    """None when dsp_relpos_attention_train_fwd / _bwd take these tensors as they are, else what is in the way"""
+    if not (isinstance(q, Tensor) and q.dim() == 3):
+        return "q has to be a [B,T,C] tensor"
+    B, T, C = q.shape
+    dt, dev = q.dtype, q.device
+    if dt not in _RA_CODES:
+        return f"q, k, v and pos have to be fp16 or bf16, got {dt} (fp32 keeps the torch lines; float64 is refused, never narrowed)"
+    if heads < 1 or C != heads * 64:
+        return f"head width {C // max(heads, 1)}: only 64 is served"
+    if not 1 <= T <= RELPOS_TRAIN_MAX_T:
+        return f"T = {T} outside 1 .. {RELPOS_TRAIN_MAX_T}"
+    if not q.is_cuda:
+        return "expected GPU tensors (HIP op, no CPU path)"
+    ld = q.stride(1)
+    for t in (q, k, v):
+        if (t.shape != q.shape or t.dtype != dt or t.device != dev or t.stride(2) != 1 or t.stride(1) != ld or (B > 1 and t.stride(0) != T * ld)
+                or t.data_ptr() % 16):
+            return "q, k, v need one shape, dtype and device, unit column stride, one common row stride and 16-byte alignment"
+    if ld < C or ld % 8:
+        return f"row stride {ld} of q, k, v has to be a multiple of 8 elements"
+    if pos.dtype != dt or pos.device != dev or pos.numel() != (2 * T - 1) * C or pos.shape[-1] != C and tuple(pos.shape[-2:]) != (heads, 64):
+        return f"pos has to hold the [2T-1, C] projected positions in {dt}"
+    pd = bias_u.dtype
+    if (pd != dt and pd != torch.float32) or bias_v.dtype != pd or bias_u.device != dev or bias_v.device != dev \
+            or tuple(bias_u.shape) != (heads, 64) or tuple(bias_v.shape) != (heads, 64):
+        return "bias_u / bias_v have to be [heads, 64] in the data dtype or both in fp32"
+    if pad_mask is not None and (tuple(pad_mask.shape) != (B, T) or pad_mask.device != dev):
+        return "pad_mask has to be [B,T] on the device of q"
+    return None
+
+
+def relpos_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias_u: Tensor, bias_v: Tensor, pad_mask: Optional[Tensor],
+                                     heads: int) -> bool:
+    """True when relpos_attention_autograd serves RelPosSelfAttention's training branch on these arguments: the switch is on, autocast off,
+    q / k / v [B,T,heads*64] GPU tensors in fp16 or bf16 with one common row stride (a multiple of 8 elements), pos the [2T-1, heads*64]
+    projected positions in that dtype, bias_u / bias_v [heads,64] in that dtype or fp32, T <= 2048, and the current stream not capturing a graph
+    (the random offset is reserved on the host).  Everything else — fp32 data, CPU tensors, another head width — keeps the torch lines."""
+    if not RELPOS_ATTENTION_HIP or torch.is_autocast_enabled():
+        return False
+    if _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) is not None:
+        return False
+    if any(t.data_ptr() % 16 or not t.is_contiguous() for t in (pos, bias_u, bias_v)):      # the layer hands them over as they are
+        return False
+    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+class _RelPosAttentionTrainFn(torch.autograd.Function):
+    """dsp_relpos_attention_train_fwd / _bwd.  Saved for the backward: q, k, v, pos, the biases, o, the fp32 lse and the mask bytes — no
+    probabilities and no dropout mask: the backward recomputes both."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pos, bias_u, bias_v, mask, heads, p, seed, offset):
+        B, T, C = q.shape
+        thr = dropout_threshold(p) if p > 0.0 else 0
+        scale = 1.0 / (1.0 - p) if thr else 1.0
+        lib = _lib.load()
+        dev = q.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            o = torch.empty((B, T, C), dtype=q.dtype, device=dev)
+            lse = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
+            rc = lib.dsp_relpos_attention_train_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(), bias_u.data_ptr(),
+                                                    bias_v.data_ptr(), None if mask is None else mask.data_ptr(), scale, thr, seed, offset,
+                                                    o.data_ptr(), lse.data_ptr(), _RA_CODES[q.dtype], _RN_CODES[bias_u.dtype], B, T, heads,
+                                                    torch._C._cuda_getCurrentRawStream(idx))
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_relpos_attention_train_fwd")
+        ctx.save_for_backward(q, k, v, pos, bias_u, bias_v, o, lse, mask)
+        ctx.call = (heads, scale, thr, seed, offset)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, do, _dlse):
+        q, k, v, pos, bias_u, bias_v, o, lse, mask = ctx.saved_tensors
+        heads, scale, thr, seed, offset = ctx.call
+        need = ctx.needs_input_grad
+        if do is None or not any(need[:6]):
+            return (None,) * 11
+        B, T, C = q.shape
+        if not do.is_contiguous():
+            do = do.contiguous()
+        lib = _lib.load()
+        dev = q.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            dq = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[0] else None
+            dk = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[1] else None
+            dv = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[2] else None
+            dpos = torch.empty(pos.shape, dtype=q.dtype, device=dev) if need[3] else None
+            du = torch.empty_like(bias_u) if need[4] else None
+            dbv = torch.empty_like(bias_v) if need[5] else None
+            nbytes = int(lib.dsp_relpos_attention_train_workspace_bytes(B, T, heads)) if (need[3] or need[4] or need[5]) else 0
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            rc = lib.dsp_relpos_attention_train_bwd(do.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(),
+                                                    bias_u.data_ptr(), bias_v.data_ptr(), ptr(mask), o.data_ptr(), lse.data_ptr(), scale, thr, seed,
+                                                    offset, ptr(dq), ptr(dk), ptr(dv), ptr(dpos), ptr(du), ptr(dbv), ptr(ws), nbytes,
+                                                    _RA_CODES[q.dtype], _RN_CODES[bias_u.dtype], B, T, heads, torch._C._cuda_getCurrentRawStream(idx))
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_relpos_attention_train_bwd")
+        return dq, dk, dv, dpos, du, dbv, None, None, None, None, None
+
+
+def relpos_attention_checked(q, k, v, pos, bias_u, bias_v, pad_mask, heads, p=0.0, training=True, return_lse=False):
+    """INTERNAL to RelPosSelfAttention: relpos_attention_autograd WITHOUT its argument checks, valid only on arguments that
+    relpos_attention_autograd_served accepted.  The kernels trust what they are handed: any other caller uses relpos_attention_autograd."""
+    p_eff = float(p) if training else 0.0
+    seed, offset = _reserve_dropout_stream(q.device) if p_eff > 0.0 else (0, 0)
+    if not pos.is_contiguous():
+        pos = pos.contiguous()
+    o, lse = _RelPosAttentionTrainFn.apply(q, k, v, pos, bias_u, bias_v, _mask_bytes(pad_mask), heads, p_eff, seed, offset)
+    return (o, lse) if return_lse else o
+
+
+def relpos_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias_u: Tensor, bias_v: Tensor, pad_mask: Optional[Tensor], heads: int,
+                              p: float = 0.0, training: bool = True, return_lse: bool = False):
+    """Conformer relative-position attention (fairseq espnet_multihead_attention.py RelPositionMultiHeadedAttention, between the projections
+    and linear_out) under autograd, one HIP launch forward (include/daspeech_decode.h: dsp_relpos_attention_train_fwd / _bwd):
+        o_i = sum_j dropout(softmax_j(((q_i + u).k_j + (q_i + v).pos[T-1-i+j]) / 8; pad_mask[b,j]: -inf), p)_ij v_j      per head of width 64
+    differentiable w.r.t. q, k, v, pos, bias_u and bias_v.  q, k, v [B,T,heads*64] fp16 / bf16 with one common row stride, pos the projected
+    positions ([2T-1, heads*64], a leading 1 allowed), bias_u / bias_v [heads,64] in that dtype or fp32, pad_mask [B,T] bool or None.  Returns
+    o [B,T,heads*64] (with return_lse: and the fp32 log-sum-exp [B,heads,T]).  No [B,h,T,T] tensor is kept: the backward recomputes the
+    probabilities.  Dropout is active with `training and p > 0`; the mask is the one dropout_keep_mask(seed, offset, p, (B, heads, T, Tp),
+    device)[..., :T] gives, Tp = T rounded up to 4, for the (seed, offset) the call reserves from the device's default CUDA generator (its
+    offset moves on by 4; calls with p = 0 do not touch the generator).  Bit-reproducible forward and backward.  Raises on what is not served."""
+    name = "relpos_attention_autograd"
+    why = _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads)
+    if why is None and not 0.0 <= p < 1.0:
+        why = f"dropout probability has to be in [0, 1), got {p}"
+    if why is not None:
+        raise RuntimeError(f"{name}: {why}")
+    ts = [t if t.data_ptr() % 16 == 0 else t.clone() for t in (pos.contiguous(), bias_u.contiguous(), bias_v.contiguous())]
+    return relpos_attention_checked(q, k, v, ts[0], ts[1], ts[2], pad_mask, heads, p, training, return_lse)
 
 
 class SplitConv1d:

@@ -174,6 +174,7 @@ class RelPosSelfAttention(nn.Module):
         """ln (eval-mode fast path only): the block's pre-LayerNorm, applied inside the stacked q|k|v projection instead of by the caller"""
         B, T, C = x.shape
         L_ = decode_ops.linear
+        pp = None                                   # linear_pos(pos), where the training branch has computed it already
         if ln is not None and (self.training or self.dk != 64):
             x, ln = decode_ops.layer_norm(x, ln), None
         if not self.training and self.dk == 64:
@@ -187,10 +188,19 @@ class RelPosSelfAttention(nn.Module):
             qf, kf, vf = qf.contiguous(), kf.contiguous(), vf.contiguous()
             q, k, v = qf.view(B, T, self.h, self.dk), kf.view(B, T, self.h, self.dk).transpose(1, 2), vf.view(B, T, self.h, self.dk).transpose(1, 2)
         else:
-            q = L_(x, self.linear_q).view(B, T, self.h, self.dk)
-            k = L_(x, self.linear_k).view(B, T, self.h, self.dk).transpose(1, 2)
-            v = L_(x, self.linear_v).view(B, T, self.h, self.dk).transpose(1, 2)
-        p = L_(pos, self.linear_pos).view(1, -1, self.h, self.dk).transpose(1, 2)
+            qf, kf, vf = L_(x, self.linear_q), L_(x, self.linear_k), L_(x, self.linear_v)
+            if self.dk == 64 and qf.is_cuda and qf.dtype != torch.float32:
+                # scores, shift, mask, soft-max, dropout and the value product as ONE HIP operator with its own backward
+                # (csrc/relpos_attention_train.hip): no [B,h,T,T] tensor is kept for autograd
+                pp = L_(pos, self.linear_pos).reshape(-1, C)
+                if decode_ops.relpos_attention_autograd_served(qf, kf, vf, pp, self.pos_bias_u, self.pos_bias_v, pad_mask, self.h):
+                    o = decode_ops.relpos_attention_checked(qf, kf, vf, pp, self.pos_bias_u, self.pos_bias_v, pad_mask, self.h,
+                                                            p=self.p_attn, training=self.training)
+                    return L_(o, self.linear_out, residual=residual)
+            q = qf.view(B, T, self.h, self.dk)
+            k = kf.view(B, T, self.h, self.dk).transpose(1, 2)
+            v = vf.view(B, T, self.h, self.dk).transpose(1, 2)
+        p = (L_(pos, self.linear_pos) if pp is None else pp).view(1, -1, self.h, self.dk).transpose(1, 2)
         ac = torch.matmul((q + self.pos_bias_u).transpose(1, 2), k.transpose(-2, -1))
         bd = self.rel_shift(torch.matmul((q + self.pos_bias_v).transpose(1, 2), p.transpose(-2, -1)))
         scores = (ac + bd) / math.sqrt(self.dk)

@@ -304,6 +304,41 @@ int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void* s, const f
                           void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream);
 int dsp_dropout_keep_mask(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, dsp_stream_t stream);
 
+/* Conformer relative-position self-attention under autograd (csrc/relpos_attention_train.hip), fp16 / bf16 data, head width 64:
+ *     s(b,h,i,j) = ((q_i + u_h).k_j + (q_i + v_h).pos[T-1-i+j]) / 8,  keys with pad_mask[b,j] != 0: -inf
+ *     P = softmax_j(s);  lse(b,h,i) = log sum_j exp s;  A = keep ? P * keep_scale : 0;  out_i = sum_j A_ij v_j
+ *   q, k, v [B,T,H,64] with one common row stride ld (elements; >= 64 H, a multiple of 8; samples T*ld apart: contiguous tensors or the column
+ *   slices of a stacked projection), pos [2T-1,H,64] contiguous (linear_pos of the relative positional encoding, rows for relative positions
+ *   T-1 .. -(T-1)), bias_u / bias_v [H,64], pad_mask [B,T] bytes or NULL, out [B,T,H*64] contiguous in the data dtype, lse [B,H,T] fp32 (saved
+ *   for the backward).  Scores, soft-max statistics and accumulators are fp32; q + u, q + v and P are rounded to the data dtype once, where
+ *   they become matrix-core operands.  Every query row is computed, padded ones too.  A sample whose keys are all masked gets NaN rows, as
+ *   torch's soft-max gives; no mask leads to an access out of range.
+ *   The mask follows dsp_resnorm_train_fwd's rule (above) on the element index e = ((b*H + h)*T + i)*Tp + j, Tp = T rounded up to a multiple
+ *   of 4: dsp_dropout_keep_mask over n = B*H*T*Tp elements, read as [B,H,T,Tp], is the mask applied.  thr == 0: no mask path.
+ *   backward from dout [B,T,H*64] contiguous with the forward's inputs, out, lse and (keep_scale, thr, seed, offset); with m = keep * keep_scale
+ *   and D_i = dout_i . out_i:   dV = (P o m)^T dout;  dP = (dout V^T) o m;  dS = P o (dP - D) / 8;  dK = dS^T (q + u);
+ *     dG[i, T-1-i+j] = dS[i,j];  dq = dS K + dG pos;  dpos = sum_b dG^T (q + v);  dbias_u = sum_{b,i} dS K;  dbias_v = sum_{b,i} dG pos.
+ *   P is recomputed; no [B,H,T,T] or [B,H,T,2T-1] tensor is written to memory in either direction.  dq, dk, dv [B,T,H*64] and dpos
+ *   [2T-1,H*64] contiguous in the data dtype, dbias_u / dbias_v [H,64] in param_dtype (act_dtype, or DSP_F32, as bias_u / bias_v).
+ *   act_dtype is DSP_F16 or DSP_BF16 (fp32 data is not served).  All pointers 16-byte aligned.  EVERY OUTPUT ELEMENT IS WRITTEN.  dpos and the
+ *   bias gradients are fp32 partials (per sample; per sample and block of 32 queries) added in ASCENDING order by tail kernels.  NO FLOAT
+ *   ATOMICS and no hand-off between workgroups: the same inputs give the same bits on every call.  Each of the six gradients may be NULL, and
+ *   leaving one out does not change the bits of the others.
+ *   workspace (backward, needed for dpos, dbias_u or dbias_v): dsp_relpos_attention_train_workspace_bytes(B, T, H) bytes of device memory,
+ *   16-byte aligned (DSP_ENOSPC if smaller); host arithmetic only, 0 for an empty problem, monotone in each argument, a multiple of 16.
+ *   1 <= T <= DSP_RELPOS_TRAIN_MAX_T, 1 <= H <= 1024.  Bad sizes, null required pointers, misalignment, an output that aliases an input:
+ *   DSP_EINVAL before any launch; B == 0: DSP_OK. */
+#define DSP_RELPOS_TRAIN_MAX_T 2048
+size_t dsp_relpos_attention_train_workspace_bytes(int B, int T, int H);
+int dsp_relpos_attention_train_fwd(const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u, const void* bias_v,
+                                   const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* out,
+                                   float* lse, int act_dtype, int param_dtype, int B, int T, int H, dsp_stream_t stream);
+int dsp_relpos_attention_train_bwd(const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
+                                   const void* bias_v, const unsigned char* pad_mask, const void* out, const float* lse, float keep_scale,
+                                   unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv, void* dpos, void* dbias_u,
+                                   void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H,
+                                   dsp_stream_t stream);
+
 /* fp32-accurate Conv1d ("same" padding, stride 1) on the fp16 matrix cores by operand splitting (x = xh + xl/2048, w = wh + wl/2048;
  * the products xh.wh, xh.wl, xl.wh are exact in the fp32 accumulator, the dropped xl.wl term is 2^-22 relative) — for the
  * FastSpeech2 FFT feed-forward convolutions (fairseq fastspeech2.py:42-63), which MIOpen runs at 60-70 TFLOP/s in fp32.
