@@ -21,6 +21,7 @@
 // takes one new block per tile) and read back from a per-wave scratch at [query][key - query + 31]: the rel_shift of the torch
 // formulation without its [B,h,T,2T-1] tensor.  (r03's fp32-FMA kernel for this: 113 us per layer at B=32, T=200; this one ~15.)
 #include "common.h"
+#include "split_operand.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -49,11 +50,6 @@ template <int DK> struct AtLds {
     // scratch per wave for the shift of the [query][relative position] product into [query][key]
     static constexpr int PRING = 6, PBLK = KF, SCR_PITCH = 68, SCR = 32 * SCR_PITCH * 4;
 };
-
-__device__ __forceinline__ void at_split8(const float* x, at_h8& hi, at_h8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { hi[e] = (_Float16)x[e]; lo[e] = (_Float16)((x[e] - (float)hi[e]) * 2048.f); }
-}
 
 template <int DK, bool REL>
 __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_split_kernel(AtParams p)
@@ -113,9 +109,9 @@ __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_spl
                 *reinterpret_cast<float4*>(bw + 4) = *reinterpret_cast<const float4*>(p.bias_v + h * DK + 8 * g + c * 16 + 4);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { y[e] = x[e] + bw[e]; x[e] += bu[e]; }
-                at_split8(y, rh[c], rl[c]);
+                split_hi_lo<8>(y, rh[c], rl[c]);
             }
-            at_split8(x, qh[c], ql[c]);
+            split_hi_lo<8>(x, qh[c], ql[c]);
         }
     }
     // ---- staging registers: K rows (8 floats per pass) and V columns (4 keys of one d per item)
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_spl
         float z[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) z[e] = ok ? x[e] : 0.f;
-        at_h8 hi, lo; at_split8(z, hi, lo);
+        at_h8 hi, lo; split_hi_lo<8>(z, hi, lo);
         char* dst = pring + (u % L::PRING) * L::PBLK + ((k_d8 >> 1) * 2) * AT_FRAG + (k_d8 & 1) * AT_HALF + k_key * 16;
         *reinterpret_cast<at_h8*>(dst) = hi;
         *reinterpret_cast<at_h8*>(dst + AT_FRAG) = lo;
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_spl
         if constexpr (REL) pos_store(t + 4, r.pr, r.pr_ok);
 #pragma unroll
         for (int ps = 0; ps < KP; ++ps) {
-            at_h8 hi, lo; at_split8(r.kr[ps], hi, lo);
+            at_h8 hi, lo; split_hi_lo<8>(r.kr[ps], hi, lo);
             const int d8 = k_d8 + 8 * ps, c = d8 >> 1, gk = d8 & 1;
             char* dst = st + (c * 2) * AT_FRAG + gk * AT_HALF + k_key * 16;
             *reinterpret_cast<at_h8*>(dst) = hi;
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_spl
             const int db = d >> 5, c2 = kq >> 2, e4 = (kq >> 1) & 1, gv = kq & 1;
             at_h4 hi, lo;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { hi[i] = (_Float16)r.vr[j][i]; lo[i] = (_Float16)((r.vr[j][i] - (float)hi[i]) * 2048.f); }
+            for (int i = 0; i < 4; ++i) split_hi_lo(r.vr[j][i], hi, lo, i);
             char* dst = st + L::KF + ((db * 2 + c2) * 2) * AT_FRAG + gv * AT_HALF + (d & 31) * 16 + e4 * 8;
             *reinterpret_cast<at_h4*>(dst) = hi;
             *reinterpret_cast<at_h4*>(dst + AT_FRAG) = lo;
@@ -277,9 +273,7 @@ __global__ __launch_bounds__(256, (DK == 64 && !REL) ? 2 : 1) void attention_spl
             for (int r = 0; r < 16; ++r) {
                 const float e = __expf(s[r] - m_use);
                 ps += e;
-                const _Float16 hi = (_Float16)e;
-                ph[r >> 3][r & 7] = hi;
-                pl[r >> 3][r & 7] = (_Float16)((e - (float)hi) * 2048.f);
+                split_hi_lo(e, ph[r >> 3], pl[r >> 3], r & 7);
             }
             l_run = l_run * alpha + ps;
             m_run = m_new;

@@ -28,51 +28,6 @@ constexpr int CM_TPT = DSP_CONVMOD_CHUNK_TILES / CM_TY;   // tiles per thread
 constexpr int CM_KG = 8;                                  // taps per round of the dw reduction through LDS
 static_assert(DSP_CONVMOD_CHUNK_TILES % CM_TY == 0, "a chunk is a whole number of tiles per slot");
 
-// ---- four consecutive channels <-> floats
-template <typename T> __device__ __forceinline__ void ld4(const T* __restrict__ p, float (&f)[4]);
-template <> __device__ __forceinline__ void ld4<float>(const float* __restrict__ p, float (&f)[4])
-{
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-template <> __device__ __forceinline__ void ld4<__half>(const __half* __restrict__ p, float (&f)[4])
-{
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    f[0] = __half2float(__ushort_as_half((unsigned short)(u.x & 0xffffu))); f[1] = __half2float(__ushort_as_half((unsigned short)(u.x >> 16)));
-    f[2] = __half2float(__ushort_as_half((unsigned short)(u.y & 0xffffu))); f[3] = __half2float(__ushort_as_half((unsigned short)(u.y >> 16)));
-}
-template <> __device__ __forceinline__ void ld4<__hip_bfloat16>(const __hip_bfloat16* __restrict__ p, float (&f)[4])
-{
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-    f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-}
-__device__ __forceinline__ uint32_t bits16(__half v) { return (uint32_t)__half_as_ushort(v); }
-__device__ __forceinline__ uint32_t bits16(__hip_bfloat16 v) { unsigned short u; __builtin_memcpy(&u, &v, 2); return (uint32_t)u; }
-template <typename T> __device__ __forceinline__ void st4(T* __restrict__ p, const float (&f)[4])
-{
-    *reinterpret_cast<uint2*>(p) = make_uint2(bits16(from_f<T>(f[0])) | (bits16(from_f<T>(f[1])) << 16),
-                                              bits16(from_f<T>(f[2])) | (bits16(from_f<T>(f[3])) << 16));
-}
-template <> __device__ __forceinline__ void st4<float>(float* __restrict__ p, const float (&f)[4])
-{
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-}
-
-// one element of a BatchNorm tensor (gamma, beta, the running buffers, dgamma, dbeta) in its own dtype code
-__device__ __forceinline__ float bn_load(const void* p, int dtype, int c)
-{
-    if (dtype == DSP_F32) return ((const float*)p)[c];
-    if (dtype == DSP_F16) return __half2float(((const __half*)p)[c]);
-    return __bfloat162float(((const __hip_bfloat16*)p)[c]);
-}
-__device__ __forceinline__ void bn_store(void* p, int dtype, int c, float v)
-{
-    if (dtype == DSP_F32) ((float*)p)[c] = v;
-    else if (dtype == DSP_F16) ((__half*)p)[c] = __float2half(v);
-    else ((__hip_bfloat16*)p)[c] = __float2bfloat16(v);
-}
-
 // (count, mean, M2) of a set  <-  the same of a second, disjoint set (Chan, Golub, LeVeque); either may be empty
 __device__ __forceinline__ void chan_merge(float& na, float& ma, float& qa, float nb, float mb, float qb)
 {
@@ -105,7 +60,7 @@ __device__ __forceinline__ void conv_tile(const T* __restrict__ X, int T_, int C
     for (int s = 0; s < K + CM_TT - 1; ++s) {
         const int ti = t0 - P + s;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (ti >= 0 && ti < T_) ld4<T>(X + (size_t)ti * C, v);
+        if (ti >= 0 && ti < T_) load_f<T, 4>(X + (size_t)ti * C, v);
 #pragma unroll
         for (int u = 0; u < CM_TT; ++u) {
             const int k = s - u;
@@ -207,11 +162,11 @@ __global__ __launch_bounds__(256) void cm_fwd_apply_kernel(const T* __restrict__
                 chan_merge(n, m, q, p[c], p[C + c], p[2 * C + c]);
             }
             const float var = q / n, invstd = 1.f / sqrtf(var + eps);
-            sm[0][cl] = m; sm[1][cl] = invstd; sm[2][cl] = bn_load(gamma, bn_dtype, c); sm[3][cl] = bn_load(beta, bn_dtype, c);
+            sm[0][cl] = m; sm[1][cl] = invstd; sm[2][cl] = param_load(gamma, bn_dtype, c); sm[3][cl] = param_load(beta, bn_dtype, c);
             if (blockIdx.x == 0) {
                 save_mean[c] = m; save_invstd[c] = invstd;
-                if (run_mean) bn_store(run_mean, bn_dtype, c, (1.f - momentum) * bn_load(run_mean, bn_dtype, c) + momentum * m);
-                if (run_var) bn_store(run_var, bn_dtype, c, (1.f - momentum) * bn_load(run_var, bn_dtype, c) + momentum * (q / (n - 1.f)));
+                if (run_mean) param_store(run_mean, bn_dtype, c, (1.f - momentum) * param_load(run_mean, bn_dtype, c) + momentum * m);
+                if (run_var) param_store(run_var, bn_dtype, c, (1.f - momentum) * param_load(run_var, bn_dtype, c) + momentum * (q / (n - 1.f)));
             }
         }
     }
@@ -242,7 +197,7 @@ __global__ __launch_bounds__(256) void cm_fwd_apply_kernel(const T* __restrict__
                         const float uu = sm[2][cl + i] * ((acc[u][i] - sm[0][cl + i]) * sm[1][cl + i]) + sm[3][cl + i];
                         o[i] = uu / (1.f + expf(-uu));
                     }
-                    st4<T>(y + ((size_t)b * T_ + t0 + u) * C + c, o);
+                    store_f<T, 4>(y + ((size_t)b * T_ + t0 + u) * C + c, o);
                 }
             }
         }
@@ -272,7 +227,7 @@ __global__ __launch_bounds__(256) void cm_bwd_sums_kernel(const T* __restrict__ 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 mean[i] = save_mean[c + i]; invstd[i] = save_invstd[c + i];
-                g[i] = bn_load(gamma, bn_dtype, c + i); be[i] = bn_load(beta, bn_dtype, c + i);
+                g[i] = param_load(gamma, bn_dtype, c + i); be[i] = param_load(beta, bn_dtype, c + i);
             }
 #pragma unroll 1
             for (int j = 0; j < CM_TPT; ++j) {
@@ -285,7 +240,7 @@ __global__ __launch_bounds__(256) void cm_bwd_sums_kernel(const T* __restrict__ 
                 for (int u = 0; u < CM_TT; ++u) {
                     if (t0 + u < T_) {
                         float go[4];
-                        ld4<T>(gy + ((size_t)b * T_ + t0 + u) * C + c, go);
+                        load_f<T, 4>(gy + ((size_t)b * T_ + t0 + u) * C + c, go);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             const float zh = (acc[u][i] - mean[i]) * invstd[i];
@@ -335,8 +290,8 @@ __global__ __launch_bounds__(256) void cm_bwd_dz_kernel(const T* __restrict__ x,
             const float N = (float)B * (float)T_;
             sm[0][cl] = a / N; sm[1][cl] = g / N;
             if (blockIdx.x == 0) {
-                if (dbeta) bn_store(dbeta, bn_dtype, c, a);
-                if (dgamma) bn_store(dgamma, bn_dtype, c, g);
+                if (dbeta) param_store(dbeta, bn_dtype, c, a);
+                if (dgamma) param_store(dgamma, bn_dtype, c, g);
             }
         }
     }
@@ -355,7 +310,7 @@ __global__ __launch_bounds__(256) void cm_bwd_dz_kernel(const T* __restrict__ x,
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             mean[i] = save_mean[c + i]; invstd[i] = save_invstd[c + i];
-            g[i] = bn_load(gamma, bn_dtype, c + i); be[i] = bn_load(beta, bn_dtype, c + i);
+            g[i] = param_load(gamma, bn_dtype, c + i); be[i] = param_load(beta, bn_dtype, c + i);
         }
 #pragma unroll 1
         for (int j = 0; j < CM_TPT; ++j) {
@@ -369,7 +324,7 @@ __global__ __launch_bounds__(256) void cm_bwd_dz_kernel(const T* __restrict__ x,
                 if (t0 + u < T_) {
                     const size_t at = ((size_t)b * T_ + t0 + u) * C + c;
                     float go[4], o[4];
-                    ld4<T>(gy + at, go);
+                    load_f<T, 4>(gy + at, go);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const float zh = (acc[u][i] - mean[i]) * invstd[i];
@@ -377,7 +332,7 @@ __global__ __launch_bounds__(256) void cm_bwd_dz_kernel(const T* __restrict__ x,
                         const float du = go[i] * silu_grad_factor(g[i] * zh + be[i], s);
                         o[i] = g[i] * invstd[i] * (du - sm[0][cl + i] - zh * sm[1][cl + i]);
                     }
-                    st4<float>(dz + at, o);
+                    store_f<float, 4>(dz + at, o);
                 }
             }
         }
@@ -410,7 +365,7 @@ __global__ __launch_bounds__(256) void cm_bwd_dxdw_kernel(const T* __restrict__ 
                 conv_tile<float, K, true>(dz + (size_t)b * T_ * C + c, T_, C, t0, wr, acc);
 #pragma unroll
                 for (int u = 0; u < CM_TT; ++u)
-                    if (t0 + u < T_) st4<T>(dx + ((size_t)b * T_ + t0 + u) * C + c, acc[u]);
+                    if (t0 + u < T_) store_f<T, 4>(dx + ((size_t)b * T_ + t0 + u) * C + c, acc[u]);
             }
         }
         if (DW) {
@@ -431,14 +386,14 @@ __global__ __launch_bounds__(256) void cm_bwd_dxdw_kernel(const T* __restrict__ 
                     for (int u = 0; u < CM_TT; ++u) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) g[u][i] = 0.f;
-                        if (t0 + u < T_) ld4<float>(dz + base + (size_t)(t0 + u) * C, g[u]);
+                        if (t0 + u < T_) load_f<float, 4>(dz + base + (size_t)(t0 + u) * C, g[u]);
                     }
                     // input row t0 - P + s meets output row t0 + u at tap k = s - u
 #pragma unroll
                     for (int s = 0; s < K + CM_TT - 1; ++s) {
                         const int ti = t0 - P + s;
                         float v[4] = {0.f, 0.f, 0.f, 0.f};
-                        if (ti >= 0 && ti < T_) ld4<T>(x + base + (size_t)ti * C, v);
+                        if (ti >= 0 && ti < T_) load_f<T, 4>(x + base + (size_t)ti * C, v);
 #pragma unroll
                         for (int u = 0; u < CM_TT; ++u) {
                             const int k = s - u;
@@ -485,7 +440,6 @@ __global__ __launch_bounds__(256) void cm_bwd_dw_merge_kernel(const float* __res
     dw[e] = from_f<T>(a);
 }
 
-static int cm_es(int dtype) { return dtype == DSP_F32 ? 4 : ((dtype == DSP_F16 || dtype == DSP_BF16) ? 2 : 0); }
 static size_t cm_a16(size_t n) { return (n + 15) & ~(size_t)15; }
 static long cm_chunks(int B, int T) { return ((long)B * ((T + CM_TT - 1) / CM_TT) + DSP_CONVMOD_CHUNK_TILES - 1) / DSP_CONVMOD_CHUNK_TILES; }
 // the workspace: [chunks][3][C] statistics (forward) or [chunks][2][C] dbeta / dgamma sums (backward) | dz [B,T,C] | [chunks][C][K] dw sums
@@ -496,8 +450,8 @@ static size_t cm_wpart_bytes(int B, int T, int C, int K) { return cm_a16((size_t
 // what both entry points check; 1: nothing to do (B == 0), 0: go on, < 0: refused
 static int cm_check(const char* who, int act_dtype, int bn_dtype, int B, int T, int C, int K)
 {
-    const int es = cm_es(act_dtype);
-    if (!es || !cm_es(bn_dtype) || (bn_dtype != act_dtype && bn_dtype != DSP_F32)) {
+    const int es = elem_size(act_dtype);
+    if (!es || !elem_size(bn_dtype) || (bn_dtype != act_dtype && bn_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (x, w, y) / %d (BatchNorm tensors: the same, or fp32)", who, act_dtype, bn_dtype); return DSP_EINVAL;
     }
     const int V = 16 / es;
@@ -522,12 +476,7 @@ using namespace dsp;
         case 7: { constexpr int KK = 7; __VA_ARGS__; } break;                    \
         default: { constexpr int KK = 3; __VA_ARGS__; } break;                   \
     }
-#define CM_DISPATCH(dtype, K, ...)                                               \
-    switch (dtype) {                                                             \
-        case DSP_F32: { using E = float; CM_K_SWITCH(K, __VA_ARGS__); } break;   \
-        case DSP_F16: { using E = __half; CM_K_SWITCH(K, __VA_ARGS__); } break;  \
-        default: { using E = __hip_bfloat16; CM_K_SWITCH(K, __VA_ARGS__); } break; \
-    }
+#define CM_DISPATCH(dtype, K, ...) DSP_DISPATCH_ELEM(dtype, E, CM_K_SWITCH(K, __VA_ARGS__))
 
 extern "C" size_t dsp_dwconv_bn_silu_train_workspace_bytes(int B, int T, int C, int K)
 {
@@ -551,7 +500,7 @@ extern "C" int dsp_dwconv_bn_silu_train_fwd(const void* x, const void* w, const 
         set_error("%s: workspace of dsp_dwconv_bn_silu_train_workspace_bytes bytes (16-byte aligned) needed", who);
         return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
     }
-    const int V = 16 / cm_es(act_dtype);
+    const int V = 16 / elem_size(act_dtype);
     const int nchunks = (int)cm_chunks(B, T);
     const dim3 grid((unsigned)nchunks, (unsigned)((C / V + CM_CG - 1) / CM_CG));
     float* part = (float*)workspace;
@@ -579,7 +528,7 @@ extern "C" int dsp_dwconv_bn_silu_train_bwd(const void* x, const void* w, const 
         set_error("%s: workspace of dsp_dwconv_bn_silu_train_workspace_bytes bytes (16-byte aligned) needed", who);
         return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
     }
-    const int V = 16 / cm_es(act_dtype);
+    const int V = 16 / elem_size(act_dtype);
     const int nchunks = (int)cm_chunks(B, T);
     const unsigned gy_ = (unsigned)((C / V + CM_CG - 1) / CM_CG);
     const dim3 grid((unsigned)nchunks, gy_);

@@ -11,6 +11,7 @@
 //   MFMA fragment order (dsp_conv1d_split_pack), out [B,T,M] fp32 = [out +] bias + conv, optional ReLU.
 #include "common.h"
 #include "split_frag.h"
+#include "split_operand.h"
 #include <stdlib.h>
 #include "../../include/daspeech_decode.h"
 
@@ -147,10 +148,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
                     }
                     cs_h8 vh, vl;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const float x = ok[u] ? f[i] : 0.f;
-                        vh[i] = (_Float16)x; vl[i] = (_Float16)((x - (float)vh[i]) * 2048.f);
-                    }
+                    for (int i = 0; i < 8; ++i) split_hi_lo(ok[u] ? f[i] : 0.f, vh, vl, i);
                     const size_t o = ((size_t)row * CH + split_swz<CI>(row, ch)) * 16;
                     *reinterpret_cast<cs_h8*>(th + o) = vh;
                     *reinterpret_cast<cs_h8*>(tl + o) = vl;
@@ -256,16 +254,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
                 const float4 old = *reinterpret_cast<const float4*>(O);
                 v[0] += old.x; v[1] += old.y; v[2] += old.z; v[3] += old.w;
             }
-            if (p.relu == 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (p.relu == 2) {                  // SiLU
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.f + __expf(-v[e]));
-            } else if (p.relu == 3) {                  // GELU (erf form, torch's default)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = 0.5f * v[e] * (1.f + erff(v[e] * 0.70710678118654752f));
-            }
+            split_act(v, p.relu);
             if (p.res) {
                 const float4 r4 = *reinterpret_cast<const float4*>(p.res + ((size_t)b * p.T + t) * p.ldr + co);
                 v[0] = r4.x + p.alpha * v[0]; v[1] = r4.y + p.alpha * v[1]; v[2] = r4.z + p.alpha * v[2]; v[3] = r4.w + p.alpha * v[3];
@@ -279,7 +268,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv1d_split_kernel(CsParams p)
     }     // output tiles
 }
 
-// fp32 weight [ntaps][M][CI] (tap-major) -> hi / lo fp16 in fragment order [ntaps][CI/32][ceil(M/16)][64][8] (see hifigan_conv.hip)
+// fp32 weight [ntaps][M][CI] (tap-major) -> hi / lo fp16 in fragment order [ntaps][CI/32][ceil(M/16)][64][8] (the order of
+// hifigan_conv.hip's hg_pack_weights_kernel)
 __global__ void conv1d_split_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ wh, _Float16* __restrict__ wl,
                                          int ntaps, int M, int CI)
 {
@@ -292,10 +282,15 @@ __global__ void conv1d_split_pack_kernel(const float* __restrict__ w, _Float16* 
         const int c = (int)(r % NC); const int k = (int)(r / NC);
         const int co = tile * 16 + (ln & 15), ci = c * 32 + (ln >> 4) * 8 + h;
         const float v = (co < M) ? w[((size_t)k * M + co) * CI + ci] : 0.f;
-        const _Float16 hi = (_Float16)v;
-        wh[e] = hi;
-        wl[e] = (_Float16)((v - (float)hi) * 2048.f);
+        split_hi_lo(v, wh[e], wl[e]);
     }
+}
+
+int split_pack_launch(const char* who, const float* w, _Float16* w_hi, _Float16* w_lo, long n, int ntaps, int M, int CI, hipStream_t st)
+{
+    int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(conv1d_split_pack_kernel, dim3(grid), dim3(256), 0, st, w, w_hi, w_lo, ntaps, M, CI);
+    return check_launch(who);
 }
 
 // out = res + alpha * act(bias + part[0] + part[1] + ...): the K-parts in a fixed order
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(256) void cs_reduce_kernel(const float* __restrict_
         float v[4] = {s4.x, s4.y, s4.z, s4.w};
         if (bias) { const float4 bb = *reinterpret_cast<const float4*>(bias + c); v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w; }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {                     // split_act's chain, spelled out: through the helper this kernel comes out as other code
             if (act == 1) v[i] = fmaxf(v[i], 0.f);
             else if (act == 2) v[i] = v[i] / (1.f + __expf(-v[i]));
             else if (act == 3) v[i] = 0.5f * v[i] * (1.f + erff(v[i] * 0.70710678118654752f));
@@ -458,9 +453,7 @@ extern "C" int dsp_conv1d_split_pack(const float* w_tap_major, void* w_hi, void*
 {
     const long n = dsp_conv1d_split_packed_elems(ntaps, M, CI);
     if (n < 0 || !w_tap_major || !w_hi || !w_lo) { set_error("conv1d_split_pack: bad arguments"); return DSP_EINVAL; }
-    int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(conv1d_split_pack_kernel, dim3(grid), dim3(256), 0, as_stream(stream), w_tap_major, (_Float16*)w_hi, (_Float16*)w_lo, ntaps, M, CI);
-    return check_launch("conv1d_split_pack");
+    return split_pack_launch("conv1d_split_pack", w_tap_major, (_Float16*)w_hi, (_Float16*)w_lo, n, ntaps, M, CI, as_stream(stream));
 }
 
 static int cs_run(const float* x, long ldx, const void* w_hi, const void* w_lo, const float* bias, float* out, long ldo,

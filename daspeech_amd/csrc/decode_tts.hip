@@ -355,7 +355,6 @@ __global__ __launch_bounds__(256) void lr_expand_kernel(const char* __restrict__
     }
 }
 
-static int elem_size(int dtype) { return dtype == DSP_F32 ? 4 : ((dtype == DSP_F16 || dtype == DSP_BF16) ? 2 : 0); }
 
 }  // namespace dsp
 

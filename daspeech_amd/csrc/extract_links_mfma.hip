@@ -34,6 +34,7 @@
 // autograd on the device; tests/test_gpu_links_regimes.py holds each family on its own to a float64 CPU reference, per sample and head, at
 // the tile, length and dispatch edges and under peaked scores, wide-ranged and non-finite (beyond the graph) gradients.
 #include "dag_dp.h"
+#include "split_operand.h"
 #include <atomic>
 #include "../../include/daspeech_decode.h"
 #include <type_traits>
@@ -72,7 +73,7 @@ __device__ __forceinline__ void xm_split8(const float* x, xm_h8& hi, xm_h8& lo) 
         const bool big = fabsf(x[e]) > 65000.f;                                    // (false for NaN: a NaN operand stays a NaN)
         const float xc = big ? copysignf(65000.f, x[e]) : x[e];
         over |= big;
-        hi[e] = (_Float16)xc; lo[e] = (_Float16)((xc - (float)hi[e]) * 2048.f);
+        split_hi_lo(xc, hi, lo, e);
     }
     if (__builtin_expect(over, 0)) atomicOr(&g_xl_range, 1u);
 }

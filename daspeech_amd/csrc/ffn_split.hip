@@ -12,6 +12,8 @@
 // write partial sums that ffn_reduce_kernel adds in a FIXED order with the bias and the residual (deterministic; no atomics).
 // Weight traffic per workgroup is 1/G of the two matrices; the intermediate never leaves the CU.
 #include "common.h"
+#include "split_frag.h"
+#include "split_operand.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -26,9 +28,6 @@ struct FfParams {
     float* part;                                                       // [G][B][T][C] partial sums of W2 . h
     int B, T, H, act, G;
 };
-
-// 16-byte chunk swizzle of a [rows][256 halves] tile (conv1d_split.hip cs_swz<256>: 32 chunks per row)
-__device__ __forceinline__ int ff_swz(int row, int chunk) { return chunk ^ ((row & 7) << 1); }
 
 template <int C, int NT>
 __global__ __launch_bounds__(512) void ffn_split_kernel(FfParams p)
@@ -82,11 +81,8 @@ __global__ __launch_bounds__(512) void ffn_split_kernel(FfParams p)
                 }
                 ff_h8 vh, vl;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float v = ok[u] ? f[u][i] : 0.f;
-                    vh[i] = (_Float16)v; vl[i] = (_Float16)((v - (float)vh[i]) * 2048.f);
-                }
-                const size_t o = ((size_t)row * CH + ff_swz(row, ch)) * 16;
+                for (int i = 0; i < 8; ++i) split_hi_lo(ok[u] ? f[u][i] : 0.f, vh, vl, i);
+                const size_t o = ((size_t)row * CH + split_swz<256>(row, ch)) * 16;
                 *reinterpret_cast<ff_h8*>(xh + o) = vh;
                 *reinterpret_cast<ff_h8*>(xl + o) = vl;
             }
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(512) void ffn_split_kernel(FfParams p)
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int row = j * 16 + lr;
-            const size_t o = ((size_t)row * CH + ff_swz(row, s * 4 + lk)) * 16;
+            const size_t o = ((size_t)row * CH + split_swz<256>(row, s * 4 + lk)) * 16;
             const ff_h8 bh = *reinterpret_cast<const ff_h8*>(th + o);
             const ff_h8 bl = *reinterpret_cast<const ff_h8*>(tl + o);
 #pragma unroll
@@ -150,14 +146,10 @@ __global__ __launch_bounds__(512) void ffn_split_kernel(FfParams p)
                 _Float16 hv[4], lv[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float v = h0[i][j][e] + h1[i][j][e] * (1.f / 2048.f) + bv[e];
-                    if (p.act == 1) v = fmaxf(v, 0.f);
-                    else if (p.act == 2) v = v / (1.f + __expf(-v));
-                    else if (p.act == 3) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-                    const _Float16 q = (_Float16)v;
-                    hv[e] = q; lv[e] = (_Float16)((v - (float)q) * 2048.f);
+                    const float v = h0[i][j][e] + h1[i][j][e] * (1.f / 2048.f) + bv[e];
+                    split_hi_lo(split_act(v, p.act), hv[e], lv[e]);
                 }
-                const size_t o = ((size_t)m * CH + ff_swz(m, hcl >> 3)) * 16 + (hcl & 4) * 2;
+                const size_t o = ((size_t)m * CH + split_swz<256>(m, hcl >> 3)) * 16 + (hcl & 4) * 2;
                 *reinterpret_cast<uint2*>(hh + o) = *reinterpret_cast<uint2*>(hv);
                 *reinterpret_cast<uint2*>(hl + o) = *reinterpret_cast<uint2*>(lv);
             }

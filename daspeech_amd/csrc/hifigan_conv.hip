@@ -13,6 +13,7 @@
 //     that wave's time tiles);
 //   * mfma_f32_16x16x32_f16, fp32 accumulate; 8 waves as WM (channel) x WN (time) sub-tiles.
 #include "common.h"
+#include "split_frag.h"
 #include <stdlib.h>
 #include "../../include/daspeech_hifigan.h"
 
@@ -36,23 +37,6 @@ __device__ __forceinline__ int hg_valid_len(const int* lens, int len_mul, int b,
     if (!lens) return T;
     const int v = lens[b] * len_mul;
     return v < T ? v : T;
-}
-
-template <int CI>
-__device__ __forceinline__ int hg_swz(int row, int chunk) {
-    constexpr int CH = CI / 8;                          // 16-byte chunks per row
-    // ds_read_b128 is serviced in four NON-contiguous groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ... MI355X_MICROARCH.md
-    // §LDS): a B-fragment read puts 8 rows at k-chunk q and the other 8 rows of the same 16 at chunk q ^ 1 into one group.  The r01
-    // swizzle (chunk ^ row) is conflict-free for 16 rows at ONE chunk; with the real groups it collides whenever the tile row of
-    // lane 0 is odd (every odd tap shift): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.27 - 0.46 (profiles/r03f_pmc_hifigan.txt).
-    // XOR-ing only EVEN values leaves bit 0 of the slot to tell the two halves of a group apart, and 8 rows x 8 even values are
-    // distinct for any base row: conflict-free for every shift.  (256-byte bank row = 16 slots of 16 bytes; rows narrower than that
-    // share a bank row: the row's position inside it supplies the remaining slot bits.)
-    if constexpr ((CH & (CH - 1)) != 0) return chunk;   // CI = 96: 12 chunks, not a power of two -> no swizzle
-    else if constexpr (CH >= 16) return chunk ^ ((row & 7) << 1);
-    else if constexpr (CH == 8) return chunk ^ (((row >> 1) & 3) << 1);
-    else if constexpr (CH == 4) return chunk ^ (((row >> 2) & 1) << 1);
-    else return chunk;
 }
 
 // Stage rows [t_first, t_first + R) of channels-last x (zero outside [0,T)) into the swizzled LDS tile, leaky_relu applied once
@@ -84,7 +68,7 @@ __device__ __forceinline__ void hg_stage_tile(char* tile, const _Float16* __rest
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[u][i] = v[u][i] > (_Float16)0 ? v[u][i] : v[u][i] * slope;
                 }
-                *reinterpret_cast<h8*>(tile + ((size_t)row * CH + hg_swz<CI>(row, ch)) * 16) = v[u];
+                *reinterpret_cast<h8*>(tile + ((size_t)row * CH + split_swz<CI>(row, ch)) * 16) = v[u];
             }
         }
     }
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(512) void hifigan_conv_kernel(HgParams p)
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int row = tl_base + j * 16 + lr + rshift;
-            const h8 bf = *reinterpret_cast<const h8*>(smem + ((size_t)row * CH + hg_swz<CI>(row, c * 4 + lk)) * 16);
+            const h8 bf = *reinterpret_cast<const h8*>(smem + ((size_t)row * CH + split_swz<CI>(row, c * 4 + lk)) * 16);
 #pragma unroll
             for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], bf, acc[i][j], 0, 0, 0);
         }
@@ -312,7 +296,7 @@ __global__ __launch_bounds__(512) void hifigan_resunit_kernel(HgUnitParams p)
             for (int j = 0; j < NI; ++j) {
                 // straight-line: c2's 16 columns past NT (last wave, last j) read the 16 slack rows behind `mid`; never stored
                 const int row = (wn * NI + j) * 16 + lr + row0 + k * rstep;
-                const h8 bf = *reinterpret_cast<const h8*>(tile + ((size_t)row * CH + hg_swz<C>(row, c * 4 + lk)) * 16);
+                const h8 bf = *reinterpret_cast<const h8*>(tile + ((size_t)row * CH + split_swz<C>(row, c * 4 + lk)) * 16);
 #pragma unroll
                 for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], bf, acc[i][j], 0, 0, 0);
             }
@@ -354,7 +338,7 @@ __global__ __launch_bounds__(512) void hifigan_resunit_kernel(HgUnitParams p)
                 h = h > (_Float16)0 ? h : h * slope;
                 hv[e] = (tm >= 0 && tm < Tb) ? h : (_Float16)0;
             }
-            *reinterpret_cast<uint2*>(mid + ((size_t)m * CH + hg_swz<C>(m, co >> 3)) * 16 + (co & 4) * 2) = *reinterpret_cast<uint2*>(hv);
+            *reinterpret_cast<uint2*>(mid + ((size_t)m * CH + split_swz<C>(m, co >> 3)) * 16 + (co & 4) * 2) = *reinterpret_cast<uint2*>(hv);
         }
     }
     __syncthreads();                                  // intermediate complete

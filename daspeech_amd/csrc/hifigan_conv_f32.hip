@@ -7,11 +7,12 @@
 //     acc_main += wh . xh          acc_corr += wh . xl + wl . xh          out = acc_main + acc_corr / 2048
 // Every product is exact in the fp32 accumulator; the dropped wl . xl term is 2^-22 of the result.  Activations live in HBM as fp32
 // (channels-last [B][T][C]); the leaky_relu and the split happen once per element while the input tile is staged into two LDS tiles
-// (hi, lo; the XOR swizzle of hifigan_conv.hip), weights come pre-split in MFMA fragment order.  Three MFMAs per fragment pair and
+// (hi, lo; the XOR swizzle of split_frag.h), weights come pre-split in MFMA fragment order.  Three MFMAs per fragment pair and
 // twice the activation bytes: the price of the reference's arithmetic (measured beside the fp16-storage path in bench.py).
 // Range: |x|, |w| < 65504 (fp16 hi part); values under 6e-5 keep fewer than 22 bits — both far from what a vocoder holds.
 #include "common.h"
 #include "split_frag.h"
+#include "split_operand.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <type_traits>
@@ -31,7 +32,6 @@ struct HgsParams {
     const int* lens; int len_mul;
 };
 
-constexpr float HGS_LO = 2048.f, HGS_LO_INV = 1.f / 2048.f;
 
 __device__ __forceinline__ int hgs_valid_len(const int* lens, int len_mul, int b, int T) {
     if (!lens) return T;
@@ -68,9 +68,9 @@ __device__ __forceinline__ void hgs_stage_tile(char* thi, char* tlo, const float
                 for (int i = 0; i < 8; ++i) {
                     float v = i < 4 ? va[u][i] : vb[u][i - 4];
                     v = v > 0.f ? v : v * slope;
-                    const _Float16 h = (_Float16)v;
-                    hi[i] = h;
-                    lo[i] = (_Float16)((v - (float)h) * HGS_LO);
+                    _Float16 h, l;
+                    split_hi_lo(v, h, l);
+                    hi[i] = h; lo[i] = l;
                 }
                 const size_t o = ((size_t)row * CH + split_swz<CI>(row, ch)) * 16;
                 *reinterpret_cast<h8*>(thi + o) = hi;
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(512) void hifigan_conv_f32_kernel(HgsParams p)
             const int tl = tl_base + j * 16 + lr;
             f4 v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accc[i][j][e] * HGS_LO_INV + bv[e];
+            for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accc[i][j][e] * SPLIT_LO_INV + bv[e];
             *reinterpret_cast<f4*>(otile + (size_t)tl * OPITCH + ml) = v;
         }
     }
@@ -350,11 +350,10 @@ __global__ __launch_bounds__(512, (C == 64 ? 2 : 4)) void hifigan_resunit_f32_ke
             _Float16 hv[4], lv[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float v = accm[i][j][e] + accc[i][j][e] * HGS_LO_INV + bv[e];
+                float v = accm[i][j][e] + accc[i][j][e] * SPLIT_LO_INV + bv[e];
                 v = v > 0.f ? v : v * p.slope;
                 if (!(tm >= 0 && tm < Tb)) v = 0.f;
-                const _Float16 hh = (_Float16)v;
-                hv[e] = hh; lv[e] = (_Float16)((v - (float)hh) * HGS_LO);
+                split_hi_lo(v, hv[e], lv[e]);
             }
             const size_t o = ((size_t)m * CH + split_swz<C>(m, co >> 3)) * 16 + (co & 4) * 2;
             *reinterpret_cast<uint2*>(mhi + o) = *reinterpret_cast<uint2*>(hv);
@@ -378,7 +377,7 @@ __global__ __launch_bounds__(512, (C == 64 ? 2 : 4)) void hifigan_resunit_f32_ke
             if (tl < nt) {                            // the output tile holds nt rows
                 f4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accc[i][j][e] * HGS_LO_INV + bv[e];
+                for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accc[i][j][e] * SPLIT_LO_INV + bv[e];
                 *reinterpret_cast<f4*>(otile + (size_t)tl * OPITCH + ml) = v;
             }
         }
@@ -473,24 +472,6 @@ template <int C, int NTI, int WM, int WN>
 static int hgs_unit_launch_trim(const HgsUnitParams& p, const HgsUnitTile& tile, hipStream_t st)
 {
     return tile.trim ? hgs_unit_launch<C, NTI, WM, WN, true>(p, tile, st) : hgs_unit_launch<C, NTI, WM, WN, false>(p, tile, st);
-}
-
-// fp32 tap-major [ntaps][M][CI] -> (hi, lo * 2048) in the fragment order of hifigan_conv.hip's hg_pack_weights_kernel
-__global__ void hgs_pack_weights_kernel(const float* __restrict__ w, _Float16* __restrict__ oh, _Float16* __restrict__ ol, int ntaps, int M, int CI)
-{
-    const int Mt = (M + 15) >> 4, NC = CI / 32;
-    const long n = (long)ntaps * NC * Mt * 512;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        const int h = (int)(e & 7), ln = (int)((e >> 3) & 63);
-        long r = e >> 9;
-        const int tile = (int)(r % Mt); r /= Mt;
-        const int c = (int)(r % NC); const int k = (int)(r / NC);
-        const int co = tile * 16 + (ln & 15), ci = c * 32 + (ln >> 4) * 8 + h;
-        const float v = (co < M) ? w[((size_t)k * M + co) * CI + ci] : 0.f;
-        const _Float16 hi = (_Float16)v;
-        oh[e] = hi;
-        ol[e] = (_Float16)((v - (float)hi) * HGS_LO);
-    }
 }
 
 __global__ void hgs_pad_kernel(const float* __restrict__ x, float* __restrict__ out, long n_rows, int C, int Cpad)
@@ -630,9 +611,7 @@ extern "C" int dsp_hifigan_pack_weights_f32(const float* w, void* w_hi_lo, int n
 {
     const long n = dsp_hifigan_packed_weight_elems(ntaps, M, CI);
     if (n < 0 || !w || !w_hi_lo) { set_error("hifigan_pack_weights_f32: bad arguments"); return DSP_EINVAL; }
-    int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(hgs_pack_weights_kernel, dim3(grid), dim3(256), 0, as_stream(stream), w, (_Float16*)w_hi_lo, (_Float16*)w_hi_lo + n, ntaps, M, CI);
-    return check_launch("hifigan_pack_weights_f32");
+    return split_pack_launch("hifigan_pack_weights_f32", w, (_Float16*)w_hi_lo, (_Float16*)w_hi_lo + n, n, ntaps, M, CI, as_stream(stream));
 }
 
 extern "C" int dsp_hifigan_pad_input_f32(const float* x, float* out, int B, int T, int C, int Cpad, dsp_stream_t stream)

@@ -42,24 +42,21 @@ __device__ __forceinline__ void lsg_st16(void* p, const uint4& o)
 }
 
 
-template <typename T> struct Vec;                 // 16-byte vector of T
-template <> struct Vec<float> { static constexpr int N = 4; };
-template <> struct Vec<__half> { static constexpr int N = 8; };
-template <> struct Vec<__hip_bfloat16> { static constexpr int N = 8; };
-
+// 16 bytes of T <-> floats.  Not elem_io.h's load_f / store_f: with their word-wise bit-picking the 16-bit instances of lsg_fwd_kernel and
+// lsg_bwd_kernel come out with other register counts (42 -> 44, 40 -> 36 VGPRs); these kernels keep the element-wise form they were tuned with.
 template <typename T>
-__device__ __forceinline__ void load16(const T* p, float (&f)[Vec<T>::N]) {
+__device__ __forceinline__ void load16(const T* p, float (&f)[elems16<T>]) {
     uint4 raw = *reinterpret_cast<const uint4*>(p);
     const T* e = reinterpret_cast<const T*>(&raw);
 #pragma unroll
-    for (int i = 0; i < Vec<T>::N; ++i) f[i] = to_f(e[i]);
+    for (int i = 0; i < elems16<T>; ++i) f[i] = to_f(e[i]);
 }
 template <typename T>
-__device__ __forceinline__ void store16(T* p, const float (&f)[Vec<T>::N]) {
+__device__ __forceinline__ void store16(T* p, const float (&f)[elems16<T>]) {
     uint4 raw;
     T* e = reinterpret_cast<T*>(&raw);
 #pragma unroll
-    for (int i = 0; i < Vec<T>::N; ++i) e[i] = from_f<T>(f[i]);
+    for (int i = 0; i < elems16<T>; ++i) e[i] = from_f<T>(f[i]);
     *reinterpret_cast<uint4*>(p) = raw;
 }
 
@@ -69,7 +66,7 @@ __device__ __forceinline__ void store16(T* p, const float (&f)[Vec<T>::N]) {
 template <typename T> struct Peel {
     int head, nb, tail0, nscalar;
     __device__ __forceinline__ Peel(const T* row, int V) {
-        constexpr int N = Vec<T>::N;
+        constexpr int N = elems16<T>;
         const int h = (int)(((16 - (int)((uintptr_t)row & 15)) & 15) / (int)sizeof(T));
         head = h < V ? h : V; nb = (V - head) / N; tail0 = head + nb * N; nscalar = head + (V - tail0);
     }
@@ -86,7 +83,7 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
 // block-wide (max, sum-exp) of one row; result broadcast to every thread. red = 2*8 floats of LDS.
 template <typename T, bool VEC>
 __device__ __forceinline__ void row_max_sum(const T* row, int V, float* red, float& m_out, float& s_out) {
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     float m = NEG_INF, s = 0.f;
     if (VEC) {
         for (int v = threadIdx.x * N; v < V; v += blockDim.x * N) {
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(256) void lsg_fwd_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* red = smem;                // 16 floats
     float* stage = smem + 16;         // [S][RT]
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     const int tiles_per_b = (L + RT - 1) / RT;
     const long ntiles = (long)B * tiles_per_b;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -222,7 +219,7 @@ __global__ __launch_bounds__(256) void lsg_fwd_reg_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* red = smem;                // 2 x 16 floats (alternating per row)
     float* stage = smem + 32;         // [S][RT]
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     const int tid = threadIdx.x;
     const int tiles_per_b = (L + RT - 1) / RT;
     const long ntiles = (long)B * tiles_per_b;
@@ -358,7 +355,7 @@ __global__ __launch_bounds__(256) void lsg_fwd_regl_kernel(
     float* red = smem;                // 2 x 16 floats (alternating per row)
     float* stage = smem + 32;         // [S][RT]
     T* rowbuf = reinterpret_cast<T*>(stage + (size_t)S * RT);     // [V] raw logits of the current row
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     const int tid = threadIdx.x;
     const int tiles_per_b = (L + RT - 1) / RT;
     const long ntiles = (long)B * tiles_per_b;
@@ -482,7 +479,7 @@ __global__ __launch_bounds__(256) void lsg_bwd_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* red = smem;            // 16 floats
     float* delta = smem + 16;     // [V]
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     for (int v = threadIdx.x; v < V; v += blockDim.x) delta[v] = 0.f;
     __syncthreads();
     const long nrows = (long)B * L;
@@ -554,7 +551,7 @@ __global__ __launch_bounds__(256) void lsg_bwd_reg_kernel(
     float* red = smem;                // 16 floats
     float* delta = smem + 16;         // [V]   scatter image of the current row
     float* gt = delta + V;            // [S][RT]
-    constexpr int N = Vec<T>::N;
+    constexpr int N = elems16<T>;
     const int tid = threadIdx.x;
     for (int v = tid; v < V; v += 256) delta[v] = 0.f;
     const int tiles_per_b = (L + RT - 1) / RT;
@@ -846,7 +843,7 @@ extern "C" int dsp_logsoftmax_gather_plan(int backward, int dtype, int B, int L,
     out[0] = -1; out[1] = out[2] = out[3] = out[4] = out[5] = 0;
     if (B == 0 || L == 0) return DSP_OK;
     LsgPlan p;
-    const int esize = dtype == DSP_F32 ? 4 : 2;
+    const int esize = elem_size(dtype);
     const int rc = backward ? lsg_plan_bwd(esize, B, L, V, S, aligned16 != 0, p) : lsg_plan_fwd(esize, B, L, V, S, aligned16 != 0, p);
     if (rc) return rc;
     out[0] = p.family; out[1] = p.vec; out[2] = p.nv; out[3] = p.rt; out[4] = p.grid; out[5] = (int)p.lds;

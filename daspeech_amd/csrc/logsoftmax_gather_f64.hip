@@ -73,12 +73,6 @@ __device__ __forceinline__ void online_merge64(double& m, double& s, double m2, 
     m = nm;
 }
 
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // block-wide (max, sum-exp) of one row; result broadcast to every thread.  red = 2 x 8 doubles of LDS.
 __device__ __forceinline__ void row_max_sum64(const double* row, int V, const Peel64& pl, double* red, double& m_out, double& s_out) {
     const int tid = threadIdx.x;
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256) void lsg64_fwd_reg_kernel(
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < NV; ++k) { v[k].x = exp(v[k].x - mm); v[k].y = exp(v[k].y - mm); s += v[k].x + v[k].y; }      // padding lanes: exp(-inf) = 0
-            s = wave_sum64(s);
+            s = wave_sum(s);
             if ((tid & 63) == 0) red[8 + (tid >> 6)] = s;
             __syncthreads();
             s = (red[8] + red[9]) + (red[10] + red[11]);
@@ -312,7 +306,7 @@ __global__ __launch_bounds__(256) void lsg64_bwd_kernel(
                     if (t >= lo && t < hi) atomicAdd(&delta[(int)t - lo], gv);
                 }
                 if (lo == 0) {
-                    gs = wave_sum64(gs);
+                    gs = wave_sum(gs);
                     if ((tid & 63) == 0) red[tid >> 6] = gs;
                 }
                 __syncthreads();

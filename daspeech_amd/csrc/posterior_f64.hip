@@ -36,26 +36,15 @@ constexpr int P64_TM = 32;             // output rows per workgroup
 constexpr int P64_KC = 16;             // reduction chunk
 constexpr int P64_AS = P64_TM + 2;     // row stride of the P tile [KC][TM + 2]: 16-byte aligned rows, conflict-free writes along k
 
-__device__ __forceinline__ double p64_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double p64_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // log-sum-exp of one row of alpha + beta by one wave; -inf for a row without a finite entry (or with a +inf / NaN maximum)
 __device__ __forceinline__ double p64_row_lse(const double* __restrict__ a, const double* __restrict__ b, int L, int lane) {
     double m = P64_NEG;
     for (int j = lane; j < L; j += 64) m = fmax(m, a[j] + b[j]);
-    m = p64_wave_max(m);
+    m = wave_max(m);
     if (!(m > P64_NEG) || isinf(m)) return P64_NEG;
     double s = 0.0;
     for (int j = lane; j < L; j += 64) s += exp(a[j] + b[j] - m);
-    s = p64_wave_sum(s);
+    s = wave_sum(s);
     return m + log(s);
 }
 

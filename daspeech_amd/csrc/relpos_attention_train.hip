@@ -100,7 +100,7 @@ __device__ __forceinline__ void ra_load_bias(float* bias, const void* bu, const 
     for (int c = lane; c < 128; c += 64) {
         const void* p = c < 64 ? bu : bv;
         const int at = h * 64 + (c & 63);
-        bias[c] = pdtype == DSP_F32 ? ((const float*)p)[at] : (pdtype == DSP_F16 ? __half2float(((const __half*)p)[at]) : __bfloat162float(((const __hip_bfloat16*)p)[at]));
+        bias[c] = param_load(p, pdtype, at);
     }
 }
 
@@ -130,19 +130,6 @@ __device__ __forceinline__ void ra_scores(const ra_u16* Qu, const ra_u16* Qv, co
         s[reg] = ok ? (ac[reg] + Gs[il * RA_PG + 31 - il + jl]) * 0.125f : NEG_INF;
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ float ra_half_max(float v)
-{
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float ra_half_sum(float v)
-{
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __device__ __forceinline__ uint64_t ra_elem(int b, int h, int H, int T, int Tp, int i, int j)
@@ -212,11 +199,11 @@ __global__ __launch_bounds__(64) void ra_fwd_kernel(const E* __restrict__ q, con
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int il = RA_ROW(reg, hi);
-            const float mn = fmaxf(m[reg], ra_half_max(s[reg]));
+            const float mn = fmaxf(m[reg], lanes_max<32>(s[reg]));
             const float ms = mn == NEG_INF ? 0.f : mn;                      // nothing but masked keys so far: every weight is 0
             const float a = expf(m[reg] - ms);
             float p = expf(s[reg] - ms);
-            l[reg] = fmaf(l[reg], a, ra_half_sum(p));
+            l[reg] = fmaf(l[reg], a, lanes_sum<32>(p));
             m[reg] = mn;
             o0[reg] *= a; o1[reg] *= a;
             if (thr) p *= kf[reg];
@@ -298,9 +285,8 @@ __device__ __forceinline__ void ra_store_t(ra_u16* dst, const float (&x)[16], in
     const int jl = lane & 31, hi = lane >> 5;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const uint32_t lo = (uint32_t)Ra<E>::bits(x[4 * g]) | ((uint32_t)Ra<E>::bits(x[4 * g + 1]) << 16);
-        const uint32_t hi2 = (uint32_t)Ra<E>::bits(x[4 * g + 2]) | ((uint32_t)Ra<E>::bits(x[4 * g + 3]) << 16);
-        *reinterpret_cast<uint2*>(dst + jl * RA_P32 + 8 * g + 4 * hi) = make_uint2(lo, hi2);
+        const float q[4] = {x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
+        store_f<E, 4>(reinterpret_cast<E*>(dst + jl * RA_P32 + 8 * g + 4 * hi), q);
     }
 }
 
@@ -526,9 +512,7 @@ __global__ __launch_bounds__(256) void ra_bias_merge_kernel(const float* __restr
     if (!o) return;
     float acc = 0.f;
     for (long x = 0; x < nchunks; ++x) acc += part[x * C + c];
-    if (pdtype == DSP_F32) ((float*)o)[c] = acc;
-    else if (pdtype == DSP_F16) ((__half*)o)[c] = __float2half(acc);
-    else ((__hip_bfloat16*)o)[c] = __float2bfloat16(acc);
+    param_store(o, pdtype, c, acc);
 }
 
 // what the entry points check; 1: nothing to do (B == 0), 0: go on, < 0: refused
@@ -553,11 +537,7 @@ static size_t ra_part_bias_floats(long B, long T, long H) { return (size_t)(B * 
 
 using namespace dsp;
 
-#define RA_DISPATCH(dtype, ...)                                       \
-    do {                                                              \
-        if ((dtype) == DSP_F16) { using E = __half; __VA_ARGS__; }    \
-        else { using E = __hip_bfloat16; __VA_ARGS__; }               \
-    } while (0)
+#define RA_DISPATCH(dtype, ...) DSP_DISPATCH_ELEM_16(dtype, E, __VA_ARGS__)
 
 extern "C" size_t dsp_relpos_attention_train_workspace_bytes(int B, int T, int H)
 {

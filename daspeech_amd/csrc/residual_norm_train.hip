@@ -27,69 +27,6 @@ constexpr int RN_MIN_W = 64 * RN_WAVES / RN_CHUNK;       // fewest lanes per row
 constexpr int RN_FWD_PASSES = 2;                          // forward: passes of the four waves per workgroup (no partials: small workgroups)
 static_assert(RN_CHUNK % RN_WAVES == 0 && RN_MIN_W >= 1 && 64 % RN_MIN_W == 0, "a chunk is a whole number of wave passes");
 
-// ---- one 16-byte group of columns <-> floats
-template <typename T> struct RnVec { static constexpr int V = 16 / (int)sizeof(T); };
-template <typename T> __device__ __forceinline__ void ldv(const T* __restrict__ p, float (&f)[RnVec<T>::V]);
-template <> __device__ __forceinline__ void ldv<float>(const float* __restrict__ p, float (&f)[4])
-{
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-template <> __device__ __forceinline__ void ldv<__half>(const __half* __restrict__ p, float (&f)[8])
-{
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __half2float(__ushort_as_half((unsigned short)(w[i] & 0xffffu)));
-        f[2 * i + 1] = __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
-    }
-}
-template <> __device__ __forceinline__ void ldv<__hip_bfloat16>(const __hip_bfloat16* __restrict__ p, float (&f)[8])
-{
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint32_t rn_bits16(__half v) { return (uint32_t)__half_as_ushort(v); }
-__device__ __forceinline__ uint32_t rn_bits16(__hip_bfloat16 v) { unsigned short u; __builtin_memcpy(&u, &v, 2); return (uint32_t)u; }
-template <typename T> __device__ __forceinline__ void stv(T* __restrict__ p, const float (&f)[8])
-{
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = rn_bits16(from_f<T>(f[2 * i])) | (rn_bits16(from_f<T>(f[2 * i + 1])) << 16);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-}
-__device__ __forceinline__ void stv(float* __restrict__ p, const float (&f)[4])
-{
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-}
-// V parameters (gamma, beta, bias) from column c on: in the data dtype, or in fp32
-template <typename T> __device__ __forceinline__ void ld_param(const void* __restrict__ p, int pdtype, int c, float (&f)[RnVec<T>::V])
-{
-    constexpr int V = RnVec<T>::V;
-    if (sizeof(T) == 4 || pdtype != DSP_F32) { ldv<T>((const T*)p + c, f); return; }
-#pragma unroll
-    for (int j = 0; j < V / 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4*>((const float*)p + c + 4 * j);
-        f[4 * j] = v.x; f[4 * j + 1] = v.y; f[4 * j + 2] = v.z; f[4 * j + 3] = v.w;
-    }
-}
-__device__ __forceinline__ void st_param(void* p, int pdtype, int c, float v)
-{
-    if (pdtype == DSP_F32) ((float*)p)[c] = v;
-    else if (pdtype == DSP_F16) ((__half*)p)[c] = __float2half(v);
-    else ((__hip_bfloat16*)p)[c] = __float2bfloat16(v);
-}
-
-// sum over the W lanes of a row (W a power of two): a butterfly, every lane gets the same bits
-__device__ __forceinline__ float row_sum(float v, int W)
-{
-    for (int o = W >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------- forward
 template <typename T, int NG>
 __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, const T* __restrict__ res, const void* __restrict__ bias,
@@ -97,7 +34,7 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
                                                      float alpha, float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset,
                                                      T* __restrict__ s_out, T* __restrict__ y, float* __restrict__ stats, long R, int C, int W)
 {
-    constexpr int V = RnVec<T>::V;
+    constexpr int V = elems16<T>;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rpw = 64 / W, sub = lane / W, l = lane % W, G = C / V;
     const float invC = 1.f / (float)C;
@@ -110,9 +47,9 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
 #pragma unroll
         for (int i = 0; i < V; ++i) { ga[k][i] = 0.f; be[k][i] = 0.f; bi[k][i] = 0.f; }
         if (cv[k]) {
-            ld_param<T>(gamma, pdtype, c, ga[k]);
-            ld_param<T>(beta, pdtype, c, be[k]);
-            if (h && bias) ld_param<T>(bias, pdtype, c, bi[k]);
+            param_load_f<T>(gamma, pdtype, c, ga[k]);
+            param_load_f<T>(beta, pdtype, c, be[k]);
+            if (h && bias) param_load_f<T>(bias, pdtype, c, bi[k]);
         }
     }
 #pragma unroll 1
@@ -127,10 +64,10 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
             for (int i = 0; i < V; ++i) v[k][i] = 0.f;
             if (rv && cv[k]) {
                 const size_t at = (size_t)row * C + (size_t)(k * 64 + l) * V;
-                ldv<T>(res + at, v[k]);
+                load_f<T>(res + at, v[k]);
                 if (h) {
                     float hv[V];
-                    ldv<T>(h + at, hv);
+                    load_f<T>(h + at, hv);
                     if (thr) {
                         bool keep[V];
                         keep_flags<V>((uint64_t)at, seed, offset, thr, keep);
@@ -142,13 +79,13 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
                     }
 #pragma unroll
                     for (int i = 0; i < V; ++i) v[k][i] = to_f(from_f<T>(v[k][i]));      // the statistics are those of s as stored
-                    stv(s_out + at, v[k]);
+                    store_f(s_out + at, v[k]);
                 }
 #pragma unroll
                 for (int i = 0; i < V; ++i) sum += v[k][i];
             }
         }
-        float mean = row_sum(sum, W) * invC;
+        float mean = lanes_sum(sum, W) * invC;
         // the mean in two steps, as layer_norm_kernel (conformer_ops.hip): the centred values carry the rounding that the first sum lost
         float e = 0.f;
 #pragma unroll
@@ -157,7 +94,7 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
 #pragma unroll
                 for (int i = 0; i < V; ++i) { v[k][i] -= mean; e += v[k][i]; }
             }
-        const float corr = row_sum(e, W) * invC;
+        const float corr = lanes_sum(e, W) * invC;
         mean += corr;
         float q = 0.f;
 #pragma unroll
@@ -166,7 +103,7 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
 #pragma unroll
                 for (int i = 0; i < V; ++i) { v[k][i] -= corr; q = fmaf(v[k][i], v[k][i], q); }
             }
-        const float rstd = 1.f / sqrtf(row_sum(q, W) * invC + eps);
+        const float rstd = 1.f / sqrtf(lanes_sum(q, W) * invC + eps);
         if (rv) {
 #pragma unroll
             for (int k = 0; k < NG; ++k)
@@ -174,7 +111,7 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
                     float o[V];
 #pragma unroll
                     for (int i = 0; i < V; ++i) o[i] = fmaf(v[k][i] * rstd, ga[k][i], be[k][i]);
-                    stv(y + (size_t)row * C + (size_t)(k * 64 + l) * V, o);
+                    store_f(y + (size_t)row * C + (size_t)(k * 64 + l) * V, o);
                 }
             if (l == 0) *reinterpret_cast<float2*>(stats + 2 * row) = make_float2(mean, rstd);
         }
@@ -188,7 +125,7 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
                                                      float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset, T* __restrict__ dh,
                                                      T* __restrict__ dres, float* __restrict__ part, int want_dh, long R, int C, int W)
 {
-    constexpr int V = RnVec<T>::V;
+    constexpr int V = elems16<T>;
     __shared__ float red[RN_WAVES][NG * 64 * V];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rpw = 64 / W, sub = lane / W, l = lane % W, G = C / V;
@@ -200,7 +137,7 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
         cv[k] = k * 64 + l < G;
 #pragma unroll
         for (int i = 0; i < V; ++i) { ga[k][i] = 0.f; ag[k][i] = 0.f; ab[k][i] = 0.f; ah[k][i] = 0.f; }
-        if (cv[k] && dy) ld_param<T>(gamma, pdtype, (k * 64 + l) * V, ga[k]);
+        if (cv[k] && dy) param_load_f<T>(gamma, pdtype, (k * 64 + l) * V, ga[k]);
     }
     const int passes = RN_CHUNK / (RN_WAVES * rpw);
 #pragma unroll 1
@@ -218,8 +155,8 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
             for (int i = 0; i < V; ++i) { xh[k][i] = 0.f; gy[k][i] = 0.f; }
             if (rv && cv[k] && dy) {
                 const size_t at = (size_t)row * C + (size_t)(k * 64 + l) * V;
-                ldv<T>(s + at, xh[k]);
-                ldv<T>(dy + at, gy[k]);
+                load_f<T>(s + at, xh[k]);
+                load_f<T>(dy + at, gy[k]);
 #pragma unroll
                 for (int i = 0; i < V; ++i) {
                     xh[k][i] = (xh[k][i] - mean) * rstd;
@@ -228,7 +165,7 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
                 }
             }
         }
-        if (dy) { a = row_sum(a, W) * invC; b = row_sum(b, W) * invC; }      // kernel-uniform
+        if (dy) { a = lanes_sum(a, W) * invC; b = lanes_sum(b, W) * invC; }      // kernel-uniform
         if (rv) {
 #pragma unroll
             for (int k = 0; k < NG; ++k)
@@ -237,14 +174,14 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
                     float g[V];
 #pragma unroll
                     for (int i = 0; i < V; ++i) g[i] = 0.f;
-                    if (ds) ldv<T>(ds + at, g);
+                    if (ds) load_f<T>(ds + at, g);
 #pragma unroll
                     for (int i = 0; i < V; ++i) {
                         g[i] = fmaf(rstd, gy[k][i] * ga[k][i] - a - xh[k][i] * b, g[i]);
                         ag[k][i] = fmaf(gy[k][i], xh[k][i], ag[k][i]);
                         ab[k][i] += gy[k][i];
                     }
-                    if (dres) stv(dres + at, g);
+                    if (dres) store_f(dres + at, g);
                     if (want_dh) {
                         if (thr) {
                             bool keep[V];
@@ -257,7 +194,7 @@ __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, c
                         }
 #pragma unroll
                         for (int i = 0; i < V; ++i) ah[k][i] += g[i];
-                        if (dh) stv(dh + at, g);
+                        if (dh) store_f(dh + at, g);
                     }
                 }
         }
@@ -319,7 +256,7 @@ __global__ __launch_bounds__(256) void rn_bwd_merge_kernel(const float* __restri
     if (ty != 0 || e >= E) return;
     const int qn = e / C, c = e % C;
     void* out = qn == 0 ? dgamma : (qn == 1 ? dbeta : dbias);
-    if (out) st_param(out, pdtype, c, acc);
+    if (out) param_store(out, pdtype, c, acc);
 }
 
 // ---------------------------------------------------------------- the mask alone, as bytes
@@ -333,14 +270,13 @@ __global__ __launch_bounds__(256) void rn_keep_mask_kernel(uint64_t seed, uint64
         if (4 * g + i < n) out[4 * g + i] = keep[i] ? 1 : 0;
 }
 
-static int rn_es(int dtype) { return dtype == DSP_F32 ? 4 : ((dtype == DSP_F16 || dtype == DSP_BF16) ? 2 : 0); }
 static long rn_chunks(long R) { return (R + RN_CHUNK - 1) / RN_CHUNK; }
 
 // what both entry points check; 1: nothing to do (R == 0), 0: go on, < 0: refused
 static int rn_check(const char* who, int act_dtype, int param_dtype, long R, int C)
 {
-    const int es = rn_es(act_dtype);
-    if (!es || !rn_es(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
+    const int es = elem_size(act_dtype);
+    if (!es || !elem_size(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (h, residual, s, y and their gradients) / %d (gamma, beta, bias: the same, or fp32)", who, act_dtype, param_dtype);
         return DSP_EINVAL;
     }
@@ -371,14 +307,8 @@ using namespace dsp;
     }
 // C <= 2048: at most 8 groups of four fp32 per lane, 4 groups of eight 16-bit elements
 #define RN_DISPATCH(dtype, NG_, ...)                                             \
-    switch (dtype) {                                                             \
-        case DSP_F32:                                                            \
-            if (NG_ == 8) { using E = float; constexpr int NGC = 8; __VA_ARGS__; } \
-            else { using E = float; RN_NG_SWITCH4(NG_, __VA_ARGS__); }           \
-            break;                                                               \
-        case DSP_F16: { using E = __half; RN_NG_SWITCH4(NG_, __VA_ARGS__); } break; \
-        default: { using E = __hip_bfloat16; RN_NG_SWITCH4(NG_, __VA_ARGS__); } break; \
-    }
+    if ((dtype) == DSP_F32 && NG_ == 8) { using E = float; constexpr int NGC = 8; __VA_ARGS__; } \
+    else DSP_DISPATCH_ELEM(dtype, E, RN_NG_SWITCH4(NG_, __VA_ARGS__))
 
 extern "C" size_t dsp_resnorm_train_workspace_bytes(int64_t R, int C)
 {
@@ -402,7 +332,7 @@ extern "C" int dsp_resnorm_train_fwd(const void* h, const void* residual, const 
         set_error("%s: tensors must be 16-byte aligned (stats: 8)", who); return DSP_EINVAL;
     }
     int W, NG;
-    rn_plan(C / (16 / rn_es(act_dtype)), W, NG);
+    rn_plan(C / (16 / elem_size(act_dtype)), W, NG);
     const long rows_per_wg = (long)RN_FWD_PASSES * RN_WAVES * (64 / W);
     const unsigned grid = (unsigned)((R + rows_per_wg - 1) / rows_per_wg);
     hipStream_t st = as_stream(stream);
@@ -435,7 +365,7 @@ extern "C" int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void*
         return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
     }
     int W, NG;
-    rn_plan(C / (16 / rn_es(act_dtype)), W, NG);
+    rn_plan(C / (16 / elem_size(act_dtype)), W, NG);
     const long nchunks = rn_chunks((long)R);
     float* part = sums ? (float*)workspace : (float*)nullptr;
     hipStream_t st = as_stream(stream);

@@ -1,4 +1,5 @@
-// split_frag.h — fragment addresses of the split-operand MFMA loops (conv1d_split.hip, hifigan_conv_f32.hip).
+// split_frag.h — the LDS chunk swizzle of the convolution / GEMM tiles (conv1d_split.hip, ffn_split.hip, hifigan_conv.hip, hifigan_conv_f32.hip)
+// and the fragment addresses of the split-operand MFMA loops (conv1d_split.hip, hifigan_conv_f32.hip).
 //
 // B fragments: the staged tile is [rows][CI] halves in 16-byte chunks, chunk q of row r stored at slot split_swz(r, q).  A K step (tap k,
 // 32-channel group c) reads, per 16-column tile j and plane (hi, lo), the chunk 4 c + lk of row  j * 16 + row0,  row0 = the lane's row of

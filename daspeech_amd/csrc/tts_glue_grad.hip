@@ -13,63 +13,6 @@ namespace dsp {
 constexpr int EG_CHUNK = DSP_EMBED_GRAD_CHUNK;        // rows of one bucket that one wave sums
 constexpr int GG_MAX_WG = 1024;                       // 4 waves each: a launch serves at most 4096 rows per trip of its grid-stride loop
 
-// ---- 32-bit words <-> floats for the three dtype codes
-template <typename T> struct Word;
-template <> struct Word<float> {
-    static constexpr int PER = 1;
-    static __device__ __forceinline__ void unpack(uint32_t w, float* f) { f[0] = __uint_as_float(w); }
-    static __device__ __forceinline__ uint32_t pack(const float* f) { return __float_as_uint(f[0]); }
-};
-template <> struct Word<__half> {
-    static constexpr int PER = 2;
-    static __device__ __forceinline__ void unpack(uint32_t w, float* f)
-    {
-        f[0] = __half2float(__ushort_as_half((unsigned short)(w & 0xffffu)));
-        f[1] = __half2float(__ushort_as_half((unsigned short)(w >> 16)));
-    }
-    static __device__ __forceinline__ uint32_t pack(const float* f)
-    {
-        return (uint32_t)__half_as_ushort(__float2half(f[0])) | ((uint32_t)__half_as_ushort(__float2half(f[1])) << 16);
-    }
-};
-template <> struct Word<__hip_bfloat16> {
-    static constexpr int PER = 2;
-    static __device__ __forceinline__ void unpack(uint32_t w, float* f) { f[0] = __uint_as_float(w << 16); f[1] = __uint_as_float(w & 0xffff0000u); }
-    static __device__ __forceinline__ uint32_t pack(const float* f)
-    {
-        const __hip_bfloat16 a = __float2bfloat16(f[0]), b = __float2bfloat16(f[1]);
-        unsigned short ua, ub;
-        __builtin_memcpy(&ua, &a, 2); __builtin_memcpy(&ub, &b, 2);
-        return (uint32_t)ua | ((uint32_t)ub << 16);
-    }
-};
-
-// V consecutive elements at a 16-byte aligned address, widened to float / rounded once from float
-template <typename T, int V> __device__ __forceinline__ void load_f(const T* __restrict__ p, float (&f)[V])
-{
-    constexpr int NQ = V * (int)sizeof(T) / 16;
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        const uint4 u = q[i];
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) Word<T>::unpack(w[j], &f[(i * 4 + j) * Word<T>::PER]);
-    }
-}
-template <typename T, int V> __device__ __forceinline__ void store_f(T* __restrict__ p, const float (&f)[V])
-{
-    constexpr int NQ = V * (int)sizeof(T) / 16;
-    uint4* q = reinterpret_cast<uint4*>(p);
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        uint32_t w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = Word<T>::pack(&f[(i * 4 + j) * Word<T>::PER]);
-        q[i] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
 static inline bool aligned16(const void* a, const void* b, size_t row_a, size_t row_b)
 {
     return (((uintptr_t)a | (uintptr_t)b | row_a | row_b) & 15) == 0;
@@ -113,13 +56,6 @@ __device__ __forceinline__ void wave_sum_rows(const TI* __restrict__ src, TO* __
     }
 }
 
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------- F6b': out = x + emb[bucketize(v)], idx kept; one wave per row
 template <typename T>
 __global__ __launch_bounds__(256) void bucketize_embed_add_fwd_kernel(const T* __restrict__ x, const float* __restrict__ v,
@@ -158,7 +94,7 @@ __global__ __launch_bounds__(256) void embed_count_kernel(const int32_t* __restr
     for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < K; k += gridDim.x * 4) {
         int c = 0;
         for (long r = lane; r < n; r += 64) c += (idx[r] == k);
-        c = wave_sum_int(c);
+        c = wave_sum(c);
         if (lane == 0) counts[k] = c;
     }
 }
@@ -172,7 +108,7 @@ __global__ __launch_bounds__(256) void embed_index_kernel(const int32_t* __restr
     for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < K; k += gridDim.x * 4) {
         int o = 0, cs = 0;
         for (int j = lane; j < k; j += 64) { const int c = counts[j]; o += c; cs += (c + EG_CHUNK - 1) / EG_CHUNK; }
-        o = wave_sum_int(o); cs = wave_sum_int(cs);
+        o = wave_sum(o); cs = wave_sum(cs);
         if (lane == 0) {
             offs[k] = o; cstart[k] = cs;
             if (k == K - 1) cstart[K] = cs + (counts[k] + EG_CHUNK - 1) / EG_CHUNK;
@@ -240,7 +176,6 @@ __global__ __launch_bounds__(256) void lr_bwd_kernel(const T* __restrict__ g, co
     }
 }
 
-static int es_of(int dtype) { return dtype == DSP_F32 ? 4 : ((dtype == DSP_F16 || dtype == DSP_BF16) ? 2 : 0); }
 static unsigned wave_grid(long waves) { const long g = (waves + 3) / 4; return (unsigned)(g < 1 ? 1 : (g > GG_MAX_WG ? GG_MAX_WG : g)); }
 static size_t eg_int_bytes(int64_t n, int K) { return (((size_t)3 * K + 1 + (size_t)n) * sizeof(int32_t) + 15) & ~(size_t)15; }
 static long eg_max_chunks(int64_t n, int K) { return (long)((n + EG_CHUNK - 1) / EG_CHUNK) + K; }
@@ -249,17 +184,12 @@ static long eg_max_chunks(int64_t n, int K) { return (long)((n + EG_CHUNK - 1) /
 
 using namespace dsp;
 
-#define GG_DISPATCH(dtype, CALL)                                         \
-    switch (dtype) {                                                     \
-        case DSP_F32: { using T = float; CALL; } break;                  \
-        case DSP_F16: { using T = __half; CALL; } break;                 \
-        default: { using T = __hip_bfloat16; CALL; } break;              \
-    }
+#define GG_DISPATCH(dtype, CALL) DSP_DISPATCH_ELEM(dtype, T, CALL)
 
 extern "C" int dsp_bucketize_embed_add_fwd(const void* x, int dtype, const float* v, const float* bins, int nb, const void* emb,
                                            void* out, int32_t* idx, int64_t n, int C, dsp_stream_t stream)
 {
-    const int es = es_of(dtype);
+    const int es = elem_size(dtype);
     if (!es) { set_error("bucketize_embed_add_fwd: unsupported dtype %d", dtype); return DSP_EINVAL; }
     if (n < 0 || nb < 0 || C < 1) { set_error("bucketize_embed_add_fwd: bad sizes"); return DSP_EINVAL; }
     if (n == 0) return DSP_OK;
@@ -280,7 +210,7 @@ extern "C" size_t dsp_embed_grad_workspace_bytes(int64_t n, int nb, int C)
 extern "C" int dsp_embed_grad(const void* grad_out, int dtype, const int32_t* idx, void* grad_emb, int64_t n, int nb, int C,
                               void* workspace, size_t workspace_bytes, dsp_stream_t stream)
 {
-    const int es = es_of(dtype);
+    const int es = elem_size(dtype);
     if (!es) { set_error("embed_grad: unsupported dtype %d", dtype); return DSP_EINVAL; }
     if (n < 0 || n > 0x7fffffffLL || nb < 0 || C < 1) { set_error("embed_grad: bad sizes"); return DSP_EINVAL; }
     if (!grad_emb) { set_error("embed_grad: null pointer"); return DSP_EINVAL; }
@@ -316,7 +246,7 @@ extern "C" int dsp_embed_grad(const void* grad_out, int dtype, const int32_t* id
 extern "C" int dsp_length_regulator_bwd(const void* grad_out, int dtype, const int64_t* cum, void* grad_x, int B, int N, int C, int maxlen,
                                         dsp_stream_t stream)
 {
-    const int es = es_of(dtype);
+    const int es = elem_size(dtype);
     if (!es || B < 0 || N < 0 || C < 1 || maxlen < 0) { set_error("length_regulator_bwd: bad arguments"); return DSP_EINVAL; }
     if (B == 0 || N == 0) return DSP_OK;
     if (!cum || !grad_x || (maxlen && !grad_out)) { set_error("length_regulator_bwd: null pointer"); return DSP_EINVAL; }
