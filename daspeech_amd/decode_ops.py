@@ -34,9 +34,13 @@ Host-side mirror of the reference code these replace:
                       relpos_attention_autograd_served says no (set_relpos_attention_hip(False): always); relpos_attention_checked is
                       internal to that layer
 No CPU fallback elsewhere: GPU tensors only.
+Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
+gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
+caller's torch lines run; the alignment gates of the C ABI are never reached with something they refuse.
 """
 import ctypes
 import math
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -58,6 +62,24 @@ def _mask_bytes(m: Optional[Tensor]) -> Optional[Tensor]:
     if m.dtype == torch.bool and m.is_contiguous():
         return m.view(torch.uint8)
     return m.to(torch.uint8).contiguous()
+
+
+def _on_grid(*ts) -> bool:
+    """every tensor given (None allowed) starts on a 16-byte boundary: the question the "not served" answers ask before a launch whose
+    kernel reads with 16-byte loads — a contiguous view at an odd storage offset (a parameter of a flattened buffer, x[:, 1:] of a
+    one-utterance batch) is off it"""
+    for t in ts:
+        if t is not None and t.data_ptr() % 16:
+            return False
+    return True
+
+
+def _dense16(t: Optional[Tensor]) -> Optional[Tensor]:
+    """t itself when it is contiguous and starts on a 16-byte boundary, else a dense copy (fresh allocations are on the grid): what the
+    wrappers without a torch path hand to the C ABI, whose gates refuse everything else.  The copy is a torch op, so gradients pass."""
+    if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0):
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 def _code(t: Tensor) -> int:
@@ -136,12 +158,12 @@ def extract_links(q: Tensor, k: Tensor, log_gates: Tensor, output_length: Tensor
     _gpu("extract_links", q, k, log_gates, output_length)
     if _links_f64(q, k, log_gates):
         return _links_f64_forward(q, k, log_gates, output_length, int(TR), dist_bias, False)[5]
-    qf = q.detach().to(torch.float32).contiguous()
-    kf = k.detach().to(torch.float32).contiguous()
-    gf = log_gates.detach().to(torch.float32).contiguous()
+    qf = _dense16(q.detach().to(torch.float32))
+    kf = _dense16(k.detach().to(torch.float32))
+    gf = _dense16(log_gates.detach().to(torch.float32))
     ol = output_length.to(torch.long).contiguous()
     B, L, H, CK = qf.shape
-    bias = None if dist_bias is None else dist_bias.detach().to(device=qf.device, dtype=torch.float32).contiguous()
+    bias = None if dist_bias is None else _dense16(dist_bias.detach().to(device=qf.device, dtype=torch.float32))
     lib = _lib.load()
     with torch.cuda.device(qf.device):
         links = torch.empty((B, L, TR), dtype=torch.float32, device=qf.device)
@@ -171,12 +193,12 @@ class _ExtractLinksFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, log_gates, output_length, TR, dist_bias):
-        qf = q.detach().to(torch.float32).contiguous()
-        kf = k.detach().to(torch.float32).contiguous()
-        gf = log_gates.detach().to(torch.float32).contiguous()
+        qf = _dense16(q.detach().to(torch.float32))
+        kf = _dense16(k.detach().to(torch.float32))
+        gf = _dense16(log_gates.detach().to(torch.float32))
         ol = output_length.to(torch.long).contiguous()
         B, L, H, CK = qf.shape
-        bias = None if dist_bias is None else dist_bias.detach().to(device=qf.device, dtype=torch.float32).contiguous()
+        bias = None if dist_bias is None else _dense16(dist_bias.detach().to(device=qf.device, dtype=torch.float32))
         lib = _lib.load()
         with torch.cuda.device(qf.device):
             links = torch.empty((B, L, TR), dtype=torch.float32, device=qf.device)
@@ -199,7 +221,7 @@ class _ExtractLinksFn(torch.autograd.Function):
     def backward(ctx, grad_links):
         qf, kf, gf, ol, links, stats, bias = ctx.saved_tensors
         B, L, H, CK = qf.shape
-        g = grad_links.detach().to(torch.float32).contiguous()
+        g = _dense16(grad_links.detach().to(torch.float32))
         lib = _lib.load()
         with torch.cuda.device(qf.device):
             dq, dk = torch.empty_like(qf), torch.empty_like(kf)
@@ -230,12 +252,12 @@ def _links_f64_forward(q, k, log_gates, output_length, TR: int, dist_bias, need_
     for t in (q, k, log_gates, dist_bias):
         if t is not None and not t.is_floating_point():
             raise RuntimeError(f"extract_links: expected floating-point tensors, got {t.dtype}")
-    qd = q.detach().to(torch.float64).contiguous()
-    kd = k.detach().to(torch.float64).contiguous()
-    gd = log_gates.detach().to(torch.float64).contiguous()
+    qd = _dense16(q.detach().to(torch.float64))
+    kd = _dense16(k.detach().to(torch.float64))
+    gd = _dense16(log_gates.detach().to(torch.float64))
     ol = output_length.to(device=qd.device, dtype=torch.long).contiguous()
     B, L, H, CK = qd.shape
-    bias = None if dist_bias is None else dist_bias.detach().to(device=qd.device, dtype=torch.float64).contiguous()
+    bias = None if dist_bias is None else _dense16(dist_bias.detach().to(device=qd.device, dtype=torch.float64))
     if tuple(kd.shape) != (B, L, H, CK) or tuple(gd.shape) != (B, L, H) or ol.numel() != B or (bias is not None and bias.numel() < TR):
         raise RuntimeError(f"extract_links: shapes q {tuple(qd.shape)} k {tuple(kd.shape)} log_gates {tuple(gd.shape)} out_len {tuple(ol.shape)}"
                            f" dist_bias {None if bias is None else tuple(bias.shape)} TR {TR}")
@@ -251,7 +273,7 @@ def _links_f64_forward(q, k, log_gates, output_length, TR: int, dist_bias, need_
 def _links_f64_backward(qd, kd, gd, ol, bias, links, stats, grad_links, TR: int):
     """dsp_extract_links_bwd_f64: (grad_q, grad_k, grad_log_gates) float64; grad_links of any floating dtype is widened"""
     B, L, H, CK = qd.shape
-    g = grad_links.detach().to(torch.float64).contiguous()
+    g = _dense16(grad_links.detach().to(torch.float64))
     lib = _lib.load()
     with torch.cuda.device(qd.device):
         dq, dk, dg = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(gd)
@@ -905,11 +927,11 @@ def dwconv_bn_silu(x: Tensor, conv_weight: Tensor, bn: "torch.nn.BatchNorm1d") -
     """SiLU(BatchNorm_eval(depthwise_conv1d(x))) on channels-last x [B,T,C] — the middle of the Conformer convolution module in
     eval mode (include/daspeech_decode.h: dsp_dwconv_bn_silu).  conv_weight is the Conv1d(C, C, K, groups=C) weight [C,1,K]."""
     _gpu("dwconv_bn_silu", x, conv_weight)
-    xf = x.detach().to(torch.float32).contiguous()
+    xf = _dense16(x.detach().to(torch.float32))            # .contiguous() alone keeps a contiguous view at an odd offset, which the C side refuses
     B, T, C = xf.shape
-    wt = conv_weight.detach().to(torch.float32).reshape(C, -1).contiguous()
+    wt = _dense16(conv_weight.detach().to(torch.float32).reshape(C, -1))
     K = wt.shape[1]
-    f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    f = lambda t: None if t is None else _dense16(t.detach().to(torch.float32))
     bw, bb, bm, bv = f(bn.weight), f(bn.bias), f(bn.running_mean), f(bn.running_var)
     lib = _lib.load()
     with torch.cuda.device(xf.device):
@@ -960,7 +982,9 @@ def dwconv_bn_silu_autograd_served(x: Tensor, conv: "torch.nn.Conv1d", bn: "torc
     if not (bn.training and bn.affine and bn.momentum is not None and bn.num_features == C):
         return False
     ts = _bn_tensors(bn)
-    return all(t.device == x.device for t in ts) and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts))
+    if not (all(t.device == x.device for t in ts) and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts))):
+        return False
+    return x.data_ptr() % 16 == 0                       # 16-byte loads of x: a contiguous view at an odd offset keeps the torch lines
 
 
 class _DwconvBnSiluTrainFn(torch.autograd.Function):
@@ -969,7 +993,7 @@ class _DwconvBnSiluTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, momentum, eps):
-        xx = x.detach().contiguous()
+        xx = _dense16(x.detach())
         B, T, C = xx.shape
         wt = w.detach().reshape(C, -1).contiguous()
         K = wt.shape[1]
@@ -998,7 +1022,7 @@ class _DwconvBnSiluTrainFn(torch.autograd.Function):
         B, T, C = xx.shape
         K = wt.shape[1]
         need = ctx.needs_input_grad
-        gy = grad_y.contiguous()
+        gy = _dense16(grad_y)                          # autograd may hand over a narrow of a larger gradient, or a broadcast
         lib = _lib.load()
         dev = xx.device
         with torch.cuda.device(dev):
@@ -1116,6 +1140,8 @@ def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln
         return False
     if not _resnorm_params_ok(x, ln, bias if h is not None else None):
         return False
+    if not _on_grid(x, h, ln.weight, ln.bias, bias if h is not None else None):         # 16-byte loads of every one of them
+        return False
     return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
 
 
@@ -1126,7 +1152,7 @@ def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
     if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
         return False
     dt = x.dtype
-    if not (x.is_cuda and dt in _RN_CODES and x.is_contiguous() and _resnorm_shape_ok(x)):
+    if not (x.is_cuda and dt in _RN_CODES and x.is_contiguous() and _resnorm_shape_ok(x) and x.data_ptr() % 16 == 0):
         return False
     C, dev, f32 = x.shape[-1], x.device, torch.float32
     for ln, bias in sites:
@@ -1137,6 +1163,8 @@ def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
         if (pd != dt and pd != f32) or b.dtype != pd or w.device != dev or b.device != dev:
             return False
         if bias is not None and (bias.dtype != pd or bias.device != dev or bias.dim() != 1 or bias.shape[0] != C):
+            return False
+        if not _on_grid(w, b, bias):
             return False
     return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
 
@@ -1200,10 +1228,10 @@ class _ResidualNormTrainFn(torch.autograd.Function):
             return (None,) * 10
         C = s.shape[-1]
         R = s.numel() // C
-        if ds is not None and not ds.is_contiguous():
-            ds = ds.contiguous()
-        if dy is not None and not dy.is_contiguous():
-            dy = dy.contiguous()
+        if ds is not None and (not ds.is_contiguous() or ds.data_ptr() % 16):       # a broadcast, a transpose, a narrow at an odd offset
+            ds = _dense16(ds)
+        if dy is not None and (not dy.is_contiguous() or dy.data_ptr() % 16):
+            dy = _dense16(dy)
         lib = _lib.load()
         dev = s.device
         idx, switch = _rn_launch_ctx(dev)
@@ -1246,8 +1274,8 @@ def residual_dropout_layer_norm_checked(h, residual, ln, bias=None, alpha=1.0, p
     trust what they are handed: any other caller uses residual_dropout_layer_norm_autograd."""
     if h is None:
         return _ResidualNormTrainFn.apply(None, residual, None, ln.weight, ln.bias, ln.eps, 1.0, 0.0, 0, 0)
-    if not h.is_contiguous():                  # the served rule looked at the residual; a block's output is contiguous, a view of it is copied
-        h = h.contiguous()
+    if not h.is_contiguous() or h.data_ptr() % 16:      # the served rule looked at the residual; a block's output is dense, a view of it is copied
+        h = _dense16(h)
     p_eff = float(p) if training else 0.0
     seed, offset = _reserve_dropout_stream(residual.device) if p_eff > 0.0 else (0, 0)
     out = _ResidualNormTrainFn.apply(h, residual, bias, ln.weight, ln.bias, ln.eps, float(alpha), p_eff, seed, offset)
@@ -1280,7 +1308,10 @@ def residual_dropout_layer_norm_autograd(h: Optional[Tensor], residual: Tensor, 
         raise RuntimeError(f"{name}: residual {tuple(residual.shape)} / h {None if h is None else tuple(h.shape)} / LayerNorm "
                            f"{tuple(ln.normalized_shape)} / p {p} are not served ([..., C] with C a multiple of the elements in 16 bytes, "
                            f"C <= {RESNORM_MAX_C}, 1 <= rows <= 2^24, h of the shape of residual, LayerNorm(C), 0 <= p < 1)")
-    return residual_dropout_layer_norm_checked(None if h is None else h.contiguous(), residual.contiguous(), ln, bias, alpha, p, training, return_sum)
+    if not _on_grid(w, b, bias if h is not None else None) or not (w.is_contiguous() and b.is_contiguous() and (bias is None or bias.is_contiguous())):
+        # parameters that are views (a flattened buffer, a broadcast): dense copies, gradients pass through
+        ln, bias = types.SimpleNamespace(weight=_dense16(w), bias=_dense16(b), eps=ln.eps), _dense16(bias)
+    return residual_dropout_layer_norm_checked(None if h is None else _dense16(h), _dense16(residual), ln, bias, alpha, p, training, return_sum)
 
 
 # ------------------------------------------------------------------------------------------------ relative-position attention under autograd (csrc/relpos_attention_train.hip)
@@ -1295,6 +1326,9 @@ def set_relpos_attention_hip(on: bool) -> bool:
     global RELPOS_ATTENTION_HIP
     old, RELPOS_ATTENTION_HIP = RELPOS_ATTENTION_HIP, bool(on)
     return old
+
+
+_RELPOS_LAYOUT = "layout"      # how _relpos_train_problem begins where a dense copy of q, k, v settles it
 
 
 def _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) -> Optional[str]:
@@ -1315,9 +1349,11 @@ def _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) -> Opti
     for t in (q, k, v):
         if (t.shape != q.shape or t.dtype != dt or t.device != dev or t.stride(2) != 1 or t.stride(1) != ld or (B > 1 and t.stride(0) != T * ld)
                 or t.data_ptr() % 16):
-            return "q, k, v need one shape, dtype and device, unit column stride, one common row stride and 16-byte alignment"
+            if t.shape != q.shape or t.dtype != dt or t.device != dev:
+                return "q, k, v need one shape, dtype and device"
+            return _RELPOS_LAYOUT + ": q, k, v need unit column stride, one common row stride and 16-byte alignment"
     if ld < C or ld % 8:
-        return f"row stride {ld} of q, k, v has to be a multiple of 8 elements"
+        return _RELPOS_LAYOUT + f": row stride {ld} of q, k, v has to be a multiple of 8 elements"
     if pos.dtype != dt or pos.device != dev or pos.numel() != (2 * T - 1) * C or pos.shape[-1] != C and tuple(pos.shape[-2:]) != (heads, 64):
         return f"pos has to hold the [2T-1, C] projected positions in {dt}"
     pd = bias_u.dtype
@@ -1386,8 +1422,8 @@ class _RelPosAttentionTrainFn(torch.autograd.Function):
         if do is None or not any(need[:6]):
             return (None,) * 11
         B, T, C = q.shape
-        if not do.is_contiguous():
-            do = do.contiguous()
+        if not do.is_contiguous() or do.data_ptr() % 16:
+            do = _dense16(do)
         lib = _lib.load()
         dev = q.device
         idx, switch = _rn_launch_ctx(dev)
@@ -1442,9 +1478,12 @@ def relpos_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias
     why = _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads)
     if why is None and not 0.0 <= p < 1.0:
         why = f"dropout probability has to be in [0, 1), got {p}"
+    if why is not None and why.startswith(_RELPOS_LAYOUT):       # views the kernels do not take as they are: dense copies, gradients pass through
+        q, k, v = _dense16(q), _dense16(k), _dense16(v)
+        why = _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads)
     if why is not None:
         raise RuntimeError(f"{name}: {why}")
-    ts = [t if t.data_ptr() % 16 == 0 else t.clone() for t in (pos.contiguous(), bias_u.contiguous(), bias_v.contiguous())]
+    ts = [_dense16(t) for t in (pos, bias_u, bias_v)]
     return relpos_attention_checked(q, k, v, ts[0], ts[1], ts[2], pad_mask, heads, p, training, return_lse)
 
 
@@ -1457,7 +1496,7 @@ class SplitConv1d:
         lib = _lib.load()
         Cout, Cin, K = weight.shape
         self.Cout, self.Cin, self.K = Cout, Cin, K
-        self.bias = None if bias is None else bias.detach().float().contiguous()
+        self.bias = None if bias is None else _dense16(bias.detach().float())      # the split-K reduction reads it with 16-byte loads
         step = Cin if Cin <= 512 else 512          # (256-channel slices with 128-row tiles: 125 vs 95 us for 2048 -> 256; r04 for the 512-wide decoder GEMMs: 3 - 10 % faster, not taken)
         assert Cin % step == 0 and step in (128, 256, 512) and Cout % 4 == 0 and K % 2 == 1, (Cin, Cout, K)
         self.step, self.nslices = step, Cin // step
@@ -1494,8 +1533,16 @@ class SplitConv1d:
         the split-K form of short sequences, as residual + alpha * act(bias) — finite either way."""
         _gpu("SplitConv1d", x)
         code = 1 if relu else self.ACT[act]
-        assert x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.Cin and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1)
+        assert x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.Cin
         B, T, _ = x.shape
+        # served as it is: unit column stride, rows pitched by a multiple of 4 floats with the batches dense over them, the base on the 16-byte
+        # grid (a contiguous tensor, a column slice of a fused projection); every other view is copied (there is no torch path from here)
+        if x.stride(2) != 1 or x.stride(1) % 4 or x.stride(1) < self.Cin or (B > 1 and x.stride(0) != T * x.stride(1)) or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        r = None                                             # the residual as the kernels take it: dense fp32 on the grid
+        if residual is not None:
+            r = _dense16(residual if residual.dtype == torch.float32 else residual.float())
+            assert tuple(r.shape) == (B, T, self.Cout)
         lib = _lib.load()
         with torch.cuda.device(x.device):
             st = _lib.current_stream_handle()
@@ -1505,29 +1552,17 @@ class SplitConv1d:
                 assert lens.dtype == torch.int32 and lens.is_cuda and lens.is_contiguous() and lens.numel() == B
             if tg:
                 # short sequence: split the reduction over slices x tap groups so that the launch fills the chip (dsp_conv1d_split_ksplit)
-                r = None
-                if residual is not None:
-                    r = residual if (residual.dtype == torch.float32 and residual.is_contiguous()) else residual.float().contiguous()
-                    assert tuple(r.shape) == (B, T, self.Cout)
                 nws = lib.dsp_conv1d_split_ksplit_workspace_bytes(B, T, self.Cout, self.nslices, tg)
                 ws = torch.empty((nws // 4,), dtype=torch.float32, device=x.device)
                 _lib.check(lib.dsp_conv1d_split_ksplit(_lib.ptr(x), x.stride(1), _lib.ptr(self.hi), _lib.ptr(self.lo), _lib.ptr(self.bias), _lib.ptr(r), self.Cout,
                                                        float(alpha), _lib.ptr(out), self.Cout, B, T, self.step, self.nslices, self.Cout, self.K, code, tg,
                                                        _lib.ptr(ws), nws, _lib.ptr(lens), int(slack), st), "dsp_conv1d_split_ksplit")
             elif lens is not None:
-                r = None
-                if residual is not None:
-                    r = residual if (residual.dtype == torch.float32 and residual.is_contiguous()) else residual.float().contiguous()
-                    assert tuple(r.shape) == (B, T, self.Cout)
                 assert lens.dtype == torch.int32 and lens.is_cuda and lens.is_contiguous() and lens.numel() == B
                 _lib.check(lib.dsp_conv1d_split_ragged(_lib.ptr(x), x.stride(1), _lib.ptr(self.hi), _lib.ptr(self.lo), _lib.ptr(self.bias), _lib.ptr(r),
                                                        self.Cout, float(alpha), _lib.ptr(out), self.Cout, B, T, self.step, self.nslices, self.Cout,
                                                        self.K, code, _lib.ptr(lens), int(slack), st), "dsp_conv1d_split_ragged")
             elif residual is not None or alpha != 1.0:
-                r = None
-                if residual is not None:
-                    r = residual if (residual.dtype == torch.float32 and residual.is_contiguous()) else residual.float().contiguous()
-                    assert tuple(r.shape) == (B, T, self.Cout)
                 _lib.check(lib.dsp_conv1d_split_residual(_lib.ptr(x), x.stride(1), _lib.ptr(self.hi), _lib.ptr(self.lo), _lib.ptr(self.bias), _lib.ptr(r),
                                                          self.Cout, float(alpha), _lib.ptr(out), self.Cout, B, T, self.step, self.nslices, self.Cout,
                                                          self.K, code, st), "dsp_conv1d_split_residual")
@@ -1561,8 +1596,8 @@ def split_linear(x: Tensor, lin, act: Optional[str] = None, residual: Optional[T
     served (caller falls back to F.linear): eval-mode inference in fp32 on the GPU, in_features 128 / 256 / 512 or a multiple of 512,
     out_features % 4 == 0, at least 128 rows.  The packed weight is cached on the module."""
     if (not SPLIT_GEMM or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or torch.is_autocast_enabled() or lin.weight.dtype != torch.float32
-            or x.dim() != 3 or not x.is_contiguous() or x.shape[0] * x.shape[1] < 128):
-        return None
+            or x.dim() != 3 or not x.is_contiguous() or x.shape[0] * x.shape[1] < 128 or x.data_ptr() % 16):
+        return None                                                # (x off the 16-byte grid: F.linear takes it; the residual is copied by SplitConv1d)
     wt = lin.weight                                                # nn.Linear [out,in] or a kernel-1 nn.Conv1d [out,in,1]
     if wt.dim() == 3 and wt.shape[2] != 1:
         return None
@@ -1611,7 +1646,8 @@ def linear_fused(x: Tensor, lins, lens: Optional[Tensor] = None, slack: int = 0)
     same reduction as in its own GEMM, so the values are bit-identical to separate calls; separate `linear` calls otherwise."""
     first = lins[0]
     if (SPLIT_GEMM and not first.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-            and x.dim() == 3 and x.is_contiguous() and x.shape[0] * x.shape[1] >= 128 and all(l.weight.dim() == 2 and l.weight.dtype == torch.float32 for l in lins)):
+            and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0 and x.shape[0] * x.shape[1] >= 128
+            and all(l.weight.dim() == 2 and l.weight.dtype == torch.float32 for l in lins)):
         key = tuple((l.weight.data_ptr(), l.weight._version, None if l.bias is None else l.bias._version) for l in lins)
         cache = getattr(first, "_dsp_cat", None)
         if cache is None or cache[0] != key:
@@ -1654,13 +1690,13 @@ def ffn_fused(x: Tensor, ln: Optional["torch.nn.LayerNorm"], lin1, lin2, act: st
         return None
     for n_ in (ln, post_ln):
         if n_ is not None and (tuple(n_.normalized_shape) != (C,) or n_.weight is None or n_.bias is None or n_.weight.dtype != torch.float32
-                               or n_.weight.data_ptr() % 16 or n_.bias.data_ptr() % 16):
+                               or n_.weight.data_ptr() % 16 or n_.bias.data_ptr() % 16 or not n_.weight.is_contiguous() or not n_.bias.is_contiguous()):
             return None
     lib = _lib.load()
     p1, p2 = _packed(lin1), _packed(lin2)
     r = None
     if residual is not None:
-        r = residual if (residual.dtype == torch.float32 and residual.is_contiguous()) else residual.float().contiguous()
+        r = _dense16(residual if residual.dtype == torch.float32 else residual.float())
         assert tuple(r.shape) == (B, T, C)
     with torch.cuda.device(x.device):
         nws = lib.dsp_ffn_split_workspace_bytes(B, T, C, H)
@@ -1684,6 +1720,7 @@ def linear_ln(x: Tensor, ln: "torch.nn.LayerNorm", lins, act: Optional[str] = No
     if (SPLIT_GEMM and not first.training and not ln.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
             and not torch.is_autocast_enabled() and x.dim() == 3 and x.is_contiguous() and x.shape[2] == 256 and x.shape[0] * x.shape[1] >= 128
             and tuple(ln.normalized_shape) == (256,) and ln.weight is not None and ln.bias is not None and ln.weight.dtype == torch.float32
+            and _on_grid(x, ln.weight, ln.bias) and ln.weight.is_contiguous() and ln.bias.is_contiguous()
             and all(l.weight.dim() in (2, 3) and l.weight.shape[1] == 256 and l.weight.dtype == torch.float32 and (l.weight.dim() == 2 or l.weight.shape[2] == 1)
                     for l in lins)):
         if len(lins) == 1:
@@ -1718,7 +1755,8 @@ def layer_norm(x: Tensor, ln: "torch.nn.LayerNorm") -> Tensor:
     """ln(x): the one-wave-per-row HIP kernel (dsp_layer_norm) in eval-mode fp32 inference on the GPU, torch otherwise."""
     C = x.shape[-1]
     if (SPLIT_GEMM and not ln.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-            and x.is_contiguous() and tuple(ln.normalized_shape) == (C,) and C % 4 == 0 and C <= 2048 and (ln.weight is None or ln.weight.dtype == torch.float32)):
+            and x.is_contiguous() and tuple(ln.normalized_shape) == (C,) and C % 4 == 0 and C <= 2048 and (ln.weight is None or ln.weight.dtype == torch.float32)
+            and _on_grid(x, ln.weight, ln.bias) and (ln.weight is None or (ln.weight.is_contiguous() and ln.bias.is_contiguous()))):
         lib = _lib.load()
         with torch.cuda.device(x.device):
             y = torch.empty_like(x)

@@ -82,9 +82,13 @@ class _OnGpu:
     """what dwconv_bn_silu_autograd_served reads of a tensor, answering as a contiguous GPU tensor would: the rule is pure argument
     inspection, so each unserved condition can be checked one at a time without a device"""
 
-    def __init__(self, shape, dtype, contiguous=True, cuda=True):
+    def __init__(self, shape, dtype, contiguous=True, cuda=True, offset=0):
         self.shape, self.dtype, self._c, self.is_cuda = torch.Size(shape), dtype, contiguous, cuda
         self.device = torch.device("cuda:0") if cuda else torch.device("cpu")
+        self._offset = offset                          # elements past a 16-byte boundary
+
+    def data_ptr(self):
+        return 0x7F0000001000 + self._offset * self.element_size()
 
     def dim(self):
         return len(self.shape)
@@ -129,6 +133,17 @@ def test_served_rule_says_no_to_each_unserved_condition():
     no(lambda x, c, b: (_OnGpu(x.shape, x.dtype, cuda=False), c, b))                      # CPU
     no(lambda x, c, b: (_OnGpu(x.shape, x.dtype, contiguous=False), c, b))                # not contiguous
     no(lambda x, c, b: (_OnGpu((2, 5, 2, 8), x.dtype), c, b))                             # not [B,T,C]
+    for dtype in (torch.float32, torch.float16, torch.bfloat16):                          # odd offset: contiguous, but off the 16-byte grid
+        for off in (1, 2, 3):
+            no(lambda x, c, b: (_OnGpu(x.shape, x.dtype, offset=off), c, b), dtype=dtype)
+        per = 16 // torch.empty((), dtype=dtype).element_size()
+        x, conv, bn = _served_args(dtype)
+        assert served(_OnGpu(x.shape, dtype, offset=per), conv, bn) and served(_OnGpu(x.shape, dtype, offset=3 * per), conv, bn)
+    # the parameters are read element by element: a flattened-buffer view of them is served (the C side asks nothing of them)
+    x, conv, bn = _served_args()
+    conv.weight = _OnGpu(conv.weight.shape, conv.weight.dtype, offset=1)
+    bn.weight, bn.running_var = _OnGpu((8,), torch.float32, offset=1), _OnGpu((8,), torch.float32, offset=3)
+    assert served(x, conv, bn)
     no(lambda x, c, b: None, C=6)                                                         # C % 4
     no(lambda x, c, b: None, dtype=torch.float16, C=12)                                   # C % 8 for the 16-bit dtypes
     no(lambda x, c, b: None, dtype=torch.bfloat16, C=4)

@@ -17,13 +17,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from tests import util_resnorm_ref as R
+from tests.util_4x_rule import ROUND, check_4x, f64, figure      # (names other test modules import from here)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 EPS = 1e-5
 SEED, OFFSET = 0x9E3779B97F4A7C15, 0x1_0000_0008          # both with a high word: all six words of key and counter matter
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-ROUND = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}      # one rounding of the dtype
 CH = R.CHUNK_ROWS
 # (leading dims, C): one row; idle lanes; a chunk less one, a chunk, a chunk and one (with a ragged number of 16-byte groups per lane);
 # several chunks and not a multiple of one; the widest row; a 3-D input; and the layer tests' width, where a wave holds 8 (16-bit) or 4 rows
@@ -58,10 +58,6 @@ def served_shape(shape, dtype):
 
 CASES = [(s, d) for s in SHAPES for d in DTYPES if served_shape(s, d)]
 CASE_IDS = ["R%s-C%d-%s" % ("x".join(map(str, s[0])), s[1], str(d).split(".")[1]) for s, d in CASES]
-
-
-def f64(t):
-    return t.detach().to(torch.float64).cpu().numpy()
 
 
 def poisoned(shape, dtype):
@@ -186,27 +182,6 @@ def reference(case, cfg, t, keep):
         if not cfg["bias"]:
             del out["dbias"]
     return out
-
-
-def figure(got, ref, scale=None):
-    """max|got - ref| / max|ref|; where the reference is zero throughout (dgamma / dbeta when y was not used) the absolute figure: the bound of
-    check_4x then admits next to nothing but the zeros themselves"""
-    sc = np.abs(ref).max() if scale is None else scale
-    return float(np.abs(f64(got) - ref).max() / (sc if sc > 0 else 1.0))
-
-
-def check_4x(tag, hip, tor, ref, scales=None):
-    """the 4 x rule on every tensor of `ref`; prints both figures.  scales: max|ref| replaced for the named tensors (see its users)"""
-    bad = []
-    for name, r in ref.items():
-        assert not np.isnan(f64(hip[name])).any(), f"{tag} {name}: NaN in the result (an element never written)"
-        sc = (scales or {}).get(name)
-        fh, ft = figure(hip[name], r, sc), figure(tor[name], r, sc)
-        bound = 4.0 * max(ft, ROUND[hip[name].dtype])
-        print(f"resnorm {tag} {name}: hip {fh:.3e} torch {ft:.3e} bound {bound:.3e}")
-        if not fh <= bound:
-            bad.append((name, fh, ft, bound))
-    assert not bad, f"{tag}: figure above 4 x torch's (name, hip, torch, bound): {bad}"
 
 
 _cache = {}

@@ -59,9 +59,13 @@ class _OnGpu:
     """what residual_dropout_layer_norm_served reads of a tensor, answering as a contiguous GPU tensor would: the rule is pure argument
     inspection, so each unserved condition can be checked one at a time without a device"""
 
-    def __init__(self, shape, dtype, contiguous=True, cuda=True, device="cuda:0"):
+    def __init__(self, shape, dtype, contiguous=True, cuda=True, device="cuda:0", offset=0):
         self.shape, self.dtype, self._c, self.is_cuda = torch.Size(shape), dtype, contiguous, cuda
         self.device = torch.device(device) if cuda else torch.device("cpu")
+        self._offset = offset                          # elements past a 16-byte boundary
+
+    def data_ptr(self):
+        return 0x7F0000001000 + self._offset * self.element_size()
 
     def dim(self):
         return len(self.shape)
@@ -108,6 +112,23 @@ def test_served_rule_says_no_to_each_unserved_condition():
     no(lambda a: a.__setitem__(0, _OnGpu(a[0].shape, a[0].dtype, cuda=False)))
     no(lambda a: a.__setitem__(1, _OnGpu(a[1].shape, a[1].dtype, contiguous=False)))           # not contiguous
     no(lambda a: a.__setitem__(0, _OnGpu(a[0].shape, a[0].dtype, contiguous=False)))
+    for dtype in (torch.float32, torch.float16, torch.bfloat16):                               # odd offset: contiguous, but off the 16-byte grid
+        for off in (1, 3):
+            no(lambda a: a.__setitem__(1, _OnGpu(a[1].shape, a[1].dtype, offset=off)), dtype=dtype)        # the residual
+            no(lambda a: a.__setitem__(0, _OnGpu(a[0].shape, a[0].dtype, offset=off)), dtype=dtype)        # h
+            no(lambda a: a.__setitem__(1, _OnGpu(a[1].shape, a[1].dtype, offset=off)), dtype=dtype, with_h=False)
+            no(lambda a: setattr(a[2], "weight", _OnGpu((8,), a[2].weight.dtype, offset=off)), dtype=dtype)    # the parameters: views of a flat buffer
+            no(lambda a: setattr(a[2], "bias", _OnGpu((8,), a[2].bias.dtype, offset=off)), dtype=dtype)
+            no(lambda a: setattr(a[2], "weight", _OnGpu((8,), torch.float32, offset=off)), dtype=dtype, param_dtype=torch.float32)
+            no(lambda a: a.__setitem__(3, _OnGpu((8,), a[3].dtype, offset=off)), dtype=dtype, with_bias=True)
+        per = 16 // torch.empty((), dtype=dtype).element_size()                               # a whole number of 16-byte units: on the grid again
+        a = list(_args(dtype, with_bias=True))
+        a[0], a[1], a[3] = _OnGpu(a[0].shape, dtype, offset=per), _OnGpu(a[1].shape, dtype, offset=2 * per), _OnGpu((8,), dtype, offset=per)
+        a[2].weight = _OnGpu((8,), dtype, offset=3 * per)
+        assert served(*a)
+    a = list(_args(with_h=False, with_bias=True))                                              # no h: `bias` is not read, so not asked about
+    a[3] = _OnGpu((8,), torch.float32, offset=1)
+    assert served(*a)
     no(lambda a: a.__setitem__(0, _OnGpu(a[0].shape, torch.float16)))                          # h of another dtype
     no(lambda a: a.__setitem__(0, _OnGpu((2, 5, 16), a[0].dtype)))                             # h of another shape
     no(lambda a: a.__setitem__(0, _OnGpu(a[0].shape, a[0].dtype, device="cuda:1")))            # h on another device
@@ -169,6 +190,14 @@ def test_the_layers_one_question_per_forward_agrees_with_the_per_site_rule():
     other = _Ln(8, torch.float16)
     other.weight = _OnGpu((8,), torch.float16, device="cuda:1")
     assert not both(x, ((other, None),))
+    for off in (1, 5):                                                                         # odd offsets: x, one site's weight, bias or `bias`
+        assert not both(_OnGpu((2, 5, 8), torch.float16, offset=off), (ok,))
+        for field in ("weight", "bias"):
+            odd = _Ln(8, torch.float16)
+            setattr(odd, field, _OnGpu((8,), torch.float16, offset=off))
+            assert not both(x, (ok, (odd, None)))
+        assert not both(x, (ok, (_Ln(8, torch.float16), _OnGpu((8,), torch.float16, offset=off))))
+    assert both(_OnGpu((2, 5, 8), torch.float16, offset=8), ((_Ln(8, torch.float16), _OnGpu((8,), torch.float16, offset=16)),))
     for bad in (_OnGpu((2, 5, 8), torch.float16, cuda=False), _OnGpu((2, 5, 8), torch.float16, contiguous=False), _OnGpu((2, 5, 8), torch.float64),
                 _OnGpu((2, 5, 12), torch.float16), _OnGpu((3, 2056), torch.float16), _OnGpu((8,), torch.float16)):
         assert not both(bad, ((_Ln(bad.shape[-1], bad.dtype), None),))
