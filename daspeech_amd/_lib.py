@@ -125,6 +125,11 @@ SIGNATURES = {
     "dsp_resnorm_train_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
                                        _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_i64, _c_int, _c_p]),
     "dsp_dropout_keep_mask": (_c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint, _c_p, _c_i64, _c_p]),
+    "dsp_act_dropout_train_workspace_bytes": (_c_sz, [_c_i64, _c_int]),
+    "dsp_act_dropout_train_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, _c_int, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64, _c_p,
+                                           _c_int, _c_int, _c_i64, _c_int, _c_p]),
+    "dsp_act_dropout_train_bwd": (_c_int, [_c_p, _c_p, ctypes.c_long, _c_p, _c_int, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
+                                           _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_i64, _c_int, _c_p]),
     "dsp_relpos_attention_train_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
     "dsp_relpos_attention_train_fwd": (_c_int, [_c_p, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64,
                                                 ctypes.c_uint64, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),

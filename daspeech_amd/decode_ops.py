@@ -27,6 +27,12 @@ Host-side mirror of the reference code these replace:
                       generator, column sums in a fixed order without float atomics; ConformerLayer / NATDecoderLayer / FFTLayer keep their
                       torch lines where residual_dropout_layer_norm_served says no (set_residual_norm_hip(False): always);
                       residual_dropout_layer_norm_checked / _sites_served are internal to those layers (no argument checks: not an API)
+  bias_act_dropout_autograd   the element-wise pass between the two GEMMs of a feed-forward block in TRAINING mode, y = dropout(act(h + bias))
+                      with act identity / relu / silu / gelu / glu (fairseq conformer_layer.py:140-146,86-90, transformer_layer.py:501-507,
+                      s2s_conformer_dag_fastspeech2.py:24-39), under autograd (csrc/act_dropout_train.hip): fp32 / fp16 / bf16, h and bias the only
+                      saved tensors (mask, activation and derivative recomputed), the bias gradient a fixed-order column sum without float
+                      atomics; the layers keep their torch lines where bias_act_dropout_served says no (set_act_dropout_hip(False): always);
+                      bias_act_dropout_checked / _sites_served are internal to those layers
   relpos_attention_autograd   fairseq espnet_multihead_attention.py RelPositionMultiHeadedAttention between the projections and linear_out, in
                       TRAINING mode under autograd (csrc/relpos_attention_train.hip): fp16 / bf16, scores + relative shift + mask + soft-max +
                       dropout + value product in one launch, a backward that recomputes the probabilities (no [B,h,T,T] tensor is kept) and
@@ -1312,6 +1318,213 @@ def residual_dropout_layer_norm_autograd(h: Optional[Tensor], residual: Tensor, 
         # parameters that are views (a flattened buffer, a broadcast): dense copies, gradients pass through
         ln, bias = types.SimpleNamespace(weight=_dense16(w), bias=_dense16(b), eps=ln.eps), _dense16(bias)
     return residual_dropout_layer_norm_checked(None if h is None else _dense16(h), _dense16(residual), ln, bias, alpha, p, training, return_sum)
+
+
+# ------------------------------------------------------------------------------------------------ bias + activation + dropout (and GLU) under autograd (csrc/act_dropout_train.hip)
+ACT_DROPOUT_HIP = True       # set_act_dropout_hip(False): the layers keep their torch lines between the GEMMs in training on every input
+ACTDROP_CHUNK_ROWS = 32      # DSP_ACTDROP_CHUNK_ROWS: rows per reduction chunk of the backward (one workspace partial each)
+ACTDROP_MAX_CIN = 8192       # DSP_ACTDROP_MAX_CIN
+ACT_CODES = {"identity": 0, "relu": 1, "silu": 2, "gelu": 3, "glu": 4}      # DSP_ACT_*
+
+
+def set_act_dropout_hip(on: bool) -> bool:
+    """Switch the HIP bias + activation + dropout operator of the training branches (ConformerLayer, NATDecoderLayer, FFNAdapter,
+    ConformerEncoder's input Linear) on or off; returns the previous setting.  Off: bias_act_dropout_served answers False and the torch
+    lines run."""
+    global ACT_DROPOUT_HIP
+    old, ACT_DROPOUT_HIP = ACT_DROPOUT_HIP, bool(on)
+    return old
+
+
+def _actdrop_pitch(h: Tensor) -> Optional[int]:
+    """the row pitch (elements) when h reads as rows [R, Cin] of unit column stride, all one pitch apart; None for any other layout"""
+    C = h.shape[-1]
+    if h.is_contiguous():
+        return C
+    if h.stride(-1) != 1 and C > 1:
+        return None
+    ld = span = None
+    for size, stride in zip(reversed(h.shape[:-1]), reversed(h.stride()[:-1])):
+        if size == 1:
+            continue
+        if ld is None:
+            ld = stride
+        elif stride != span:
+            return None
+        span = stride * size
+    return C if ld is None else ld
+
+
+def _actdrop_width_ok(C: int, act, itemsize: int) -> bool:
+    V = 16 // itemsize
+    return act in ACT_CODES and V <= C <= ACTDROP_MAX_CIN and C % (2 * V if act == "glu" else V) == 0
+
+
+def _actdrop_problem(h, bias, act) -> Optional[str]:
+    """None when dsp_act_dropout_train_fwd / _bwd take these tensors as they are, else what is in the way (a layout that a dense copy settles
+    begins with _RELPOS_LAYOUT)"""
+    if not (isinstance(h, Tensor) and h.dim() >= 2):
+        return "h has to be a [..., Cin] tensor of at least two dimensions"
+    if act not in ACT_CODES:
+        return f"unknown activation {act!r} (one of {', '.join(ACT_CODES)})"
+    dt = h.dtype
+    if dt not in _RN_CODES:
+        return f"h has to be fp32, fp16 or bf16, got {dt} (float64 is refused, never narrowed)"
+    C, V = h.shape[-1], 16 // h.element_size()
+    if not _actdrop_width_ok(C, act, h.element_size()) or h.numel() // C > (1 << 24):
+        return (f"h {tuple(h.shape)} with {act} is not served (Cin a multiple of {V} elements — twice that with glu —, Cin <= {ACTDROP_MAX_CIN}, "
+                f"at most 2^24 rows)")
+    if bias is not None:
+        if tuple(bias.shape) != (C,) or bias.device != h.device or (bias.dtype != dt and bias.dtype != torch.float32):
+            return f"bias has to be [{C}] on the device of h, in its dtype or in fp32, got {tuple(bias.shape)} {bias.dtype}"
+    if not h.is_cuda:
+        return "expected GPU tensors (HIP op, no CPU path)"
+    ld = _actdrop_pitch(h)
+    if ld is None or ld < C or ld % V or h.data_ptr() % 16:
+        return _RELPOS_LAYOUT + ": h needs unit column stride, one row pitch on the 16-byte grid and 16-byte alignment"
+    return None
+
+
+def bias_act_dropout_served(h: Tensor, bias: Optional[Tensor], act: str) -> bool:
+    """True when bias_act_dropout_autograd serves a training branch on these arguments as they are: the switch is on, autocast off, h a GPU
+    tensor [..., Cin] in fp32 / fp16 / bf16 with Cin a multiple of the elements in 16 bytes (twice that with glu) and at most 8192, unit
+    column stride, rows one common pitch apart (a multiple of those elements) and a 16-byte aligned start, bias None or [Cin] contiguous and
+    aligned in that dtype or fp32 on the same device, `act` one of ACT_CODES, and the current stream not capturing a graph (the random offset
+    is reserved on the host).  Everything else — CPU tensors, float64, another layout, an unknown activation — keeps the torch lines."""
+    if not ACT_DROPOUT_HIP or torch.is_autocast_enabled():
+        return False
+    if _actdrop_problem(h, bias, act) is not None:
+        return False
+    if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):       # the layer hands it over as it is
+        return False
+    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+def bias_act_dropout_sites_served(x: Tensor, sites) -> bool:
+    """bias_act_dropout_served(F.linear(x, W), bias, act) for every (Cin, bias, act) of `sites` — the activation sites of ONE layer, each
+    behind a bias-free F.linear of a tensor with the leading dimensions, dtype and device of the layer input x, whose result is a fresh dense
+    tensor [..., Cin] — asked BEFORE those products exist, with the questions about the switch, autocast, x and the stream asked once: a
+    layer asks this once per forward, and the step follows the host time of these sites."""
+    if not ACT_DROPOUT_HIP or torch.is_autocast_enabled():
+        return False
+    dt = x.dtype
+    if not (x.is_cuda and dt in _RN_CODES and x.dim() >= 2 and x.shape[-1] >= 1 and x.numel() // x.shape[-1] <= (1 << 24)):
+        return False
+    dev, size, f32 = x.device, x.element_size(), torch.float32
+    for C, bias, act in sites:
+        if not _actdrop_width_ok(C, act, size):
+            return False
+        if bias is not None and ((bias.dtype != dt and bias.dtype != f32) or bias.device != dev or bias.dim() != 1 or bias.shape[0] != C
+                                 or bias.data_ptr() % 16 or not bias.is_contiguous()):
+            return False
+    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+class _BiasActDropoutTrainFn(torch.autograd.Function):
+    """dsp_act_dropout_train_fwd / _bwd.  Saved for the backward: h and bias — no mask, no y, no u: the backward recomputes all three."""
+
+    @staticmethod
+    def forward(ctx, h, bias, act, ld, p, seed, offset):
+        Cin = h.shape[-1]
+        Cout = Cin // 2 if act == 4 else Cin
+        R = h.numel() // Cin
+        thr = dropout_threshold(p) if p > 0.0 else 0
+        scale = 1.0 / (1.0 - p) if thr else 1.0
+        lib = _lib.load()
+        dev = h.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            y = torch.empty(h.shape[:-1] + (Cout,), dtype=h.dtype, device=dev)
+            rc = lib.dsp_act_dropout_train_fwd(h.data_ptr(), ld, None if bias is None else bias.data_ptr(), act, scale, thr, seed, offset,
+                                               y.data_ptr(), _RN_CODES[h.dtype], _RN_CODES[(h if bias is None else bias).dtype], R, Cin,
+                                               torch._C._cuda_getCurrentRawStream(idx)) if R else 0
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_act_dropout_train_fwd")
+        ctx.save_for_backward(h, bias)
+        ctx.call = (act, ld, scale, thr, seed, offset)
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        h, bias = ctx.saved_tensors
+        act, ld, scale, thr, seed, offset = ctx.call
+        need = ctx.needs_input_grad
+        want_dh, want_db = need[0], bias is not None and need[1]
+        if dy is None or not (want_dh or want_db):
+            return (None,) * 7
+        Cin = h.shape[-1]
+        R = h.numel() // Cin
+        if not dy.is_contiguous() or dy.data_ptr() % 16:                    # a broadcast, a transpose, a narrow at an odd offset
+            dy = _dense16(dy)
+        lib = _lib.load()
+        dev = h.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            dh = torch.empty(h.shape, dtype=h.dtype, device=dev) if want_dh else None
+            dbias = torch.empty_like(bias) if want_db else None
+            rc = 0
+            if R:
+                nbytes = int(lib.dsp_act_dropout_train_workspace_bytes(R, Cin)) if want_db else 0
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+                ptr = lambda t: None if t is None else t.data_ptr()
+                rc = lib.dsp_act_dropout_train_bwd(dy.data_ptr(), h.data_ptr(), ld, ptr(bias), act, scale, thr, seed, offset, ptr(dh), ptr(dbias),
+                                                   ptr(ws), nbytes, _RN_CODES[h.dtype], _RN_CODES[(h if bias is None else bias).dtype], R, Cin,
+                                                   torch._C._cuda_getCurrentRawStream(idx))
+            elif dbias is not None:
+                dbias.zero_()                                              # no rows: the empty sum
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_act_dropout_train_bwd")
+        return dh, dbias, None, None, None, None, None
+
+
+def bias_act_dropout_checked(h, bias, act, p=0.0, training=True):
+    """INTERNAL to the package's layers: bias_act_dropout_autograd WITHOUT its argument checks, valid only on arguments that
+    bias_act_dropout_served / _sites_served accepted.  The kernels trust what they are handed: any other caller uses
+    bias_act_dropout_autograd."""
+    ld = _actdrop_pitch(h)
+    if ld is None or ld % (16 // h.element_size()) or h.data_ptr() % 16:      # _sites_served asked before h existed; a GEMM's output is dense, a view of it is copied
+        h, ld = h.clone(memory_format=torch.contiguous_format), h.shape[-1]
+    p_eff = float(p) if training else 0.0
+    seed, offset = _reserve_dropout_stream(h.device) if p_eff > 0.0 else (0, 0)
+    return _BiasActDropoutTrainFn.apply(h, bias, ACT_CODES[act], ld, p_eff, seed, offset)
+
+
+def bias_act_dropout_autograd(h: Tensor, bias: Optional[Tensor], act: str, p: float = 0.0, training: bool = True) -> Tensor:
+    """y = dropout(act(h + bias), p)  — the element-wise pass between the two GEMMs of a feed-forward block, differentiable w.r.t. h and
+    bias (include/daspeech_decode.h: dsp_act_dropout_train_fwd / _bwd).  act: "identity", "relu", "silu", "gelu" (erf form, as F.gelu) give
+    y of the shape of h; "glu" gives y [..., Cin/2] = u[..., :Cin/2] * sigmoid(u[..., Cin/2:]) with u = h + bias, as F.glu(dim=-1).
+    h [..., Cin] fp32 / fp16 / bf16 (float64 is refused, never narrowed) on the GPU, bias None or [Cin] in that dtype or fp32; a layout the
+    kernels do not take (another column stride, rows of several pitches, a start off the 16-byte grid) is copied to a dense tensor, gradients
+    pass through.  All arithmetic is fp32; y is rounded once.  Saved for the backward: h and bias only — u, the derivative and the mask are
+    recomputed.  Dropout is active with `training and p > 0`; the mask is the one dropout_keep_mask(seed, offset, p, (R, Cout), device) gives
+    for the R rows and Cout columns of y, for the (seed, offset) the call reserves from the default CUDA generator of h's device (its offset
+    moves on by 4; calls with p = 0 or training=False do not touch the generator) — the same generator state gives the same mask, successive
+    calls differ, torch.cuda.set_rng_state restores the stream.  The masks are not torch's F.dropout masks.  The bias gradient is summed in fp32
+    in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
+    name = "bias_act_dropout_autograd"
+    why = _actdrop_problem(h, bias, act)
+    if why is None and not 0.0 <= p < 1.0:
+        why = f"dropout probability has to be in [0, 1), got {p}"
+    if why is not None and why.startswith(_RELPOS_LAYOUT):       # a view the kernels do not take as it is: a dense copy, gradients pass through
+        h = h.clone(memory_format=torch.contiguous_format)
+        why = _actdrop_problem(h, bias, act)
+    if why is not None:
+        raise RuntimeError(f"{name}: {why}")
+    return bias_act_dropout_checked(h, _dense16(bias), act, p, training)
 
 
 # ------------------------------------------------------------------------------------------------ relative-position attention under autograd (csrc/relpos_attention_train.hip)

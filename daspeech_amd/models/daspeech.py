@@ -240,19 +240,29 @@ class ConformerLayer(nn.Module):
             (self.self_attn_layer_norm, self.ffn1["w_2"].bias), (self.conv_module["layer_norm"], None), (self.ffn2["layer_norm"], None),
             (self.final_layer_norm, self.ffn2["w_2"].bias)))
 
-    def _forward_train_resnorm(self, x, pos, pad_mask):
+    def _actdrop_served(self, x):
+        """one question per forward for the three activation sites (both SiLU + dropout passes with the bias of their w_1, and the GLU)"""
+        w1, w2 = self.ffn1["w_1"], self.ffn2["w_1"]
+        return decode_ops.bias_act_dropout_sites_served(x, (
+            (w1.out_features, w1.bias, "silu"), (w2.out_features, w2.bias, "silu"), (self.conv_module["pointwise_conv1"].out_channels, None, "glu")))
+
+    def _forward_train_resnorm(self, x, pos, pad_mask, ad):
         """The training branch with every `x = x + alpha * dropout(block(LayerNorm(x)))` boundary as one HIP operator (csrc/residual_norm_train.hip):
         the residual add, the dropout and the NEXT block's LayerNorm in one pass that returns both the sum and its norm; the bias of each
         w_2 rides in the operator, so that Linear runs without it and its bias gradient is one of the operator's column sums."""
         c, p, tr = self.conv_module, self.p, self.training
         rn = decode_ops.residual_dropout_layer_norm_checked
+        bad = decode_ops.bias_act_dropout_checked
 
         def ffn(m, y):                              # conformer_layer.py:140-146 up to w_2's product: dropout1 after the activation
+            if ad:                                  # bias + SiLU + dropout1 as one HIP operator (csrc/act_dropout_train.hip); w_1's bias rides in it
+                return F.linear(bad(F.linear(y, m["w_1"].weight), m["w_1"].bias, "silu", p, tr), m["w_2"].weight)
             return F.linear(_drop(F.silu(m["w_1"](y)), p, tr), m["w_2"].weight)
         y = self.ffn1["layer_norm"](x)             # a LayerNorm alone: the operator's h = None form is slower than torch's here (DESIGN §8)
         x, y = rn(ffn(self.ffn1, y), x, self.self_attn_layer_norm, bias=self.ffn1["w_2"].bias, alpha=0.5, p=p, training=tr)
         x, y = rn(self.self_attn(y, pos, pad_mask), x, c["layer_norm"], p=p, training=tr)                 # :267
-        y = F.glu(F.linear(y, c["pointwise_conv1"].weight.squeeze(-1)), dim=-1)
+        y = F.linear(y, c["pointwise_conv1"].weight.squeeze(-1))
+        y = bad(y, None, "glu") if ad else F.glu(y, dim=-1)
         if decode_ops.dwconv_bn_silu_autograd_served(y, c["depthwise_conv"], c["batch_norm"]):
             y = decode_ops.dwconv_bn_silu_autograd(y, c["depthwise_conv"].weight, c["batch_norm"])
         else:
@@ -264,17 +274,24 @@ class ConformerLayer(nn.Module):
         c = self.conv_module
         if self.training or torch.is_grad_enabled():
             p, tr = self.p, self.training
+            ad = self._actdrop_served(x)               # the element-wise passes between the GEMMs as HIP operators (same conditions)
             if self._resnorm_served(x):                # the block boundaries as HIP operators (GPU, fp32 / fp16 / bf16, no autocast)
-                return self._forward_train_resnorm(x, pos, pad_mask)
+                return self._forward_train_resnorm(x, pos, pad_mask, ad)
             # otherwise plain torch ops only (the step is host-launch bound: every helper indirection and extra view costs)
+            bad = decode_ops.bias_act_dropout_checked
 
             def ffn(m, x):                          # conformer_layer.py:140-146: dropout1 after the activation, dropout2 after w_2
+                if ad:
+                    return x + 0.5 * _drop(m["w_2"](bad(F.linear(m["layer_norm"](x), m["w_1"].weight), m["w_1"].bias, "silu", p, tr)), p, tr)
                 return x + 0.5 * _drop(m["w_2"](_drop(F.silu(m["w_1"](m["layer_norm"](x))), p, tr)), p, tr)
             x = ffn(self.ffn1, x)
             x = x + _drop(self.self_attn(self.self_attn_layer_norm(x), pos, pad_mask), p, tr)          # :267
             # the two pointwise (kernel 1) convolutions are GEMMs on the [B,T,C] layout the layer already has: F.linear on the
             # checkpoint's [out, in, 1] weights instead of Conv1d, which MIOpen runs as im2col + GEMM between two transposes
-            y = F.glu(F.linear(c["layer_norm"](x), c["pointwise_conv1"].weight.squeeze(-1)), dim=-1)
+            if ad:
+                y = bad(F.linear(c["layer_norm"](x), c["pointwise_conv1"].weight.squeeze(-1)), None, "glu")
+            else:
+                y = F.glu(F.linear(c["layer_norm"](x), c["pointwise_conv1"].weight.squeeze(-1)), dim=-1)
             if decode_ops.dwconv_bn_silu_autograd_served(y, c["depthwise_conv"], c["batch_norm"]):
                 # depthwise conv + batch-statistics BN + SiLU and their backward as HIP passes over [B,T,C] (csrc/conformer_train.hip): no transposes
                 y = decode_ops.dwconv_bn_silu_autograd(y, c["depthwise_conv"].weight, c["batch_norm"])
@@ -319,7 +336,12 @@ class ConformerEncoder(nn.Module):
         x, lens = self.subsample(src_tokens, src_lengths)
         T = x.shape[1]
         pad_mask = torch.arange(T, device=x.device).unsqueeze(0) >= lens.unsqueeze(1)
-        x = _drop(decode_ops.linear(self.embed_scale * x, self.linear), self.p, self.training)        # s2t_conformer.py:119-120
+        lin = self.linear
+        if self.training and self.p > 0 and decode_ops.bias_act_dropout_sites_served(x, ((lin.out_features, lin.bias, "identity"),)):
+            # bias + dropout as one HIP operator (csrc/act_dropout_train.hip): the Linear runs without its bias
+            x = decode_ops.bias_act_dropout_checked(F.linear(self.embed_scale * x, lin.weight), lin.bias, "identity", self.p, True)
+        else:
+            x = _drop(decode_ops.linear(self.embed_scale * x, self.linear), self.p, self.training)    # s2t_conformer.py:119-120
         pos = rel_positional_encoding(T, x.shape[-1], x.device, x.dtype)
         for layer in self.conformer_layers:
             x = layer(x, pos, pad_mask)
@@ -378,15 +400,23 @@ class NATDecoderLayer(nn.Module):
         if self.training or torch.is_grad_enabled():
             p, tr = self.p, self.training                                                 # transformer_layer.py:467,497,507,511
             rn = decode_ops.residual_dropout_layer_norm_checked
+            ad = decode_ops.bias_act_dropout_sites_served(x, ((self.fc1.out_features, self.fc1.bias, "gelu"),))
             if decode_ops.residual_dropout_layer_norm_sites_served(x, ((self.self_attn_layer_norm, None), (self.encoder_attn_layer_norm, None),
                                                                        (self.final_layer_norm, self.fc2.bias))):
                 # each post-norm site (residual add, dropout, LayerNorm) as one HIP operator (csrc/residual_norm_train.hip); fc2's bias rides in it
                 x = rn(self.self_attn(x, x, self_pad), x, self.self_attn_layer_norm, p=p, training=tr, return_sum=False)
                 x = rn(self.encoder_attn(x, enc, enc_pad), x, self.encoder_attn_layer_norm, p=p, training=tr, return_sum=False)
-                h = F.linear(_drop(F.gelu(self.fc1(x)), self.p_act, tr), self.fc2.weight)
+                if ad:                                 # fc1's bias + GELU + activation dropout as one HIP operator (csrc/act_dropout_train.hip)
+                    h = decode_ops.bias_act_dropout_checked(F.linear(x, self.fc1.weight), self.fc1.bias, "gelu", self.p_act, tr)
+                    h = F.linear(h, self.fc2.weight)
+                else:
+                    h = F.linear(_drop(F.gelu(self.fc1(x)), self.p_act, tr), self.fc2.weight)
                 return rn(h, x, self.final_layer_norm, bias=self.fc2.bias, p=p, training=tr, return_sum=False)
             x = self.self_attn_layer_norm(x + _drop(self.self_attn(x, x, self_pad), p, tr))
             x = self.encoder_attn_layer_norm(x + _drop(self.encoder_attn(x, enc, enc_pad), p, tr))
+            if ad:
+                h = decode_ops.bias_act_dropout_checked(F.linear(x, self.fc1.weight), self.fc1.bias, "gelu", self.p_act, tr)
+                return self.final_layer_norm(x + _drop(self.fc2(h), p, tr))
             return self.final_layer_norm(x + _drop(self.fc2(_drop(F.gelu(self.fc1(x)), self.p_act, tr)), p, tr))
         x = decode_ops.layer_norm(self.self_attn(x, x, self_pad, residual=x, lens=lens, mem_lens=lens), self.self_attn_layer_norm)
         x = decode_ops.layer_norm(self.encoder_attn(x, enc, enc_pad, residual=x, lens=lens, mem_lens=enc_lens), self.encoder_attn_layer_norm)

@@ -44,6 +44,10 @@ class FFNAdapter(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         from ..decode_ops import linear
+        fc1 = self.fc1
+        if self.training and decode_ops.bias_act_dropout_sites_served(x, ((fc1.out_features, fc1.bias, "relu"),)):
+            # fc1's bias + ReLU + dropout as one HIP operator (csrc/act_dropout_train.hip): the Linear runs without its bias
+            return linear(decode_ops.bias_act_dropout_checked(F.linear(x, fc1.weight), fc1.bias, "relu", self.p, True), self.fc2)
         return linear(_drop(linear(x, self.fc1, act="relu"), self.p, self.training), self.fc2)
 
 

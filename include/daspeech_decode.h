@@ -304,6 +304,47 @@ int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void* s, const f
                           void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream);
 int dsp_dropout_keep_mask(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, dsp_stream_t stream);
 
+/* Bias + activation + dropout (and GLU) under autograd (csrc/act_dropout_train.hip): the element-wise pass between the two GEMMs of a
+ * feed-forward block of the training step, on R rows (the product of the leading dimensions).  With u = h + bias in fp32 (bias may be NULL):
+ *     act = DSP_ACT_IDENTITY / _RELU / _SILU / _GELU (erf form):  Cout = Cin,      y[r,c] = keep ? keep_scale * act(u[r,c]) : 0
+ *     act = DSP_ACT_GLU:                                          Cout = Cin / 2,  y[r,c] = keep ? keep_scale * u[r,c] * sigmoid(u[r,c+Cout]) : 0
+ *   (the first half of a row is gated by the second, as F.glu(dim=-1)).  h [R,Cin] has unit column stride and the row pitch ld_h (elements,
+ *   >= Cin: a contiguous tensor or a column slice of a wider one); y [R,Cout] is contiguous.
+ *   The mask follows dsp_resnorm_train_fwd's rule (above) on the element index e = r*Cout + c of the OUTPUT: dsp_dropout_keep_mask over
+ *   n = R*Cout elements, read as [R,Cout], is the mask applied.  It is never stored.  thr == 0: no dropout — no mask path at all, keep_scale
+ *   is not read.
+ *   backward from dy [R,Cout] contiguous with h, bias and the same (act, keep_scale, thr, seed, offset); u, the derivative and the mask are
+ *   recomputed, nothing else of the forward is needed.  With m = keep * keep_scale (1 with thr == 0):
+ *     dh = dy * m * act'(u):   identity 1;  relu u > 0;  silu s(1 + u(1 - s)), s = sigmoid(u);  gelu Phi(u) + u phi(u);
+ *     glu, a = u[:, :Cout], g = u[:, Cout:], s = sigmoid(g):   dh[:, :Cout] = dy * m * s;   dh[:, Cout:] = dy * m * a * s(1 - s)
+ *     dbias[c] = sum_r dh[r,c], summed in fp32 BEFORE dh is rounded to the data dtype.
+ *   dh [R,Cin] is contiguous (whatever ld_h is); dbias [Cin].
+ *   h, y, dy, dh share the dtype code act_dtype (DSP_F32 / DSP_F16 / DSP_BF16); bias and dbias share param_dtype (act_dtype, or DSP_F32).
+ *   All arithmetic is fp32.  All pointers 16-byte aligned, Cin and ld_h multiples of the elements in 16 bytes (4 or 8; glu: Cin a multiple of
+ *   twice that, so that Cout is on the grid too), Cin <= DSP_ACTDROP_MAX_CIN, R <= 2^24.  EVERY OUTPUT ELEMENT IS WRITTEN.  dbias is two-stage:
+ *   a thread owns a 16-byte column group and adds the rows of its chunk of DSP_ACTDROP_CHUNK_ROWS rows in row order, one fp32 partial
+ *   [chunks, Cin] goes to the workspace, and a tail kernel adds the partials in ASCENDING chunk order.  NO FLOAT ATOMICS and no hand-off between
+ *   workgroups: the same inputs give the same bits on every call.  dh and dbias may each be NULL, and leaving one out does not change the bits
+ *   of the other; with both NULL the call returns DSP_OK without a launch.
+ *   workspace (backward, needed for dbias only; without dbias none is read and no tail is launched): dsp_act_dropout_train_workspace_bytes(R,
+ *   Cin) bytes of device memory, 16-byte aligned (DSP_ENOSPC if smaller); host arithmetic only, 0 for an empty problem, monotone in each
+ *   argument, a multiple of 16.
+ *   Bad sizes, null or aliased pointers, misalignment, an unknown act, glu with an odd number of 16-byte groups per row: DSP_EINVAL
+ *   (dsp_last_error says which) before any launch; R == 0: DSP_OK without a launch. */
+#define DSP_ACT_IDENTITY 0
+#define DSP_ACT_RELU 1
+#define DSP_ACT_SILU 2
+#define DSP_ACT_GELU 3
+#define DSP_ACT_GLU 4
+#define DSP_ACTDROP_CHUNK_ROWS 32
+#define DSP_ACTDROP_MAX_CIN 8192
+size_t dsp_act_dropout_train_workspace_bytes(int64_t R, int Cin);
+int dsp_act_dropout_train_fwd(const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
+                              uint64_t offset, void* y, int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream);
+int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
+                              uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes, int act_dtype,
+                              int param_dtype, int64_t R, int Cin, dsp_stream_t stream);
+
 /* Conformer relative-position self-attention under autograd (csrc/relpos_attention_train.hip), fp16 / bf16 data, head width 64:
  *     s(b,h,i,j) = ((q_i + u_h).k_j + (q_i + v_h).pos[T-1-i+j]) / 8,  keys with pad_mask[b,j] != 0: -inf
  *     P = softmax_j(s);  lse(b,h,i) = log sum_j exp s;  A = keep ? P * keep_scale : 0;  out_i = sum_j A_ij v_j
