@@ -39,6 +39,12 @@ Host-side mirror of the reference code these replace:
                       sums in a fixed order without float atomics; RelPosSelfAttention keeps its torch lines where
                       relpos_attention_autograd_served says no (set_relpos_attention_hip(False): always); relpos_attention_checked is
                       internal to that layer
+  conv1d_channels_last_autograd   fairseq fastspeech2.py:42-70,117-151 — the Conv1d layers of PositionwiseFeedForward and VariancePredictor (stride 1,
+                      "same" zero padding) in TRAINING mode on the channels-last tensor, without the transposes (csrc/conv1d_train.hip): fp16 / bf16,
+                      forward, input, weight and bias gradients on the matrix cores with fp32 accumulators, x and weight the only saved tensors,
+                      the weight and bias gradients fixed-order sums without float atomics; _ConvFFN / VariancePredictor keep their torch lines
+                      where conv1d_channels_last_served says no (set_conv1d_train_hip(False): always); conv1d_channels_last_checked /
+                      _sites_served are internal to those layers
 No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
@@ -1698,6 +1704,226 @@ def relpos_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias
         raise RuntimeError(f"{name}: {why}")
     ts = [_dense16(t) for t in (pos, bias_u, bias_v)]
     return relpos_attention_checked(q, k, v, ts[0], ts[1], ts[2], pad_mask, heads, p, training, return_lse)
+
+
+# ------------------------------------------------------------------------------------------------ channels-last Conv1d under autograd (csrc/conv1d_train.hip)
+CONV1D_TRAIN_HIP = True          # set_conv1d_train_hip(False): _ConvFFN / VariancePredictor keep their torch lines in training on every input
+CONV1D_TRAIN_ROW_TILE = 64       # DSP_CONV1D_TRAIN_ROW_TILE: rows of one sample per workgroup of the forward and of dx
+CONV1D_TRAIN_WGRAD_ROWS = 1024   # DSP_CONV1D_TRAIN_WGRAD_ROWS: rows of the flattened B*T per split of the weight gradient (one workspace partial each)
+CONV1D_TRAIN_MAX_K = 15          # DSP_CONV1D_TRAIN_MAX_K
+CONV1D_TRAIN_MAX_C = 8192        # DSP_CONV1D_TRAIN_MAX_C
+
+
+def set_conv1d_train_hip(on: bool) -> bool:
+    """Switch the HIP channels-last convolution of the training branches (FastSpeech2 _ConvFFN, VariancePredictor) on or off; returns the
+    previous setting.  Off: conv1d_channels_last_served answers False and the torch lines run."""
+    global CONV1D_TRAIN_HIP
+    old, CONV1D_TRAIN_HIP = CONV1D_TRAIN_HIP, bool(on)
+    return old
+
+
+def _conv1d_pitch(x: Tensor) -> Optional[int]:
+    """the row stride (elements) when x [B,T,C] reads as B*T rows of unit column stride, samples T rows apart; None for any other layout"""
+    B, T, C = x.shape
+    if x.stride(2) != 1 and C > 1:
+        return None
+    if T > 1:
+        ld = x.stride(1)
+        if B > 1 and x.stride(0) != T * ld:
+            return None
+        return ld
+    return x.stride(0) if B > 1 else C
+
+
+def _conv1d_module_problem(conv) -> Optional[str]:
+    """None when `conv` is a convolution the operator computes, else what is in the way"""
+    if not isinstance(conv, torch.nn.Conv1d):
+        return "conv has to be an nn.Conv1d"
+    K = conv.kernel_size[0]
+    if conv.stride != (1,):
+        return f"stride {conv.stride[0]}: only 1 is served"
+    if conv.dilation != (1,):
+        return f"dilation {conv.dilation[0]}: only 1 is served"
+    if conv.groups != 1:
+        return f"groups {conv.groups}: only 1 is served"
+    if K % 2 == 0 or not 1 <= K <= CONV1D_TRAIN_MAX_K:
+        return f"kernel size {K}: odd sizes from 1 to {CONV1D_TRAIN_MAX_K} are served"
+    if conv.padding != ((K - 1) // 2,) or conv.padding_mode != "zeros":
+        return f"padding {conv.padding} ({conv.padding_mode}): only zero padding of (K-1)/2 = {(K - 1) // 2} is served"
+    return None
+
+
+def _conv1d_channels_ok(C: int) -> bool:
+    return 64 <= C <= CONV1D_TRAIN_MAX_C and C % 64 == 0
+
+
+def _conv1d_train_problem(x, weight, bias) -> Optional[str]:
+    """None when dsp_conv1d_train_fwd / _bwd take these tensors as they are, else what is in the way (a layout of x that a dense copy settles
+    begins with _RELPOS_LAYOUT)"""
+    if not (isinstance(x, Tensor) and x.dim() == 3):
+        return "x has to be a [B,T,Cin] tensor"
+    if not (isinstance(weight, Tensor) and weight.dim() == 3):
+        return "weight has to be a [Cout,Cin,K] tensor"
+    B, T, Cin = x.shape
+    dt, dev = x.dtype, x.device
+    if dt not in _RA_CODES or weight.dtype != dt:
+        return f"x and weight have to be fp16 or bf16, got {dt} and {weight.dtype} (fp32 keeps the torch lines; float64 is refused, never narrowed)"
+    Cout, Cw, K = weight.shape
+    if Cw != Cin:
+        return f"weight {tuple(weight.shape)} does not fit x with {Cin} channels (groups 1: [Cout, {Cin}, K])"
+    if not (_conv1d_channels_ok(Cin) and _conv1d_channels_ok(Cout)):
+        return f"Cin = {Cin} / Cout = {Cout}: multiples of 64 up to {CONV1D_TRAIN_MAX_C} are served"
+    if K % 2 == 0 or not 1 <= K <= CONV1D_TRAIN_MAX_K:
+        return f"kernel size {K}: odd sizes from 1 to {CONV1D_TRAIN_MAX_K} are served"
+    if T < 1 or B * T > (1 << 24):
+        return f"x {tuple(x.shape)}: T >= 1 and at most 2^24 rows are served"
+    if bias is not None and (tuple(bias.shape) != (Cout,) or (bias.dtype != dt and bias.dtype != torch.float32)):
+        return f"bias has to be [{Cout}] in the dtype of x or in fp32, got {tuple(bias.shape)} {bias.dtype}"
+    if not x.is_cuda:
+        return "expected GPU tensors (HIP op, no CPU path)"
+    if weight.device != dev or (bias is not None and bias.device != dev):
+        return "x, weight and bias have to be on one device"
+    ld = _conv1d_pitch(x)
+    if ld is None or ld < Cin or ld % 8 or x.data_ptr() % 16:
+        return _RELPOS_LAYOUT + ": x needs unit column stride, one row stride on the 16-byte grid and 16-byte alignment"
+    return None
+
+
+def conv1d_channels_last_served(x: Tensor, conv: "torch.nn.Conv1d") -> bool:
+    """True when conv1d_channels_last_autograd serves a training branch for `conv` on the channels-last x [B,T,Cin] as it is: the switch is on,
+    autocast off, x a GPU tensor in fp16 or bf16 with unit column stride, one row stride on the 16-byte grid and a 16-byte aligned start,
+    conv an nn.Conv1d(Cin, Cout, K) with stride 1, dilation 1, groups 1 and zero padding (K-1)//2, K odd and at most 15, both channel counts
+    multiples of 64, weight and bias contiguous and aligned in the dtype of x (bias: or fp32).  Everything else — CPU tensors, fp32, float64,
+    the postnet's 80 channels, the subsampler's stride 2 — keeps the torch lines."""
+    if not CONV1D_TRAIN_HIP or torch.is_autocast_enabled():
+        return False
+    if _conv1d_module_problem(conv) is not None or _conv1d_train_problem(x, conv.weight, conv.bias) is not None:
+        return False
+    return not any(t is not None and (t.data_ptr() % 16 or not t.is_contiguous()) for t in (conv.weight, conv.bias))      # handed over as they are
+
+
+def conv1d_channels_last_sites_served(x: Tensor, convs) -> bool:
+    """conv1d_channels_last_served for a CHAIN of convolutions of one layer, asked before the tensors between them exist: the first reads x,
+    each later one a fresh dense tensor with the leading dimensions, dtype and device of x and the channels its predecessor leaves."""
+    if not CONV1D_TRAIN_HIP or torch.is_autocast_enabled() or not conv1d_channels_last_served(x, convs[0]):
+        return False
+    C = convs[0].out_channels
+    for conv in convs[1:]:
+        w, b = conv.weight, conv.bias
+        if (_conv1d_module_problem(conv) is not None or conv.in_channels != C or not _conv1d_channels_ok(conv.out_channels)
+                or w.dtype != x.dtype or w.device != x.device or w.data_ptr() % 16 or not w.is_contiguous()):
+            return False
+        if b is not None and ((b.dtype != x.dtype and b.dtype != torch.float32) or b.device != x.device or b.data_ptr() % 16 or not b.is_contiguous()):
+            return False
+        C = conv.out_channels
+    return True
+
+
+class _Conv1dTrainFn(torch.autograd.Function):
+    """dsp_conv1d_train_fwd / _bwd.  Saved for the backward: x and weight, nothing else — the re-laid weight lives in a workspace that does
+    not outlive the call, so no copy can go stale when the optimizer changes the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ld):
+        B, T, Cin = x.shape
+        Cout, _, K = weight.shape
+        lib = _lib.load()
+        dev = x.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            y = torch.empty((B, T, Cout), dtype=x.dtype, device=dev)
+            rc = 0
+            if B * T:
+                nbytes = int(lib.dsp_conv1d_train_workspace_bytes(0, B, T, Cin, Cout, K))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                rc = lib.dsp_conv1d_train_fwd(x.data_ptr(), ld, weight.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), Cout,
+                                              ws.data_ptr(), nbytes, _RA_CODES[x.dtype], _RN_CODES[(x if bias is None else bias).dtype], B, T, Cin,
+                                              Cout, K, torch._C._cuda_getCurrentRawStream(idx))
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_conv1d_train_fwd")
+        ctx.save_for_backward(x, weight)
+        ctx.call = (ld, None if bias is None else bias.dtype)
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        ld, bias_dtype = ctx.call
+        need = ctx.needs_input_grad
+        want_dx, want_dw, want_db = need[0], need[1], bias_dtype is not None and need[2]
+        if dy is None or not (want_dx or want_dw or want_db):
+            return None, None, None, None
+        B, T, Cin = x.shape
+        Cout, _, K = weight.shape
+        ld_dy = _conv1d_pitch(dy)
+        if ld_dy is None or ld_dy < Cout or ld_dy % 8 or dy.data_ptr() % 16:       # a transpose, a broadcast, a narrow at an odd offset
+            dy, ld_dy = dy.clone(memory_format=torch.contiguous_format), Cout
+        lib = _lib.load()
+        dev = x.device
+        idx, switch = _rn_launch_ctx(dev)
+        if switch:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(idx)
+        try:
+            dx = torch.empty((B, T, Cin), dtype=x.dtype, device=dev) if want_dx else None
+            dw = torch.empty((Cout, Cin, K), dtype=x.dtype, device=dev) if want_dw else None
+            db = torch.empty((Cout,), dtype=bias_dtype, device=dev) if want_db else None
+            rc = 0
+            if B * T:
+                nbytes = int(lib.dsp_conv1d_train_workspace_bytes(1, B, T, Cin, Cout, K))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                ptr = lambda t: None if t is None else t.data_ptr()
+                rc = lib.dsp_conv1d_train_bwd(dy.data_ptr(), ld_dy, x.data_ptr(), ld, weight.data_ptr(), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(),
+                                              nbytes, _RA_CODES[x.dtype], _RN_CODES[bias_dtype or x.dtype], B, T, Cin, Cout, K,
+                                              torch._C._cuda_getCurrentRawStream(idx))
+            else:
+                for t in (dw, db):                                          # no rows: the empty sums
+                    if t is not None:
+                        t.zero_()
+        finally:
+            if switch:
+                torch.cuda.set_device(prev)
+        if rc:
+            _lib.check(rc, "dsp_conv1d_train_bwd")
+        return dx, dw, db, None
+
+
+def conv1d_channels_last_checked(x, weight, bias=None):
+    """INTERNAL to the package's layers: conv1d_channels_last_autograd WITHOUT its argument checks, valid only on arguments that
+    conv1d_channels_last_served / _sites_served accepted.  The kernels trust what they are handed: any other caller uses
+    conv1d_channels_last_autograd."""
+    ld = _conv1d_pitch(x)
+    if ld is None or ld % 8 or x.data_ptr() % 16:       # _sites_served asked before x existed; an operator's output is dense, a view of it is copied
+        x, ld = x.clone(memory_format=torch.contiguous_format), x.shape[-1]
+    return _Conv1dTrainFn.apply(x, weight, bias, ld)
+
+
+def conv1d_channels_last_autograd(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """y[b,t,co] = [bias[co] +] sum_k sum_ci x[b, t+k-P, ci] weight[co,ci,k], P = (K-1)/2, rows outside [0, T) of a sample as zeros — what
+    F.conv1d(x.transpose(1, 2), weight, bias, padding=P).transpose(1, 2) computes, on the channels-last tensor without the transposes, and
+    differentiable w.r.t. x, weight and bias (include/daspeech_decode.h: dsp_conv1d_train_fwd / _bwd).  x [B,T,Cin] fp16 / bf16 on the GPU
+    (fp32 keeps the torch lines; float64 is refused, never narrowed), weight [Cout,Cin,K] in nn.Conv1d's layout and the dtype of x, bias
+    [Cout] in that dtype or fp32, Cin and Cout multiples of 64, K odd and at most 15.  A view of x with unit column stride and one row stride
+    on the 16-byte grid (the column slice of a wider tensor) is read as it is; any other layout, a weight or a bias that is a view, and an
+    incoming gradient that is not dense are copied, gradients pass through.  Every product runs on the matrix cores with fp32 accumulators
+    and each result is rounded once.  Saved for the backward: x and weight only.  The weight gradient's sum over the B*T rows and the bias
+    gradient's run in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
+    name = "conv1d_channels_last_autograd"
+    why = _conv1d_train_problem(x, weight, bias)
+    if why is not None and why.startswith(_RELPOS_LAYOUT):       # a view the kernels do not take as it is: a dense copy, gradients pass through
+        x = x.clone(memory_format=torch.contiguous_format)
+        why = _conv1d_train_problem(x, weight, bias)
+    if why is not None:
+        raise RuntimeError(f"{name}: {why}")
+    return conv1d_channels_last_checked(x, _dense16(weight), _dense16(bias))
 
 
 class SplitConv1d:

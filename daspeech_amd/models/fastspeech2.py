@@ -35,6 +35,15 @@ def _drop(x: Tensor, p: float, training: bool) -> Tensor:
     return F.dropout(x, p, True) if training and p > 0 else x
 
 
+def _conv_bias_relu(x: Tensor, conv: nn.Conv1d, training: bool) -> Tensor:
+    """relu(conv(x)) of a convolution that decode_ops.conv1d_channels_last_sites_served accepted, on the channels-last x: the HIP convolution
+    without its bias, then bias + ReLU as one HIP operator (csrc/act_dropout_train.hip) where that serves the site, else the torch lines"""
+    h = decode_ops.conv1d_channels_last_checked(x, conv.weight)
+    if decode_ops.bias_act_dropout_served(h, conv.bias, "relu"):
+        return decode_ops.bias_act_dropout_checked(h, conv.bias, "relu", 0.0, training)
+    return F.relu(h if conv.bias is None else h + conv.bias)
+
+
 class FFNAdapter(nn.Module):
     def __init__(self, input_size: int, hidden_size: int, output_size: int, dropout: float = 0.1):
         super().__init__()
@@ -108,6 +117,16 @@ class _ConvFFN(nn.Module):
             if self._split is not None:
                 return _dops.layer_norm(self._split[1](self._split[0](x, relu=True, lens=lens, slack=slack), residual=x, lens=lens, slack=slack),
                                         self.layer_norm)
+        c1, c2 = self.ffn[0], self.ffn[2]
+        if (self.training or torch.is_grad_enabled()) and _dops.conv1d_channels_last_sites_served(x, (c1, c2)):
+            # both convolutions as HIP operators on the channels-last tensor (csrc/conv1d_train.hip): no transposes, no copy; they run WITHOUT
+            # their biases, which ride in the element-wise operators behind them where those serve the site
+            h = _conv_bias_relu(x, c1, self.training)
+            h = _dops.conv1d_channels_last_checked(h, c2.weight)
+            if _dops.residual_dropout_layer_norm_served(h, x, self.layer_norm, bias=c2.bias):
+                return _dops.residual_dropout_layer_norm_checked(h, x, self.layer_norm, bias=c2.bias, p=self.p, training=self.training,
+                                                                 return_sum=False)
+            return self.layer_norm(_drop(h if c2.bias is None else h + c2.bias, self.p, self.training) + x)
         h = self.ffn(x.transpose(1, 2)).transpose(1, 2)
         if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(None, x, self.layer_norm):
             # dropout, residual add and LayerNorm as one HIP operator (csrc/residual_norm_train.hip) on the channels-last copy of the
@@ -166,6 +185,12 @@ class VariancePredictor(nn.Module):
                 h = _dops.layer_norm(self._split[0](x, relu=True), self.ln1)
                 h = _dops.layer_norm(self._split[1](h, relu=True), self.ln2)
                 return self.proj(h).squeeze(2)
+        if (self.training or torch.is_grad_enabled()) and _dops.conv1d_channels_last_sites_served(x, (c1, c2)):
+            # both convolutions as HIP operators on the channels-last tensor (csrc/conv1d_train.hip), bias + ReLU behind each; conv2's padding
+            # of 1 is (K-1)/2 only with K = 3, which is what the question above asks
+            x = _drop(self.ln1(_conv_bias_relu(x, c1, self.training)), self.p, self.training)
+            x = _drop(self.ln2(_conv_bias_relu(x, c2, self.training)), self.p, self.training)
+            return self.proj(x).squeeze(2)
         x = _drop(self.ln1(self.conv1(x.transpose(1, 2)).transpose(1, 2)), self.p, self.training)
         x = _drop(self.ln2(self.conv2(x.transpose(1, 2)).transpose(1, 2)), self.p, self.training)
         return self.proj(x).squeeze(2)

@@ -380,6 +380,38 @@ int dsp_relpos_attention_train_bwd(const void* dout, const void* q, const void* 
                                    void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H,
                                    dsp_stream_t stream);
 
+/* Conv1d(Cin, Cout, K, stride 1, dilation 1, groups 1, padding P = (K-1)/2) on CHANNELS-LAST data under autograd (csrc/conv1d_train.hip),
+ * fp16 / bf16 data — the FastSpeech2 feed-forward and variance-predictor convolutions of the training step without their transposes:
+ *     y [b,t,co]  = [bias[co] +] sum_k sum_ci x[b, t+k-P, ci] * W[co,ci,k]        rows outside [0, T) of a sample count as zeros
+ *     dx[b,t,ci]  = sum_k sum_co dy[b, t-k+P, co] * W[co,ci,k]
+ *     dW[co,ci,k] = sum_b sum_t  dy[b,t,co] * x[b, t+k-P, ci]
+ *     db[co]      = sum_b sum_t  dy[b,t,co]
+ *   x [B,T,Cin], y [B,T,Cout] and dy [B,T,Cout] have unit column stride and the row strides ld_x / ld_y / ld_dy (elements; at least the channel
+ *   count, multiples of 8; samples T*ld apart: a contiguous tensor or the column slice of a wider one); dx [B,T,Cin] is contiguous.  W and dW
+ *   [Cout,Cin,K] contiguous, nn.Conv1d's own layout, in the data dtype; dW is rounded once from fp32.  bias / db [Cout] in bias_dtype
+ *   (act_dtype, or DSP_F32); bias may be NULL.  act_dtype is DSP_F16 or DSP_BF16.  Every product runs on the matrix cores with fp32
+ *   accumulators; y, dx are rounded once (the bias is added in fp32 before that).  Every row is computed, padded frames included.
+ *   Served: Cin and Cout multiples of 64 up to DSP_CONV1D_TRAIN_MAX_C, K odd, 1 <= K <= DSP_CONV1D_TRAIN_MAX_K, T >= 1, B*T <= 2^24.
+ *   A workgroup of the forward (and of dx, the same kernel on dy with the transposed, tap-reversed weight) owns DSP_CONV1D_TRAIN_ROW_TILE rows
+ *   of ONE sample.  dW: the flattened B*T rows are cut into splits of DSP_CONV1D_TRAIN_WGRAD_ROWS rows, each split's fp32 partial goes to the
+ *   workspace and a tail adds the splits in ASCENDING order; db: column sums over chunks of 256 rows, the chunks added in ascending order.
+ *   NO FLOAT ATOMICS and no hand-off between workgroups: the same inputs give the same bits on every call.  dx, dW, db may each be NULL, and
+ *   leaving one out does not change the bits of the others; with all three NULL the call returns DSP_OK without a launch.
+ *   workspace: dsp_conv1d_train_workspace_bytes(phase, ...) bytes of device memory, 16-byte aligned (DSP_ENOSPC if smaller), phase 0 for the
+ *   forward (the re-laid weight), 1 for the backward (the re-laid weight and the partials); host arithmetic only, 0 for an empty problem,
+ *   monotone in each size, a multiple of 16.  Nothing in it outlives the call: the weight is re-laid on every call.
+ *   Bad sizes or dtype codes, null required pointers, misalignment, an output that aliases an input: DSP_EINVAL (dsp_last_error says which)
+ *   before any launch; B == 0: DSP_OK without a launch. */
+#define DSP_CONV1D_TRAIN_ROW_TILE 64
+#define DSP_CONV1D_TRAIN_WGRAD_ROWS 1024
+#define DSP_CONV1D_TRAIN_MAX_K 15
+#define DSP_CONV1D_TRAIN_MAX_C 8192
+size_t dsp_conv1d_train_workspace_bytes(int phase, int B, int T, int Cin, int Cout, int K);
+int dsp_conv1d_train_fwd(const void* x, long ld_x, const void* w, const void* bias, void* y, long ld_y, void* workspace, size_t workspace_bytes,
+                         int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, dsp_stream_t stream);
+int dsp_conv1d_train_bwd(const void* dy, long ld_dy, const void* x, long ld_x, const void* w, void* dx, void* dw, void* db, void* workspace,
+                         size_t workspace_bytes, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, dsp_stream_t stream);
+
 /* fp32-accurate Conv1d ("same" padding, stride 1) on the fp16 matrix cores by operand splitting (x = xh + xl/2048, w = wh + wl/2048;
  * the products xh.wh, xh.wl, xl.wh are exact in the fp32 accumulator, the dropped xl.wl term is 2^-22 relative) — for the
  * FastSpeech2 FFT feed-forward convolutions (fairseq fastspeech2.py:42-63), which MIOpen runs at 60-70 TFLOP/s in fp32.
