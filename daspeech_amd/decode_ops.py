@@ -49,6 +49,11 @@ No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
 caller's torch lines run; the alignment gates of the C ABI are never reached with something they refuse.
+The five training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
+that returns None or the reason — the ..._served() predicate asks it behind the switch and autocast gates, the raising ..._autograd() function
+raises the reason (_settled: after a dense copy where the reason begins with _LAYOUT) — and every autograd.Function launches through _launch
+(device, raw stream, return code), with _dropout_call / _dropout_thr_scale for the generator bookkeeping, _row_pitch for row-pitched views, the
+dtype tables _FLOAT_CODES / _HALF_CODES, _ptr and _workspace.
 """
 import ctypes
 import math
@@ -61,10 +66,22 @@ from torch import Tensor
 from . import _lib
 
 
+_NOT_GPU = "expected GPU tensors (HIP op, no CPU path)"
+
+
 def _gpu(name, *ts):
     for t in ts:
         if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name}: expected GPU tensors (HIP op, no CPU path)")
+            raise RuntimeError(f"{name}: {_NOT_GPU}")
+
+
+def _gpu_problem(*ts) -> Optional[str]:
+    """None when _gpu has nothing against these tensors, else its reason — asked through _gpu, as every other operator asks"""
+    try:
+        _gpu("", *ts)
+    except RuntimeError:
+        return _NOT_GPU
+    return None
 
 
 def _mask_bytes(m: Optional[Tensor]) -> Optional[Tensor]:
@@ -86,6 +103,15 @@ def _on_grid(*ts) -> bool:
     return True
 
 
+def _as_handed_over(*ts) -> bool:
+    """every tensor given (None allowed) is contiguous and starts on a 16-byte boundary: what a served rule asks of the parameters, which a
+    layer hands to the _checked function as they are"""
+    for t in ts:
+        if t is not None and (t.data_ptr() % 16 or not t.is_contiguous()):
+            return False
+    return True
+
+
 def _dense16(t: Optional[Tensor]) -> Optional[Tensor]:
     """t itself when it is contiguous and starts on a 16-byte boundary, else a dense copy (fresh allocations are on the grid): what the
     wrappers without a torch path hand to the C ABI, whose gates refuse everything else.  The copy is a torch op, so gradients pass."""
@@ -99,6 +125,75 @@ def _code(t: Tensor) -> int:
     if c is None:
         raise RuntimeError(f"unsupported dtype {t.dtype}")
     return c
+
+
+# ------------------------------------------------------------------------------------------------ host layer of the training operators
+_FLOAT_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # _lib.DTYPE_CODES by dtype object: no str() on the per-site path
+_HALF_CODES = {torch.float16: 1, torch.bfloat16: 2}                         # the matrix-core operators: 16-bit data only
+_LAYOUT = "layout"           # how a _..._problem() reason begins where a dense copy of the data tensors settles it
+
+
+def _ptr(t: Optional[Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _workspace(dev, nbytes: int) -> Optional[Tensor]:
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+
+
+def _capturing() -> bool:
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _launch(dev, entry, *args) -> None:
+    """entry(*args, stream) with the device of `dev` current and `stream` its current raw stream; a non-zero return code raises under the
+    entry's name.  The training operators are ~100 calls a step and the step is launch bound: the raw stream handle instead of a Stream
+    object, no device guard when the device is the current one already (else the previous one is put back, also when the entry raises), and a
+    plain function, not a context manager.  Tensors are allocated with their device spelled out, so only the entry needs the guard."""
+    cur = torch.cuda.current_device()
+    idx = cur if dev.index is None else dev.index
+    if idx != cur:
+        torch.cuda.set_device(idx)
+    try:
+        rc = entry(*args, torch._C._cuda_getCurrentRawStream(idx))
+    finally:
+        if idx != cur:
+            torch.cuda.set_device(cur)
+    if rc:
+        _lib.check(rc, entry.__name__)
+
+
+def _row_pitch(t: Tensor) -> Optional[int]:
+    """the row pitch (elements) when t [..., C] reads as rows of unit column stride, all one pitch apart; None for any other layout"""
+    C = t.shape[-1]
+    if t.is_contiguous():
+        return C
+    if t.stride(-1) != 1 and C > 1:
+        return None
+    ld = span = None
+    for size, stride in zip(reversed(t.shape[:-1]), reversed(t.stride()[:-1])):
+        if size == 1:
+            continue
+        if ld is None:
+            ld = stride
+        elif stride != span:
+            return None
+        span = stride * size
+    return C if ld is None else ld
+
+
+def _settled(name: str, problem, args: tuple, dense: int, p: float = 0.0) -> tuple:
+    """args as problem(*args) takes them: a reason that begins with _LAYOUT is settled by dense copies of the first `dense` tensors (torch
+    ops: gradients pass through) and asked about once more; anything left in the way, a dropout probability outside [0, 1) included, raises"""
+    why = problem(*args)
+    if why is not None and why.startswith(_LAYOUT):
+        args = tuple(_dense16(t) for t in args[:dense]) + tuple(args[dense:])
+        why = problem(*args)
+    if why is None and not 0.0 <= p < 1.0:
+        why = f"dropout probability has to be in [0, 1), got {p}"
+    if why is not None:
+        raise RuntimeError(f"{name}: {why}")
+    return args
 
 
 def argmax_logp(logits: Tensor) -> Tuple[Tensor, Tensor]:
@@ -972,6 +1067,26 @@ def _bn_tensors(bn):
     return [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
 
 
+def _convmod_problem(x, conv_weight, bn) -> Optional[str]:
+    """None when dsp_dwconv_bn_silu_train_fwd / _bwd compute this module on (a dense copy of) x, else what is in the way: dtypes, then GPU
+    tensors, then shapes"""
+    ts = _bn_tensors(bn)
+    if (x.dtype not in _FLOAT_CODES or conv_weight.dtype != x.dtype or bn.weight is None or bn.bias is None
+            or not (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts))):
+        return ("expected GPU tensors with x and conv_weight in one of fp32 / fp16 / bf16 and the BatchNorm parameters and buffers in that dtype "
+                f"or all in fp32, got {x.dtype}, {conv_weight.dtype} and {[str(t.dtype) for t in ts]}")
+    why = _gpu_problem(x, conv_weight, *ts)
+    if why is not None:
+        return why
+    C, K = (x.shape[-1], conv_weight.shape[-1]) if x.dim() == 3 and conv_weight.dim() == 3 else (0, 0)
+    if (C < 1 or C % (16 // x.element_size()) or not 2 <= x.shape[0] * x.shape[1] <= (1 << 24)
+            or tuple(conv_weight.shape) != (C, 1, K) or K not in CONVMOD_KERNEL_SIZES or bn.num_features != C or bn.momentum is None
+            or any(t.device != x.device for t in [conv_weight] + ts)):
+        return (f"x {tuple(x.shape)} / conv_weight {tuple(conv_weight.shape)} are not served (x [B,T,C] with B*T >= 2 and C a multiple of the "
+                "channels in 16 bytes, conv_weight [C,1,K] with K in 3 / 7 / 15 / 31, a momentum, everything on one device)")
+    return None
+
+
 def dwconv_bn_silu_autograd_served(x: Tensor, conv: "torch.nn.Conv1d", bn: "torch.nn.BatchNorm1d") -> bool:
     """True when dwconv_bn_silu_autograd serves ConformerLayer's training branch on these arguments: the switch is on, autocast off, x a
     contiguous GPU tensor [B,T,C] in fp32 / fp16 / bf16 with B*T >= 2 and C a multiple of the channels in 16 bytes (4, or 8 for the 16-bit
@@ -980,23 +1095,13 @@ def dwconv_bn_silu_autograd_served(x: Tensor, conv: "torch.nn.Conv1d", bn: "torc
     in fp32.  Everything else (eval mode with gradients, autocast, float64, CPU) keeps the torch formulation."""
     if not CONV_MODULE_HIP or torch.is_autocast_enabled():
         return False
-    if not (x.is_cuda and x.dim() == 3 and x.is_contiguous() and str(x.dtype) in _lib.DTYPE_CODES):
+    if _convmod_problem(x, conv.weight, bn) is not None:
         return False
-    B, T, C = x.shape
-    if B * T < 2 or B * T > (1 << 24) or C % (16 // x.element_size()) or C < 1:
-        return False
-    w = conv.weight
     K = conv.kernel_size[0]
-    if (w.dtype != x.dtype or w.device != x.device or K not in CONVMOD_KERNEL_SIZES or tuple(w.shape) != (C, 1, K) or conv.bias is not None
-            or conv.stride[0] != 1 or conv.dilation[0] != 1 or conv.groups != C or conv.padding != ((K - 1) // 2,)
-            or getattr(conv, "padding_mode", "zeros") != "zeros"):
+    if (K != conv.weight.shape[-1] or conv.bias is not None or conv.stride[0] != 1 or conv.dilation[0] != 1 or conv.groups != x.shape[2]
+            or conv.padding != ((K - 1) // 2,) or getattr(conv, "padding_mode", "zeros") != "zeros" or not (bn.training and bn.affine)):
         return False
-    if not (bn.training and bn.affine and bn.momentum is not None and bn.num_features == C):
-        return False
-    ts = _bn_tensors(bn)
-    if not (all(t.device == x.device for t in ts) and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts))):
-        return False
-    return x.data_ptr() % 16 == 0                       # 16-byte loads of x: a contiguous view at an odd offset keeps the torch lines
+    return x.is_contiguous() and x.data_ptr() % 16 == 0      # 16-byte loads of x: a contiguous view at an odd offset keeps the torch lines
 
 
 class _DwconvBnSiluTrainFn(torch.autograd.Function):
@@ -1012,17 +1117,15 @@ class _DwconvBnSiluTrainFn(torch.autograd.Function):
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
         lib = _lib.load()
         dev = xx.device
-        with torch.cuda.device(dev):
-            y = torch.empty_like(xx)
-            mean = torch.empty((C,), dtype=torch.float32, device=dev)
-            invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-            if B:
-                nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                _lib.check(lib.dsp_dwconv_bn_silu_train_fwd(_lib.ptr(xx), _lib.ptr(wt), _lib.ptr(g), _lib.ptr(b), _lib.ptr(running_mean),
-                                                            _lib.ptr(running_var), float(momentum), float(eps), _lib.ptr(y), _lib.ptr(mean),
-                                                            _lib.ptr(invstd), _lib.ptr(ws), nbytes, _code(xx), _code(g), B, T, C, K,
-                                                            _lib.current_stream_handle()), "dsp_dwconv_bn_silu_train_fwd")
+        y = torch.empty_like(xx)
+        mean = torch.empty((C,), dtype=torch.float32, device=dev)
+        invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        if B:
+            nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_dwconv_bn_silu_train_fwd, xx.data_ptr(), wt.data_ptr(), g.data_ptr(), b.data_ptr(), _ptr(running_mean),
+                    _ptr(running_var), float(momentum), float(eps), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(ws), nbytes,
+                    _FLOAT_CODES[xx.dtype], _FLOAT_CODES[g.dtype], B, T, C, K)
         ctx.save_for_backward(xx, wt, g, b, mean, invstd)
         ctx.wshape = tuple(w.shape)
         return y
@@ -1037,18 +1140,16 @@ class _DwconvBnSiluTrainFn(torch.autograd.Function):
         gy = _dense16(grad_y)                          # autograd may hand over a narrow of a larger gradient, or a broadcast
         lib = _lib.load()
         dev = xx.device
-        with torch.cuda.device(dev):
-            dx = torch.empty_like(xx) if need[0] else None
-            dw = torch.empty_like(wt) if need[1] else None
-            dg = torch.empty_like(g) if need[2] else None
-            db = torch.empty_like(b) if need[3] else None
-            if B and any(need[:4]):
-                nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                _lib.check(lib.dsp_dwconv_bn_silu_train_bwd(_lib.ptr(xx), _lib.ptr(wt), _lib.ptr(g), _lib.ptr(b), _lib.ptr(mean), _lib.ptr(invstd),
-                                                            _lib.ptr(gy), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(dg), _lib.ptr(db), _lib.ptr(ws), nbytes,
-                                                            _code(xx), _code(g), B, T, C, K, _lib.current_stream_handle()),
-                           "dsp_dwconv_bn_silu_train_bwd")
+        dx = torch.empty_like(xx) if need[0] else None
+        dw = torch.empty_like(wt) if need[1] else None
+        dg = torch.empty_like(g) if need[2] else None
+        db = torch.empty_like(b) if need[3] else None
+        if B and any(need[:4]):
+            nbytes = int(lib.dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K))
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_dwconv_bn_silu_train_bwd, xx.data_ptr(), wt.data_ptr(), g.data_ptr(), b.data_ptr(), mean.data_ptr(),
+                    invstd.data_ptr(), gy.data_ptr(), _ptr(dx), _ptr(dw), _ptr(dg), _ptr(db), _ptr(ws), nbytes, _FLOAT_CODES[xx.dtype],
+                    _FLOAT_CODES[g.dtype], B, T, C, K)
         return dx, (None if dw is None else dw.view(ctx.wshape)), dg, db, None, None, None, None
 
 
@@ -1058,18 +1159,9 @@ def dwconv_bn_silu_autograd(x: Tensor, conv_weight: Tensor, bn: "torch.nn.BatchN
     _bwd).  Batch statistics over all B*T frames (no padding mask, as the reference); bn.running_mean / running_var / num_batches_tracked
     are updated as nn.BatchNorm1d updates them, and left alone with track_running_stats=False.  fp32 / fp16 / bf16 (float64 is refused,
     never narrowed); the BatchNorm tensors in the dtype of x or all in fp32.  Bit-reproducible forward and backward."""
-    ts = [conv_weight] + _bn_tensors(bn)
-    if (str(x.dtype) not in _lib.DTYPE_CODES or conv_weight.dtype != x.dtype or bn.weight is None or bn.bias is None
-            or not (all(t.dtype == x.dtype for t in ts[1:]) or all(t.dtype == torch.float32 for t in ts[1:]))):
-        raise RuntimeError("dwconv_bn_silu_autograd: expected GPU tensors with x and conv_weight in one of fp32 / fp16 / bf16 and the BatchNorm "
-                           f"parameters and buffers in that dtype or all in fp32, got {x.dtype}, {conv_weight.dtype} and "
-                           f"{[str(t.dtype) for t in ts[1:]]}")
-    _gpu("dwconv_bn_silu_autograd", x, *ts)
-    K = conv_weight.shape[-1]
-    if (x.dim() != 3 or tuple(conv_weight.shape) != (x.shape[2], 1, K) or K not in CONVMOD_KERNEL_SIZES or bn.num_features != x.shape[2]
-            or x.shape[2] % (16 // x.element_size()) or not 2 <= x.shape[0] * x.shape[1] <= (1 << 24) or bn.momentum is None):
-        raise RuntimeError(f"dwconv_bn_silu_autograd: x {tuple(x.shape)} / conv_weight {tuple(conv_weight.shape)} are not served (x [B,T,C] with "
-                           "B*T >= 2 and C a multiple of the channels in 16 bytes, conv_weight [C,1,K] with K in 3 / 7 / 15 / 31, a momentum)")
+    why = _convmod_problem(x, conv_weight, bn)
+    if why is not None:
+        raise RuntimeError(f"dwconv_bn_silu_autograd: {why}")
     track = bn.running_mean is not None and bn.running_var is not None
     y = _DwconvBnSiluTrainFn.apply(x, conv_weight, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
                                    bn.momentum, bn.eps)
@@ -1110,6 +1202,20 @@ def _reserve_dropout_stream(device) -> Tuple[int, int]:
     return seed & 0xFFFFFFFFFFFFFFFF, offset
 
 
+def _dropout_call(p: float, training: bool, device) -> Tuple[float, int, int]:
+    """(p_eff, seed, offset) of one call of a training operator: dropout is active with `training and p > 0`, and only then is a (seed, offset)
+    reserved (the generator's offset moves on by 4, else by nothing)"""
+    p_eff = float(p) if training else 0.0
+    seed, offset = _reserve_dropout_stream(device) if p_eff > 0.0 else (0, 0)
+    return p_eff, seed, offset
+
+
+def _dropout_thr_scale(p: float) -> Tuple[int, float]:
+    """(thr, keep scale) the kernels take for the effective probability p: (0, 1.0) without dropout"""
+    thr = dropout_threshold(p) if p > 0.0 else 0
+    return thr, (1.0 / (1.0 - p) if thr else 1.0)
+
+
 def dropout_keep_mask(seed: int, offset: int, p: float, shape, device) -> Tensor:
     """The keep mask (bool, `shape`) that residual_dropout_layer_norm_autograd applies for (seed, offset, p) to a contiguous tensor of that
     shape (dsp_dropout_keep_mask): for tests and diagnostics — the operator itself stores no mask."""
@@ -1124,18 +1230,46 @@ def dropout_keep_mask(seed: int, offset: int, p: float, shape, device) -> Tensor
     return out.view(torch.bool)
 
 
-def _resnorm_params_ok(x, ln, bias) -> bool:
-    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
-    if w is None or b is None or tuple(ln.normalized_shape) != (x.shape[-1],):
-        return False
-    ts = [w, b] + ([] if bias is None else [bias])
-    return (all(t.device == x.device and tuple(t.shape) == (x.shape[-1],) for t in ts)
-            and (all(t.dtype == x.dtype for t in ts) or all(t.dtype == torch.float32 for t in ts)))
-
-
 def _resnorm_shape_ok(x) -> bool:
     C = x.shape[-1] if x.dim() >= 1 else 0
     return x.dim() >= 2 and C >= 1 and C % (16 // x.element_size()) == 0 and C <= RESNORM_MAX_C and 1 <= x.numel() // C <= (1 << 24)
+
+
+def _resnorm_param_dtypes_ok(w, b, bias, dt) -> bool:
+    """an affine LayerNorm whose weight w and bias b (and `bias`) are in dt or all in fp32: the dtype question about the parameters, asked by
+    _resnorm_problem and once per site by _sites_served"""
+    if w is None or b is None:
+        return False
+    pd = w.dtype
+    return (pd == dt or pd == torch.float32) and b.dtype == pd and (bias is None or bias.dtype == pd)
+
+
+def _resnorm_param_shapes_ok(normalized_shape, w, b, bias, C: int, dev) -> bool:
+    """a LayerNorm(C) whose weight and bias (and `bias`) are [C] tensors on dev: the shape question about the parameters, asked after
+    _resnorm_param_dtypes_ok by the same two"""
+    return (len(normalized_shape) == 1 and normalized_shape[0] == C and w.dim() == 1 and w.numel() == C and b.dim() == 1 and b.numel() == C
+            and w.device == dev and b.device == dev and (bias is None or (bias.dim() == 1 and bias.numel() == C and bias.device == dev)))
+
+
+def _resnorm_problem(h, residual, ln, bias) -> Optional[str]:
+    """None when dsp_resnorm_train_fwd / _bwd compute this site on (dense copies of) these tensors, else what is in the way: dtypes, then GPU
+    tensors, then shapes.  `bias` is not read without h, so not asked about."""
+    x = residual
+    bias = bias if h is not None else None
+    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
+    params = [t for t in (w, b, bias) if t is not None]
+    if x.dtype not in _FLOAT_CODES or (h is not None and h.dtype != x.dtype) or not _resnorm_param_dtypes_ok(w, b, bias, x.dtype):
+        return ("expected GPU tensors with h and residual in one of fp32 / fp16 / bf16 and an affine LayerNorm whose weight and bias (and `bias`) "
+                f"are in that dtype or all in fp32, got {[str(t.dtype) for t in (x, h) if t is not None]} and {[str(t.dtype) for t in params]}")
+    why = _gpu_problem(x, h, *params)
+    if why is not None:
+        return why
+    if (not _resnorm_shape_ok(x) or (h is not None and (h.shape != x.shape or h.device != x.device))
+            or not _resnorm_param_shapes_ok(ln.normalized_shape, w, b, bias, x.shape[-1], x.device)):
+        return (f"residual {tuple(x.shape)} / h {None if h is None else tuple(h.shape)} / LayerNorm {tuple(ln.normalized_shape)} are not served "
+                f"([..., C] with C a multiple of the elements in 16 bytes, C <= {RESNORM_MAX_C}, 1 <= rows <= 2^24, h of the shape of residual, "
+                "LayerNorm(C), everything on one device)")
+    return None
 
 
 def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln: "torch.nn.LayerNorm", *, bias: Optional[Tensor] = None) -> bool:
@@ -1145,16 +1279,13 @@ def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln
     fp32, and the current stream not capturing a graph (the random offset is reserved on the host).  Everything else keeps the torch lines."""
     if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
         return False
-    x = residual
-    if not (x.is_cuda and x.is_contiguous() and str(x.dtype) in _lib.DTYPE_CODES and _resnorm_shape_ok(x)):
+    if _resnorm_problem(h, residual, ln, bias) is not None:
         return False
-    if h is not None and not (h.is_cuda and h.is_contiguous() and h.dtype == x.dtype and h.shape == x.shape and h.device == x.device):
+    if not residual.is_contiguous() or (h is not None and not h.is_contiguous()):
         return False
-    if not _resnorm_params_ok(x, ln, bias if h is not None else None):
+    if not _on_grid(residual, h, ln.weight, ln.bias, bias if h is not None else None):         # 16-byte loads of every one of them
         return False
-    if not _on_grid(x, h, ln.weight, ln.bias, bias if h is not None else None):         # 16-byte loads of every one of them
-        return False
-    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+    return not _capturing()
 
 
 def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
@@ -1164,31 +1295,15 @@ def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
     if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
         return False
     dt = x.dtype
-    if not (x.is_cuda and dt in _RN_CODES and x.is_contiguous() and _resnorm_shape_ok(x) and x.data_ptr() % 16 == 0):
+    if not (x.is_cuda and dt in _FLOAT_CODES and x.is_contiguous() and _resnorm_shape_ok(x) and x.data_ptr() % 16 == 0):
         return False
-    C, dev, f32 = x.shape[-1], x.device, torch.float32
+    C, dev = x.shape[-1], x.device
     for ln, bias in sites:
         w, b = ln.weight, ln.bias
-        if w is None or b is None or len(ln.normalized_shape) != 1 or ln.normalized_shape[0] != C:
+        if not (_resnorm_param_dtypes_ok(w, b, bias, dt) and _resnorm_param_shapes_ok(ln.normalized_shape, w, b, bias, C, dev)
+                and _on_grid(w, b, bias)):
             return False
-        pd = w.dtype
-        if (pd != dt and pd != f32) or b.dtype != pd or w.device != dev or b.device != dev:
-            return False
-        if bias is not None and (bias.dtype != pd or bias.device != dev or bias.dim() != 1 or bias.shape[0] != C):
-            return False
-        if not _on_grid(w, b, bias):
-            return False
-    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
-
-
-_RN_CODES ={torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # _lib.DTYPE_CODES by dtype object: no str() on the per-site path
-
-
-def _rn_launch_ctx(dev):
-    """(device index of dev, whether dev has to be made current first).  The residual sites are ~100 calls a training step and the step is
-    launch bound: the raw stream handle instead of a Stream object, and no device guard when the device is the current one already."""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    return idx, idx != torch.cuda.current_device()
+    return not _capturing()
 
 
 class _ResidualNormTrainFn(torch.autograd.Function):
@@ -1201,27 +1316,15 @@ class _ResidualNormTrainFn(torch.autograd.Function):
         R = residual.numel() // C
         has_h = h is not None
         has_bias = has_h and bias is not None
-        thr = dropout_threshold(p) if (has_h and p > 0.0) else 0
-        scale = 1.0 / (1.0 - p) if thr else 1.0
+        thr, scale = _dropout_thr_scale(p if has_h else 0.0)
         lib = _lib.load()
         dev = residual.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            y = torch.empty_like(residual)
-            s = torch.empty_like(residual) if has_h else None
-            stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
-            rc = lib.dsp_resnorm_train_fwd(h.data_ptr() if has_h else None, residual.data_ptr(), bias.data_ptr() if has_bias else None,
-                                           gamma.data_ptr(), beta.data_ptr(), eps, alpha, scale, thr, seed, offset,
-                                           s.data_ptr() if has_h else None, y.data_ptr(), stats.data_ptr(), _RN_CODES[residual.dtype],
-                                           _RN_CODES[gamma.dtype], R, C, torch._C._cuda_getCurrentRawStream(idx))
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_resnorm_train_fwd")
+        y = torch.empty_like(residual)
+        s = torch.empty_like(residual) if has_h else None
+        stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
+        _launch(dev, lib.dsp_resnorm_train_fwd, h.data_ptr() if has_h else None, residual.data_ptr(), bias.data_ptr() if has_bias else None,
+                gamma.data_ptr(), beta.data_ptr(), eps, alpha, scale, thr, seed, offset, s.data_ptr() if has_h else None, y.data_ptr(),
+                stats.data_ptr(), _FLOAT_CODES[residual.dtype], _FLOAT_CODES[gamma.dtype], R, C)
         ctx.save_for_backward(s if has_h else residual, stats, gamma)
         ctx.call = (alpha, scale, thr, seed, offset, has_h, has_bias)
         ctx.set_materialize_grads(False)
@@ -1246,37 +1349,25 @@ class _ResidualNormTrainFn(torch.autograd.Function):
             dy = _dense16(dy)
         lib = _lib.load()
         dev = s.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            want_dh, want_dres = has_h and need[0], need[1]
-            shared = want_dh and want_dres and thr == 0 and alpha == 1.0      # dh equals dresidual: one tensor for both
-            dres = torch.empty_like(s) if want_dres else None
-            dh = torch.empty_like(s) if (want_dh and not shared) else None
-            dbias = torch.empty_like(g) if (has_bias and need[2]) else None
-            dgamma = torch.empty_like(g) if need[3] else None
-            dbeta = torch.empty_like(g) if need[4] else None
-            if dy is None:                                                 # y was not used: its parameters get zeros, not stale memory
-                for t in (dgamma, dbeta):
-                    if t is not None:
-                        t.zero_()
-            kg, kb = (dgamma, dbeta) if dy is not None else (None, None)
-            sums = kg is not None or kb is not None or dbias is not None
-            nbytes = int(lib.dsp_resnorm_train_workspace_bytes(R, C)) if sums else 0
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-            rc = 0
-            if dh is not None or dres is not None or sums:
-                ptr = lambda t: None if t is None else t.data_ptr()
-                rc = lib.dsp_resnorm_train_bwd(ptr(dy), ptr(ds), s.data_ptr(), stats.data_ptr(), g.data_ptr(), alpha, scale, thr, seed, offset,
-                                               ptr(dh), ptr(dres), ptr(dbias), ptr(kg), ptr(kb), ptr(ws), nbytes, _RN_CODES[s.dtype],
-                                               _RN_CODES[g.dtype], R, C, torch._C._cuda_getCurrentRawStream(idx))
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_resnorm_train_bwd")
+        want_dh, want_dres = has_h and need[0], need[1]
+        shared = want_dh and want_dres and thr == 0 and alpha == 1.0      # dh equals dresidual: one tensor for both
+        dres = torch.empty_like(s) if want_dres else None
+        dh = torch.empty_like(s) if (want_dh and not shared) else None
+        dbias = torch.empty_like(g) if (has_bias and need[2]) else None
+        dgamma = torch.empty_like(g) if need[3] else None
+        dbeta = torch.empty_like(g) if need[4] else None
+        if dy is None:                                                 # y was not used: its parameters get zeros, not stale memory
+            for t in (dgamma, dbeta):
+                if t is not None:
+                    t.zero_()
+        kg, kb = (dgamma, dbeta) if dy is not None else (None, None)
+        sums = kg is not None or kb is not None or dbias is not None
+        nbytes = int(lib.dsp_resnorm_train_workspace_bytes(R, C)) if sums else 0
+        ws = _workspace(dev, nbytes)
+        if dh is not None or dres is not None or sums:
+            _launch(dev, lib.dsp_resnorm_train_bwd, _ptr(dy), _ptr(ds), s.data_ptr(), stats.data_ptr(), g.data_ptr(), alpha, scale, thr, seed,
+                    offset, _ptr(dh), _ptr(dres), _ptr(dbias), _ptr(kg), _ptr(kb), _ptr(ws), nbytes, _FLOAT_CODES[s.dtype],
+                    _FLOAT_CODES[g.dtype], R, C)
         return (dres if shared else dh), dres, dbias, dgamma, dbeta, None, None, None, None, None
 
 
@@ -1288,8 +1379,7 @@ def residual_dropout_layer_norm_checked(h, residual, ln, bias=None, alpha=1.0, p
         return _ResidualNormTrainFn.apply(None, residual, None, ln.weight, ln.bias, ln.eps, 1.0, 0.0, 0, 0)
     if not h.is_contiguous() or h.data_ptr() % 16:      # the served rule looked at the residual; a block's output is dense, a view of it is copied
         h = _dense16(h)
-    p_eff = float(p) if training else 0.0
-    seed, offset = _reserve_dropout_stream(residual.device) if p_eff > 0.0 else (0, 0)
+    p_eff, seed, offset = _dropout_call(p, training, residual.device)
     out = _ResidualNormTrainFn.apply(h, residual, bias, ln.weight, ln.bias, ln.eps, float(alpha), p_eff, seed, offset)
     return out if return_sum else out[1]
 
@@ -1304,22 +1394,12 @@ def residual_dropout_layer_norm_autograd(h: Optional[Tensor], residual: Tensor, 
     differ, torch.cuda.set_rng_state restores the stream; calls with p = 0 do not touch the generator.  The masks are not torch's F.dropout
     masks.  fp32 / fp16 / bf16 (float64 is refused, never narrowed); ln.weight, ln.bias and bias in the dtype of the data or all in fp32.
     Bit-reproducible forward and backward."""
-    name = "residual_dropout_layer_norm_autograd"
-    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
-    data = [residual] + ([] if h is None else [h])
-    params = [t for t in (w, b, bias if h is not None else None) if t is not None]
-    if (str(residual.dtype) not in _lib.DTYPE_CODES or any(t.dtype != residual.dtype for t in data) or w is None or b is None
-            or not (all(t.dtype == residual.dtype for t in params) or all(t.dtype == torch.float32 for t in params))):
-        raise RuntimeError(f"{name}: expected GPU tensors with h and residual in one of fp32 / fp16 / bf16 and an affine LayerNorm whose weight and "
-                           f"bias (and `bias`) are in that dtype or all in fp32, got {[str(t.dtype) for t in data]} and "
-                           f"{[str(t.dtype) for t in params]}")
-    _gpu(name, *data, *params)
-    if (not _resnorm_shape_ok(residual) or (h is not None and h.shape != residual.shape) or tuple(ln.normalized_shape) != (residual.shape[-1],)
-            or any(tuple(t.shape) != (residual.shape[-1],) for t in params) or any(t.device != residual.device for t in params + data)
-            or not 0.0 <= p < 1.0):
-        raise RuntimeError(f"{name}: residual {tuple(residual.shape)} / h {None if h is None else tuple(h.shape)} / LayerNorm "
-                           f"{tuple(ln.normalized_shape)} / p {p} are not served ([..., C] with C a multiple of the elements in 16 bytes, "
-                           f"C <= {RESNORM_MAX_C}, 1 <= rows <= 2^24, h of the shape of residual, LayerNorm(C), 0 <= p < 1)")
+    why = _resnorm_problem(h, residual, ln, bias)
+    if why is None and not 0.0 <= p < 1.0:
+        why = f"p {p} is not served (0 <= p < 1)"
+    if why is not None:
+        raise RuntimeError(f"residual_dropout_layer_norm_autograd: {why}")
+    w, b = ln.weight, ln.bias
     if not _on_grid(w, b, bias if h is not None else None) or not (w.is_contiguous() and b.is_contiguous() and (bias is None or bias.is_contiguous())):
         # parameters that are views (a flattened buffer, a broadcast): dense copies, gradients pass through
         ln, bias = types.SimpleNamespace(weight=_dense16(w), bias=_dense16(b), eps=ln.eps), _dense16(bias)
@@ -1342,52 +1422,36 @@ def set_act_dropout_hip(on: bool) -> bool:
     return old
 
 
-def _actdrop_pitch(h: Tensor) -> Optional[int]:
-    """the row pitch (elements) when h reads as rows [R, Cin] of unit column stride, all one pitch apart; None for any other layout"""
-    C = h.shape[-1]
-    if h.is_contiguous():
-        return C
-    if h.stride(-1) != 1 and C > 1:
-        return None
-    ld = span = None
-    for size, stride in zip(reversed(h.shape[:-1]), reversed(h.stride()[:-1])):
-        if size == 1:
-            continue
-        if ld is None:
-            ld = stride
-        elif stride != span:
-            return None
-        span = stride * size
-    return C if ld is None else ld
-
-
 def _actdrop_width_ok(C: int, act, itemsize: int) -> bool:
     V = 16 // itemsize
     return act in ACT_CODES and V <= C <= ACTDROP_MAX_CIN and C % (2 * V if act == "glu" else V) == 0
 
 
+def _actdrop_bias_ok(bias, C: int, dt, dev) -> bool:
+    return bias.dim() == 1 and bias.shape[0] == C and bias.device == dev and (bias.dtype == dt or bias.dtype == torch.float32)
+
+
 def _actdrop_problem(h, bias, act) -> Optional[str]:
     """None when dsp_act_dropout_train_fwd / _bwd take these tensors as they are, else what is in the way (a layout that a dense copy settles
-    begins with _RELPOS_LAYOUT)"""
+    begins with _LAYOUT)"""
     if not (isinstance(h, Tensor) and h.dim() >= 2):
         return "h has to be a [..., Cin] tensor of at least two dimensions"
     if act not in ACT_CODES:
         return f"unknown activation {act!r} (one of {', '.join(ACT_CODES)})"
     dt = h.dtype
-    if dt not in _RN_CODES:
+    if dt not in _FLOAT_CODES:
         return f"h has to be fp32, fp16 or bf16, got {dt} (float64 is refused, never narrowed)"
     C, V = h.shape[-1], 16 // h.element_size()
     if not _actdrop_width_ok(C, act, h.element_size()) or h.numel() // C > (1 << 24):
         return (f"h {tuple(h.shape)} with {act} is not served (Cin a multiple of {V} elements — twice that with glu —, Cin <= {ACTDROP_MAX_CIN}, "
                 f"at most 2^24 rows)")
-    if bias is not None:
-        if tuple(bias.shape) != (C,) or bias.device != h.device or (bias.dtype != dt and bias.dtype != torch.float32):
-            return f"bias has to be [{C}] on the device of h, in its dtype or in fp32, got {tuple(bias.shape)} {bias.dtype}"
+    if bias is not None and not _actdrop_bias_ok(bias, C, dt, h.device):
+        return f"bias has to be [{C}] on the device of h, in its dtype or in fp32, got {tuple(bias.shape)} {bias.dtype}"
     if not h.is_cuda:
-        return "expected GPU tensors (HIP op, no CPU path)"
-    ld = _actdrop_pitch(h)
+        return _NOT_GPU
+    ld = _row_pitch(h)
     if ld is None or ld < C or ld % V or h.data_ptr() % 16:
-        return _RELPOS_LAYOUT + ": h needs unit column stride, one row pitch on the 16-byte grid and 16-byte alignment"
+        return _LAYOUT + ": h needs unit column stride, one row pitch on the 16-byte grid and 16-byte alignment"
     return None
 
 
@@ -1401,9 +1465,7 @@ def bias_act_dropout_served(h: Tensor, bias: Optional[Tensor], act: str) -> bool
         return False
     if _actdrop_problem(h, bias, act) is not None:
         return False
-    if bias is not None and (bias.data_ptr() % 16 or not bias.is_contiguous()):       # the layer hands it over as it is
-        return False
-    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+    return _as_handed_over(bias) and not _capturing()
 
 
 def bias_act_dropout_sites_served(x: Tensor, sites) -> bool:
@@ -1414,16 +1476,15 @@ def bias_act_dropout_sites_served(x: Tensor, sites) -> bool:
     if not ACT_DROPOUT_HIP or torch.is_autocast_enabled():
         return False
     dt = x.dtype
-    if not (x.is_cuda and dt in _RN_CODES and x.dim() >= 2 and x.shape[-1] >= 1 and x.numel() // x.shape[-1] <= (1 << 24)):
+    if not (x.is_cuda and dt in _FLOAT_CODES and x.dim() >= 2 and x.shape[-1] >= 1 and x.numel() // x.shape[-1] <= (1 << 24)):
         return False
-    dev, size, f32 = x.device, x.element_size(), torch.float32
+    dev, size = x.device, x.element_size()
     for C, bias, act in sites:
         if not _actdrop_width_ok(C, act, size):
             return False
-        if bias is not None and ((bias.dtype != dt and bias.dtype != f32) or bias.device != dev or bias.dim() != 1 or bias.shape[0] != C
-                                 or bias.data_ptr() % 16 or not bias.is_contiguous()):
+        if bias is not None and not (_actdrop_bias_ok(bias, C, dt, dev) and _as_handed_over(bias)):
             return False
-    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+    return not _capturing()
 
 
 class _BiasActDropoutTrainFn(torch.autograd.Function):
@@ -1434,24 +1495,13 @@ class _BiasActDropoutTrainFn(torch.autograd.Function):
         Cin = h.shape[-1]
         Cout = Cin // 2 if act == 4 else Cin
         R = h.numel() // Cin
-        thr = dropout_threshold(p) if p > 0.0 else 0
-        scale = 1.0 / (1.0 - p) if thr else 1.0
+        thr, scale = _dropout_thr_scale(p)
         lib = _lib.load()
         dev = h.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            y = torch.empty(h.shape[:-1] + (Cout,), dtype=h.dtype, device=dev)
-            rc = lib.dsp_act_dropout_train_fwd(h.data_ptr(), ld, None if bias is None else bias.data_ptr(), act, scale, thr, seed, offset,
-                                               y.data_ptr(), _RN_CODES[h.dtype], _RN_CODES[(h if bias is None else bias).dtype], R, Cin,
-                                               torch._C._cuda_getCurrentRawStream(idx)) if R else 0
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_act_dropout_train_fwd")
+        y = torch.empty(h.shape[:-1] + (Cout,), dtype=h.dtype, device=dev)
+        if R:
+            _launch(dev, lib.dsp_act_dropout_train_fwd, h.data_ptr(), ld, None if bias is None else bias.data_ptr(), act, scale, thr, seed, offset,
+                    y.data_ptr(), _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin)
         ctx.save_for_backward(h, bias)
         ctx.call = (act, ld, scale, thr, seed, offset)
         ctx.set_materialize_grads(False)
@@ -1472,28 +1522,15 @@ class _BiasActDropoutTrainFn(torch.autograd.Function):
             dy = _dense16(dy)
         lib = _lib.load()
         dev = h.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            dh = torch.empty(h.shape, dtype=h.dtype, device=dev) if want_dh else None
-            dbias = torch.empty_like(bias) if want_db else None
-            rc = 0
-            if R:
-                nbytes = int(lib.dsp_act_dropout_train_workspace_bytes(R, Cin)) if want_db else 0
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-                ptr = lambda t: None if t is None else t.data_ptr()
-                rc = lib.dsp_act_dropout_train_bwd(dy.data_ptr(), h.data_ptr(), ld, ptr(bias), act, scale, thr, seed, offset, ptr(dh), ptr(dbias),
-                                                   ptr(ws), nbytes, _RN_CODES[h.dtype], _RN_CODES[(h if bias is None else bias).dtype], R, Cin,
-                                                   torch._C._cuda_getCurrentRawStream(idx))
-            elif dbias is not None:
-                dbias.zero_()                                              # no rows: the empty sum
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_act_dropout_train_bwd")
+        dh = torch.empty(h.shape, dtype=h.dtype, device=dev) if want_dh else None
+        dbias = torch.empty_like(bias) if want_db else None
+        if R:
+            nbytes = int(lib.dsp_act_dropout_train_workspace_bytes(R, Cin)) if want_db else 0
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_act_dropout_train_bwd, dy.data_ptr(), h.data_ptr(), ld, _ptr(bias), act, scale, thr, seed, offset, _ptr(dh),
+                    _ptr(dbias), _ptr(ws), nbytes, _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin)
+        elif dbias is not None:
+            dbias.zero_()                                                  # no rows: the empty sum
         return dh, dbias, None, None, None, None, None
 
 
@@ -1501,11 +1538,10 @@ def bias_act_dropout_checked(h, bias, act, p=0.0, training=True):
     """INTERNAL to the package's layers: bias_act_dropout_autograd WITHOUT its argument checks, valid only on arguments that
     bias_act_dropout_served / _sites_served accepted.  The kernels trust what they are handed: any other caller uses
     bias_act_dropout_autograd."""
-    ld = _actdrop_pitch(h)
+    ld = _row_pitch(h)
     if ld is None or ld % (16 // h.element_size()) or h.data_ptr() % 16:      # _sites_served asked before h existed; a GEMM's output is dense, a view of it is copied
         h, ld = h.clone(memory_format=torch.contiguous_format), h.shape[-1]
-    p_eff = float(p) if training else 0.0
-    seed, offset = _reserve_dropout_stream(h.device) if p_eff > 0.0 else (0, 0)
+    p_eff, seed, offset = _dropout_call(p, training, h.device)
     return _BiasActDropoutTrainFn.apply(h, bias, ACT_CODES[act], ld, p_eff, seed, offset)
 
 
@@ -1521,22 +1557,13 @@ def bias_act_dropout_autograd(h: Tensor, bias: Optional[Tensor], act: str, p: fl
     moves on by 4; calls with p = 0 or training=False do not touch the generator) — the same generator state gives the same mask, successive
     calls differ, torch.cuda.set_rng_state restores the stream.  The masks are not torch's F.dropout masks.  The bias gradient is summed in fp32
     in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
-    name = "bias_act_dropout_autograd"
-    why = _actdrop_problem(h, bias, act)
-    if why is None and not 0.0 <= p < 1.0:
-        why = f"dropout probability has to be in [0, 1), got {p}"
-    if why is not None and why.startswith(_RELPOS_LAYOUT):       # a view the kernels do not take as it is: a dense copy, gradients pass through
-        h = h.clone(memory_format=torch.contiguous_format)
-        why = _actdrop_problem(h, bias, act)
-    if why is not None:
-        raise RuntimeError(f"{name}: {why}")
+    h, bias, act = _settled("bias_act_dropout_autograd", _actdrop_problem, (h, bias, act), 1, p)
     return bias_act_dropout_checked(h, _dense16(bias), act, p, training)
 
 
 # ------------------------------------------------------------------------------------------------ relative-position attention under autograd (csrc/relpos_attention_train.hip)
 RELPOS_ATTENTION_HIP = True   # set_relpos_attention_hip(False): RelPosSelfAttention keeps its torch lines in training on every input
 RELPOS_TRAIN_MAX_T = 2048     # DSP_RELPOS_TRAIN_MAX_T
-_RA_CODES = {torch.float16: 1, torch.bfloat16: 2}
 
 
 def set_relpos_attention_hip(on: bool) -> bool:
@@ -1547,32 +1574,29 @@ def set_relpos_attention_hip(on: bool) -> bool:
     return old
 
 
-_RELPOS_LAYOUT = "layout"      # how _relpos_train_problem begins where a dense copy of q, k, v settles it
-
-
 def _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) -> Optional[str]:
     """None when dsp_relpos_attention_train_fwd / _bwd take these tensors as they are, else what is in the way"""
     if not (isinstance(q, Tensor) and q.dim() == 3):
         return "q has to be a [B,T,C] tensor"
     B, T, C = q.shape
     dt, dev = q.dtype, q.device
-    if dt not in _RA_CODES:
+    if dt not in _HALF_CODES:
         return f"q, k, v and pos have to be fp16 or bf16, got {dt} (fp32 keeps the torch lines; float64 is refused, never narrowed)"
     if heads < 1 or C != heads * 64:
         return f"head width {C // max(heads, 1)}: only 64 is served"
     if not 1 <= T <= RELPOS_TRAIN_MAX_T:
         return f"T = {T} outside 1 .. {RELPOS_TRAIN_MAX_T}"
     if not q.is_cuda:
-        return "expected GPU tensors (HIP op, no CPU path)"
+        return _NOT_GPU
     ld = q.stride(1)
     for t in (q, k, v):
         if (t.shape != q.shape or t.dtype != dt or t.device != dev or t.stride(2) != 1 or t.stride(1) != ld or (B > 1 and t.stride(0) != T * ld)
                 or t.data_ptr() % 16):
             if t.shape != q.shape or t.dtype != dt or t.device != dev:
                 return "q, k, v need one shape, dtype and device"
-            return _RELPOS_LAYOUT + ": q, k, v need unit column stride, one common row stride and 16-byte alignment"
+            return _LAYOUT + ": q, k, v need unit column stride, one common row stride and 16-byte alignment"
     if ld < C or ld % 8:
-        return _RELPOS_LAYOUT + f": row stride {ld} of q, k, v has to be a multiple of 8 elements"
+        return _LAYOUT + f": row stride {ld} of q, k, v has to be a multiple of 8 elements"
     if pos.dtype != dt or pos.device != dev or pos.numel() != (2 * T - 1) * C or pos.shape[-1] != C and tuple(pos.shape[-2:]) != (heads, 64):
         return f"pos has to hold the [2T-1, C] projected positions in {dt}"
     pd = bias_u.dtype
@@ -1594,9 +1618,7 @@ def relpos_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pos: Tenso
         return False
     if _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) is not None:
         return False
-    if any(t.data_ptr() % 16 or not t.is_contiguous() for t in (pos, bias_u, bias_v)):      # the layer hands them over as they are
-        return False
-    return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+    return _as_handed_over(pos, bias_u, bias_v) and not _capturing()
 
 
 class _RelPosAttentionTrainFn(torch.autograd.Function):
@@ -1606,26 +1628,14 @@ class _RelPosAttentionTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, pos, bias_u, bias_v, mask, heads, p, seed, offset):
         B, T, C = q.shape
-        thr = dropout_threshold(p) if p > 0.0 else 0
-        scale = 1.0 / (1.0 - p) if thr else 1.0
+        thr, scale = _dropout_thr_scale(p)
         lib = _lib.load()
         dev = q.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            o = torch.empty((B, T, C), dtype=q.dtype, device=dev)
-            lse = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
-            rc = lib.dsp_relpos_attention_train_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(), bias_u.data_ptr(),
-                                                    bias_v.data_ptr(), None if mask is None else mask.data_ptr(), scale, thr, seed, offset,
-                                                    o.data_ptr(), lse.data_ptr(), _RA_CODES[q.dtype], _RN_CODES[bias_u.dtype], B, T, heads,
-                                                    torch._C._cuda_getCurrentRawStream(idx))
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_relpos_attention_train_fwd")
+        o = torch.empty((B, T, C), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
+        _launch(dev, lib.dsp_relpos_attention_train_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(), bias_u.data_ptr(),
+                bias_v.data_ptr(), _ptr(mask), scale, thr, seed, offset, o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype],
+                _FLOAT_CODES[bias_u.dtype], B, T, heads)
         ctx.save_for_backward(q, k, v, pos, bias_u, bias_v, o, lse, mask)
         ctx.call = (heads, scale, thr, seed, offset)
         ctx.set_materialize_grads(False)
@@ -1645,37 +1655,24 @@ class _RelPosAttentionTrainFn(torch.autograd.Function):
             do = _dense16(do)
         lib = _lib.load()
         dev = q.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            dq = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[0] else None
-            dk = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[1] else None
-            dv = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[2] else None
-            dpos = torch.empty(pos.shape, dtype=q.dtype, device=dev) if need[3] else None
-            du = torch.empty_like(bias_u) if need[4] else None
-            dbv = torch.empty_like(bias_v) if need[5] else None
-            nbytes = int(lib.dsp_relpos_attention_train_workspace_bytes(B, T, heads)) if (need[3] or need[4] or need[5]) else 0
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            rc = lib.dsp_relpos_attention_train_bwd(do.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(),
-                                                    bias_u.data_ptr(), bias_v.data_ptr(), ptr(mask), o.data_ptr(), lse.data_ptr(), scale, thr, seed,
-                                                    offset, ptr(dq), ptr(dk), ptr(dv), ptr(dpos), ptr(du), ptr(dbv), ptr(ws), nbytes,
-                                                    _RA_CODES[q.dtype], _RN_CODES[bias_u.dtype], B, T, heads, torch._C._cuda_getCurrentRawStream(idx))
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_relpos_attention_train_bwd")
+        dq = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[0] else None
+        dk = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[1] else None
+        dv = torch.empty((B, T, C), dtype=q.dtype, device=dev) if need[2] else None
+        dpos = torch.empty(pos.shape, dtype=q.dtype, device=dev) if need[3] else None
+        du = torch.empty_like(bias_u) if need[4] else None
+        dbv = torch.empty_like(bias_v) if need[5] else None
+        nbytes = int(lib.dsp_relpos_attention_train_workspace_bytes(B, T, heads)) if (need[3] or need[4] or need[5]) else 0
+        ws = _workspace(dev, nbytes)
+        _launch(dev, lib.dsp_relpos_attention_train_bwd, do.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(),
+                bias_u.data_ptr(), bias_v.data_ptr(), _ptr(mask), o.data_ptr(), lse.data_ptr(), scale, thr, seed, offset, _ptr(dq), _ptr(dk),
+                _ptr(dv), _ptr(dpos), _ptr(du), _ptr(dbv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], _FLOAT_CODES[bias_u.dtype], B, T, heads)
         return dq, dk, dv, dpos, du, dbv, None, None, None, None, None
 
 
 def relpos_attention_checked(q, k, v, pos, bias_u, bias_v, pad_mask, heads, p=0.0, training=True, return_lse=False):
     """INTERNAL to RelPosSelfAttention: relpos_attention_autograd WITHOUT its argument checks, valid only on arguments that
     relpos_attention_autograd_served accepted.  The kernels trust what they are handed: any other caller uses relpos_attention_autograd."""
-    p_eff = float(p) if training else 0.0
-    seed, offset = _reserve_dropout_stream(q.device) if p_eff > 0.0 else (0, 0)
+    p_eff, seed, offset = _dropout_call(p, training, q.device)
     if not pos.is_contiguous():
         pos = pos.contiguous()
     o, lse = _RelPosAttentionTrainFn.apply(q, k, v, pos, bias_u, bias_v, _mask_bytes(pad_mask), heads, p_eff, seed, offset)
@@ -1693,17 +1690,8 @@ def relpos_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias
     probabilities.  Dropout is active with `training and p > 0`; the mask is the one dropout_keep_mask(seed, offset, p, (B, heads, T, Tp),
     device)[..., :T] gives, Tp = T rounded up to 4, for the (seed, offset) the call reserves from the device's default CUDA generator (its
     offset moves on by 4; calls with p = 0 do not touch the generator).  Bit-reproducible forward and backward.  Raises on what is not served."""
-    name = "relpos_attention_autograd"
-    why = _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads)
-    if why is None and not 0.0 <= p < 1.0:
-        why = f"dropout probability has to be in [0, 1), got {p}"
-    if why is not None and why.startswith(_RELPOS_LAYOUT):       # views the kernels do not take as they are: dense copies, gradients pass through
-        q, k, v = _dense16(q), _dense16(k), _dense16(v)
-        why = _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads)
-    if why is not None:
-        raise RuntimeError(f"{name}: {why}")
-    ts = [_dense16(t) for t in (pos, bias_u, bias_v)]
-    return relpos_attention_checked(q, k, v, ts[0], ts[1], ts[2], pad_mask, heads, p, training, return_lse)
+    q, k, v = _settled("relpos_attention_autograd", _relpos_train_problem, (q, k, v, pos, bias_u, bias_v, pad_mask, heads), 3, p)[:3]
+    return relpos_attention_checked(q, k, v, _dense16(pos), _dense16(bias_u), _dense16(bias_v), pad_mask, heads, p, training, return_lse)
 
 
 # ------------------------------------------------------------------------------------------------ channels-last Conv1d under autograd (csrc/conv1d_train.hip)
@@ -1720,19 +1708,6 @@ def set_conv1d_train_hip(on: bool) -> bool:
     global CONV1D_TRAIN_HIP
     old, CONV1D_TRAIN_HIP = CONV1D_TRAIN_HIP, bool(on)
     return old
-
-
-def _conv1d_pitch(x: Tensor) -> Optional[int]:
-    """the row stride (elements) when x [B,T,C] reads as B*T rows of unit column stride, samples T rows apart; None for any other layout"""
-    B, T, C = x.shape
-    if x.stride(2) != 1 and C > 1:
-        return None
-    if T > 1:
-        ld = x.stride(1)
-        if B > 1 and x.stride(0) != T * ld:
-            return None
-        return ld
-    return x.stride(0) if B > 1 else C
 
 
 def _conv1d_module_problem(conv) -> Optional[str]:
@@ -1759,14 +1734,14 @@ def _conv1d_channels_ok(C: int) -> bool:
 
 def _conv1d_train_problem(x, weight, bias) -> Optional[str]:
     """None when dsp_conv1d_train_fwd / _bwd take these tensors as they are, else what is in the way (a layout of x that a dense copy settles
-    begins with _RELPOS_LAYOUT)"""
+    begins with _LAYOUT)"""
     if not (isinstance(x, Tensor) and x.dim() == 3):
         return "x has to be a [B,T,Cin] tensor"
     if not (isinstance(weight, Tensor) and weight.dim() == 3):
         return "weight has to be a [Cout,Cin,K] tensor"
     B, T, Cin = x.shape
     dt, dev = x.dtype, x.device
-    if dt not in _RA_CODES or weight.dtype != dt:
+    if dt not in _HALF_CODES or weight.dtype != dt:
         return f"x and weight have to be fp16 or bf16, got {dt} and {weight.dtype} (fp32 keeps the torch lines; float64 is refused, never narrowed)"
     Cout, Cw, K = weight.shape
     if Cw != Cin:
@@ -1780,12 +1755,12 @@ def _conv1d_train_problem(x, weight, bias) -> Optional[str]:
     if bias is not None and (tuple(bias.shape) != (Cout,) or (bias.dtype != dt and bias.dtype != torch.float32)):
         return f"bias has to be [{Cout}] in the dtype of x or in fp32, got {tuple(bias.shape)} {bias.dtype}"
     if not x.is_cuda:
-        return "expected GPU tensors (HIP op, no CPU path)"
+        return _NOT_GPU
     if weight.device != dev or (bias is not None and bias.device != dev):
         return "x, weight and bias have to be on one device"
-    ld = _conv1d_pitch(x)
+    ld = _row_pitch(x)
     if ld is None or ld < Cin or ld % 8 or x.data_ptr() % 16:
-        return _RELPOS_LAYOUT + ": x needs unit column stride, one row stride on the 16-byte grid and 16-byte alignment"
+        return _LAYOUT + ": x needs unit column stride, one row stride on the 16-byte grid and 16-byte alignment"
     return None
 
 
@@ -1799,7 +1774,7 @@ def conv1d_channels_last_served(x: Tensor, conv: "torch.nn.Conv1d") -> bool:
         return False
     if _conv1d_module_problem(conv) is not None or _conv1d_train_problem(x, conv.weight, conv.bias) is not None:
         return False
-    return not any(t is not None and (t.data_ptr() % 16 or not t.is_contiguous()) for t in (conv.weight, conv.bias))      # handed over as they are
+    return _as_handed_over(conv.weight, conv.bias)
 
 
 def conv1d_channels_last_sites_served(x: Tensor, convs) -> bool:
@@ -1811,9 +1786,9 @@ def conv1d_channels_last_sites_served(x: Tensor, convs) -> bool:
     for conv in convs[1:]:
         w, b = conv.weight, conv.bias
         if (_conv1d_module_problem(conv) is not None or conv.in_channels != C or not _conv1d_channels_ok(conv.out_channels)
-                or w.dtype != x.dtype or w.device != x.device or w.data_ptr() % 16 or not w.is_contiguous()):
+                or w.dtype != x.dtype or w.device != x.device or not _as_handed_over(w, b)):
             return False
-        if b is not None and ((b.dtype != x.dtype and b.dtype != torch.float32) or b.device != x.device or b.data_ptr() % 16 or not b.is_contiguous()):
+        if b is not None and ((b.dtype != x.dtype and b.dtype != torch.float32) or b.device != x.device):
             return False
         C = conv.out_channels
     return True
@@ -1829,24 +1804,12 @@ class _Conv1dTrainFn(torch.autograd.Function):
         Cout, _, K = weight.shape
         lib = _lib.load()
         dev = x.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            y = torch.empty((B, T, Cout), dtype=x.dtype, device=dev)
-            rc = 0
-            if B * T:
-                nbytes = int(lib.dsp_conv1d_train_workspace_bytes(0, B, T, Cin, Cout, K))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                rc = lib.dsp_conv1d_train_fwd(x.data_ptr(), ld, weight.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), Cout,
-                                              ws.data_ptr(), nbytes, _RA_CODES[x.dtype], _RN_CODES[(x if bias is None else bias).dtype], B, T, Cin,
-                                              Cout, K, torch._C._cuda_getCurrentRawStream(idx))
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_conv1d_train_fwd")
+        y = torch.empty((B, T, Cout), dtype=x.dtype, device=dev)
+        if B * T:
+            nbytes = int(lib.dsp_conv1d_train_workspace_bytes(0, B, T, Cin, Cout, K))
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_conv1d_train_fwd, x.data_ptr(), ld, weight.data_ptr(), _ptr(bias), y.data_ptr(), Cout, _ptr(ws), nbytes,
+                    _HALF_CODES[x.dtype], _FLOAT_CODES[(x if bias is None else bias).dtype], B, T, Cin, Cout, K)
         ctx.save_for_backward(x, weight)
         ctx.call = (ld, None if bias is None else bias.dtype)
         ctx.set_materialize_grads(False)
@@ -1863,36 +1826,23 @@ class _Conv1dTrainFn(torch.autograd.Function):
             return None, None, None, None
         B, T, Cin = x.shape
         Cout, _, K = weight.shape
-        ld_dy = _conv1d_pitch(dy)
+        ld_dy = _row_pitch(dy)
         if ld_dy is None or ld_dy < Cout or ld_dy % 8 or dy.data_ptr() % 16:       # a transpose, a broadcast, a narrow at an odd offset
             dy, ld_dy = dy.clone(memory_format=torch.contiguous_format), Cout
         lib = _lib.load()
         dev = x.device
-        idx, switch = _rn_launch_ctx(dev)
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(idx)
-        try:
-            dx = torch.empty((B, T, Cin), dtype=x.dtype, device=dev) if want_dx else None
-            dw = torch.empty((Cout, Cin, K), dtype=x.dtype, device=dev) if want_dw else None
-            db = torch.empty((Cout,), dtype=bias_dtype, device=dev) if want_db else None
-            rc = 0
-            if B * T:
-                nbytes = int(lib.dsp_conv1d_train_workspace_bytes(1, B, T, Cin, Cout, K))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                ptr = lambda t: None if t is None else t.data_ptr()
-                rc = lib.dsp_conv1d_train_bwd(dy.data_ptr(), ld_dy, x.data_ptr(), ld, weight.data_ptr(), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(),
-                                              nbytes, _RA_CODES[x.dtype], _RN_CODES[bias_dtype or x.dtype], B, T, Cin, Cout, K,
-                                              torch._C._cuda_getCurrentRawStream(idx))
-            else:
-                for t in (dw, db):                                          # no rows: the empty sums
-                    if t is not None:
-                        t.zero_()
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        if rc:
-            _lib.check(rc, "dsp_conv1d_train_bwd")
+        dx = torch.empty((B, T, Cin), dtype=x.dtype, device=dev) if want_dx else None
+        dw = torch.empty((Cout, Cin, K), dtype=x.dtype, device=dev) if want_dw else None
+        db = torch.empty((Cout,), dtype=bias_dtype, device=dev) if want_db else None
+        if B * T:
+            nbytes = int(lib.dsp_conv1d_train_workspace_bytes(1, B, T, Cin, Cout, K))
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_conv1d_train_bwd, dy.data_ptr(), ld_dy, x.data_ptr(), ld, weight.data_ptr(), _ptr(dx), _ptr(dw), _ptr(db),
+                    _ptr(ws), nbytes, _HALF_CODES[x.dtype], _FLOAT_CODES[bias_dtype or x.dtype], B, T, Cin, Cout, K)
+        else:
+            for t in (dw, db):                                              # no rows: the empty sums
+                if t is not None:
+                    t.zero_()
         return dx, dw, db, None
 
 
@@ -1900,7 +1850,7 @@ def conv1d_channels_last_checked(x, weight, bias=None):
     """INTERNAL to the package's layers: conv1d_channels_last_autograd WITHOUT its argument checks, valid only on arguments that
     conv1d_channels_last_served / _sites_served accepted.  The kernels trust what they are handed: any other caller uses
     conv1d_channels_last_autograd."""
-    ld = _conv1d_pitch(x)
+    ld = _row_pitch(x)
     if ld is None or ld % 8 or x.data_ptr() % 16:       # _sites_served asked before x existed; an operator's output is dense, a view of it is copied
         x, ld = x.clone(memory_format=torch.contiguous_format), x.shape[-1]
     return _Conv1dTrainFn.apply(x, weight, bias, ld)
@@ -1916,13 +1866,7 @@ def conv1d_channels_last_autograd(x: Tensor, weight: Tensor, bias: Optional[Tens
     incoming gradient that is not dense are copied, gradients pass through.  Every product runs on the matrix cores with fp32 accumulators
     and each result is rounded once.  Saved for the backward: x and weight only.  The weight gradient's sum over the B*T rows and the bias
     gradient's run in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
-    name = "conv1d_channels_last_autograd"
-    why = _conv1d_train_problem(x, weight, bias)
-    if why is not None and why.startswith(_RELPOS_LAYOUT):       # a view the kernels do not take as it is: a dense copy, gradients pass through
-        x = x.clone(memory_format=torch.contiguous_format)
-        why = _conv1d_train_problem(x, weight, bias)
-    if why is not None:
-        raise RuntimeError(f"{name}: {why}")
+    x, weight, bias = _settled("conv1d_channels_last_autograd", _conv1d_train_problem, (x, weight, bias), 1)
     return conv1d_channels_last_checked(x, _dense16(weight), _dense16(bias))
 
 

@@ -59,7 +59,7 @@ def test_served_declines_what_the_kernels_do_not_take():
 
 
 def test_row_pitch_of_views():
-    pitch = decode_ops._actdrop_pitch
+    pitch = decode_ops._row_pitch
     t = torch.zeros(4, 6, 64)
     assert pitch(t) == 64 and pitch(t[:, :, :32]) == 64 and pitch(t[:, 1:2, :32]) == 6 * 64 and pitch(t[0:1, 2:3, 8:16]) == 8
     assert pitch(t[:, :3, :32]) is None                                         # rows of two pitches

@@ -107,7 +107,7 @@ def hip_direct(t, skip=(), seed=SEED, offset=OFFSET):
     act = D().ACT_CODES[t.act]
     thr = D().dropout_threshold(t.p)
     scale = 1.0 / (1.0 - t.p) if thr else NAN                             # thr == 0: keep_scale is not read
-    ld = D()._actdrop_pitch(t.h)
+    ld = D()._row_pitch(t.h)
     out = dict(y=poisoned((t.R, t.Cout), t.dtype), dh=poisoned((t.R, t.Cin), t.dtype))
     if t.bias is not None:
         out["dbias"] = poisoned((t.Cin,), pd)
@@ -187,7 +187,7 @@ def test_pitched_h_and_transposed_dy_through_the_operator(case):
     """h a column slice of a wider tensor (served with its pitch: no copy) and dy a transposed view (made dense by the operator): the 4 x
     rule, and the bits of the entry points on the dense tensors"""
     dense, t = stored(case), stored(case, "slice")
-    assert D().bias_act_dropout_served(t.h, t.bias, t.act) and D()._actdrop_pitch(t.h) > t.Cin
+    assert D().bias_act_dropout_served(t.h, t.bias, t.act) and D()._row_pitch(t.h) > t.Cin
     direct = hip_direct(t)                                                 # the C entry points with ld_h > Cin
     for k, v in hip_direct(dense).items():
         assert torch.equal(v, direct[k]), k
