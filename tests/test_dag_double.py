@@ -96,7 +96,8 @@ def test_operator_names_take_float64_on_the_gpu():
 @pytest.mark.parametrize("seed,B,T,L,TR", CASES + [(5, 3, 40, 700, 32), (6, 2, 25, 300, 299), (7, 2, 16, 1031, 64)])
 def test_native_double_kernels_match_the_fp64_oracle(seed, B, T, L, TR):
     """r06: float64 CUDA tensors run csrc/dag_dp_f64.hip (the reference dispatches double too, dag_loss.cu:160,294,415,499), not a torch loop:
-    alpha / beta / loss to 1e-12, both gradients to 1e-9, the Viterbi path exactly — banded, dense and ragged graphs, an unreachable sample."""
+    alpha / beta / loss to 1e-12, both gradients to 1e-9, the Viterbi path exactly — banded, dense and ragged graphs, an unreachable sample.
+    The kernels' launch regimes (passes of the 1024-thread loops, the LDS opt-in and cap, grid strides) live in tests/test_gpu_dag_double_regimes.py."""
     from daspeech_amd import custom_ops as ops
     dev = torch.device("cuda:0")
     m, k, ol, tl, (mt, kt, olt, tlt) = _t(seed, B, T, L, TR)
