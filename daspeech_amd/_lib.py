@@ -158,6 +158,11 @@ SIGNATURES = {
     "dsp_hifigan_conv_chain_f32": (_c_int, [_c_p, _c_int, _c_int, _c_p, _c_int, _c_p]),
     "dsp_hifigan_pad_input_f32": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_hifigan_post_f32": (_c_int, [_c_p, _c_p, ctypes.c_float, _c_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, _c_p, _c_int, _c_p]),
+    # include/daspeech_optim.h
+    "dsp_fp16_optim_workspace_bytes": (_c_sz, [_c_i64]),
+    "dsp_fp16_optim_grad_sumsq": (_c_int, [_c_p, _c_int, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_sz, _c_p, _c_p]),
+    "dsp_fp16_optim_adam_step": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p] + [ctypes.c_double] * 8
+                                 + [_c_int, _c_p]),
     "dsp_dag_alignment_trace_optional": (_c_int, [_c_int, _c_int]),
     "dsp_dag_debug_k5": (_c_int, [ctypes.POINTER(ctypes.c_uint)]),
     "dsp_dag_set_option": (_c_int, [ctypes.c_char_p, _c_int]),
