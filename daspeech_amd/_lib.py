@@ -136,6 +136,11 @@ SIGNATURES = {
     "dsp_relpos_attention_train_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_uint,
                                                 ctypes.c_uint64, ctypes.c_uint64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int,
                                                 _c_int, _c_int, _c_p]),
+    "dsp_mha_train_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, _c_p, ctypes.c_long, _c_p, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
+                                   _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_mha_train_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "dsp_mha_train_bwd": (_c_int, [_c_p, _c_p, ctypes.c_long, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64,
+                                   ctypes.c_uint64, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_conv1d_train_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "dsp_conv1d_train_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, _c_p, _c_p, ctypes.c_long, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int,
                                       _c_int, _c_int, _c_p]),

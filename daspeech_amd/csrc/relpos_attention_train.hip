@@ -24,76 +24,12 @@
 // The dropout mask is never stored: element e = ((b H + h) T + i) Tp + j, Tp = T rounded up to a multiple of 4, of the rule in philox.h.
 #include "common.h"
 #include "philox.h"
+#include "ra_frag.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
 
-typedef _Float16 ra_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ra_b8 __attribute__((ext_vector_type(8)));
-typedef float ra_acc __attribute__((ext_vector_type(16)));
-typedef unsigned short ra_u16;
-
-constexpr int RA_P64 = 72;      // pitch (elements) of an LDS image with 64 k values: 144 bytes, 16-byte aligned rows
-constexpr int RA_P32 = 40;      // with 32 k values: 80 bytes
 constexpr int RA_PG = 65;       // pitch (floats) of the shift scratch
-#define RA_ROW(reg, hi) (((reg) & 3) + 8 * ((reg) >> 2) + 4 * (hi))
-
-template <typename E> struct Ra;
-template <> struct Ra<__half> {
-    using V = ra_h8;
-    static __device__ __forceinline__ ra_acc mma(V a, V b, ra_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ float val(ra_u16 u) { return __half2float(__ushort_as_half(u)); }
-    static __device__ __forceinline__ ra_u16 bits(float f) { return __half_as_ushort(__float2half(f)); }
-};
-template <> struct Ra<__hip_bfloat16> {
-    using V = ra_b8;
-    static __device__ __forceinline__ ra_acc mma(V a, V b, ra_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ float val(ra_u16 u) { return __uint_as_float((uint32_t)u << 16); }
-    static __device__ __forceinline__ ra_u16 bits(float f) { const __hip_bfloat16 v = __float2bfloat16(f); ra_u16 u; __builtin_memcpy(&u, &v, 2); return u; }
-};
-
-// acc += A . B^T over 16 * KS values of k: A rows at a + r * lda, B^T rows at b + r * ldb, k contiguous in both (16-byte aligned rows)
-template <typename E, int KS>
-__device__ __forceinline__ void ra_mma_nt(ra_acc& acc, const ra_u16* a, int lda, const ra_u16* b, int ldb, int lane)
-{
-    using V = typename Ra<E>::V;
-    const int r = lane & 31, k0 = (lane >> 5) * 8;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const V va = *reinterpret_cast<const V*>(a + r * lda + 16 * s + k0);
-        const V vb = *reinterpret_cast<const V*>(b + r * ldb + 16 * s + k0);
-        acc = Ra<E>::mma(va, vb, acc);
-    }
-}
-
-// rows row0 .. row0 + n - 1 (n = 32 or 64) of a matrix of R rows, 64 columns from src on, row stride ld -> an LDS image; rows outside
-// [0, R) as zeros.  TR: the image is [64 columns][n rows] instead of [n rows][64 columns].  bias (fp32, 64): added in fp32 and rounded once.
-template <typename E, bool TR>
-__device__ __forceinline__ void ra_stage(ra_u16* dst, int pitch, const E* src, long ld, int row0, int n, int R, const float* bias, int lane)
-{
-    for (int ci = lane; ci < n * 8; ci += 64) {
-        const int rl = ci >> 3, c8 = (ci & 7) * 8, row = row0 + rl;
-        uint4 u = make_uint4(0u, 0u, 0u, 0u);
-        if (row >= 0 && row < R) u = *reinterpret_cast<const uint4*>(src + (long)row * ld + c8);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-        ra_u16 e[8];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) { e[2 * x] = (ra_u16)(w[x] & 0xffffu); e[2 * x + 1] = (ra_u16)(w[x] >> 16); }
-        if (bias) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) e[x] = Ra<E>::bits(Ra<E>::val(e[x]) + bias[c8 + x]);
-        }
-        if (!TR) {
-            *reinterpret_cast<uint4*>(dst + rl * pitch + c8) =
-                make_uint4((uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16), (uint32_t)e[4] | ((uint32_t)e[5] << 16),
-                           (uint32_t)e[6] | ((uint32_t)e[7] << 16));
-        } else {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) dst[(c8 + x) * pitch + rl] = e[x];
-        }
-    }
-}
-
 // bias_u / bias_v of head h as floats: bias[0..63] = u, bias[64..127] = v
 __device__ __forceinline__ void ra_load_bias(float* bias, const void* bu, const void* bv, int pdtype, int h, int lane)
 {
@@ -132,11 +68,6 @@ __device__ __forceinline__ void ra_scores(const ra_u16* Qu, const ra_u16* Qv, co
     __syncthreads();
 }
 
-__device__ __forceinline__ uint64_t ra_elem(int b, int h, int H, int T, int Tp, int i, int j)
-{
-    return (((uint64_t)b * H + h) * (uint64_t)T + (uint64_t)i) * (uint64_t)Tp + (uint64_t)j;
-}
-
 // The keep factors (keep_scale or 0) of a lane's 16 elements of the tile of queries i0 .. i0+31 and keys j0 .. j0+31.  j0 a multiple of 4 (a query's
 // row of the index space starts on a counter boundary: Tp is a multiple of 4): the tile's 32 x 8 Philox calls are shared out, 4 per lane, and the
 // flags pass through LDS as bytes (kb: 1 KiB, the shift scratch, free after ra_scores).  Any other j0 (the position pass): one call per element.
@@ -145,16 +76,9 @@ __device__ __forceinline__ void ra_keep_tile(unsigned char* kb, int b, int h, in
 {
     const int jl = lane & 31, hi = lane >> 5, Tp = (T + 3) & ~3;
     if ((j0 & 3) == 0) {                                                    // workgroup-uniform
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int il = (lane >> 3) + 8 * t, gq = lane & 7;
-            bool keep[4];
-            keep_flags<4>(ra_elem(b, h, H, T, Tp, i0 + il, j0 + 4 * gq), seed, offset, thr, keep);
-            *reinterpret_cast<uint32_t*>(kb + il * 32 + 4 * gq) = (keep[0] ? 1u : 0u) | (keep[1] ? 0x100u : 0u) | (keep[2] ? 0x10000u : 0u) | (keep[3] ? 0x1000000u : 0u);
-        }
+        ra_keep_fill(kb, b, h, H, T, Tp, i0, j0, seed, offset, thr, lane);
         __syncthreads();
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) kf[reg] = kb[RA_ROW(reg, hi) * 32 + jl] ? keep_scale : 0.f;
+        ra_keep_read(kb, keep_scale, lane, kf);
         __syncthreads();
     } else {
 #pragma unroll
@@ -275,18 +199,6 @@ __device__ __forceinline__ void ra_grad_tile(const ra_u16* Qu, const ra_u16* Qv,
         const float f = thr ? kf[reg] : 1.f;
         pm[reg] = p * f;
         ds[reg] = p * (dp[reg] * f - Dr[reg]) * 0.125f;
-    }
-}
-
-// a tile with its COLUMN index on the lane -> the image [column][row] (k = the row index contiguous): 4 registers are 4 consecutive rows
-template <typename E>
-__device__ __forceinline__ void ra_store_t(ra_u16* dst, const float (&x)[16], int lane)
-{
-    const int jl = lane & 31, hi = lane >> 5;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float q[4] = {x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
-        store_f<E, 4>(reinterpret_cast<E*>(dst + jl * RA_P32 + 8 * g + 4 * hi), q);
     }
 }
 

@@ -39,7 +39,14 @@ Host-side mirror of the reference code these replace:
                       sums in a fixed order without float atomics; RelPosSelfAttention keeps its torch lines where
                       relpos_attention_autograd_served says no (set_relpos_attention_hip(False): always); relpos_attention_checked is
                       internal to that layer
-  conv1d_channels_last_autograd   fairseq fastspeech2.py:42-70,117-151 — the Conv1d layers of PositionwiseFeedForward and VariancePredictor (stride 1,
+  mha_attention_autograd   fairseq multihead_attention.py between the projections and out_proj — the NAT decoder's self- and encoder attention
+                      (_MHA) and the FFT layers (_SelfAttention) in TRAINING mode under autograd (csrc/mha_train.hip): fp16 / bf16, query and
+                      key lengths independent, q / k / v taken as views of stacked projections, scores + mask + soft-max + dropout + value
+                      product in one launch, a backward of two launches that recomputes the probabilities (no [B,h,N,M] tensor is kept) without
+                      float atomics, the dropout mask on the shared Philox rule; the layers keep their torch lines
+                      (F.scaled_dot_product_attention) where mha_attention_autograd_served says no (set_mha_attention_hip(False): always);
+                      mha_attention_checked is internal to those layers
+  conv1d_channels_last_autograd  fairseq fastspeech2.py:42-70,117-151 — the Conv1d layers of PositionwiseFeedForward and VariancePredictor (stride 1,
                       "same" zero padding) in TRAINING mode on the channels-last tensor, without the transposes (csrc/conv1d_train.hip): fp16 / bf16,
                       forward, input, weight and bias gradients on the matrix cores with fp32 accumulators, x and weight the only saved tensors,
                       the weight and bias gradients fixed-order sums without float atomics; _ConvFFN / VariancePredictor keep their torch lines
@@ -49,7 +56,7 @@ No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
 caller's torch lines run; the alignment gates of the C ABI are never reached with something they refuse.
-The five training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
+The six training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
 that returns None or the reason — the ..._served() predicate asks it behind the switch and autocast gates, the raising ..._autograd() function
 raises the reason (_settled: after a dense copy where the reason begins with _LAYOUT) — and every autograd.Function launches through _launch
 (device, raw stream, return code), with _dropout_call / _dropout_thr_scale for the generator bookkeeping, _row_pitch for row-pitched views, the
@@ -1694,8 +1701,131 @@ def relpos_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias
     return relpos_attention_checked(q, k, v, _dense16(pos), _dense16(bias_u), _dense16(bias_v), pad_mask, heads, p, training, return_lse)
 
 
+# ------------------------------------------------------------------------------------------------ multi-head attention under autograd (csrc/mha_train.hip)
+MHA_ATTENTION_HIP = True      # set_mha_attention_hip(False): _MHA / _SelfAttention keep their torch lines in training on every input
+MHA_TRAIN_MAX_LEN = 4096      # DSP_MHA_TRAIN_MAX_LEN
+
+
+def set_mha_attention_hip(on: bool) -> bool:
+    """Switch the HIP multi-head attention of the training branches of _MHA (NAT decoder) and _SelfAttention (FFT layers) on or off; returns
+    the previous setting.  Off: mha_attention_autograd_served answers False and the torch lines run."""
+    global MHA_ATTENTION_HIP
+    old, MHA_ATTENTION_HIP = MHA_ATTENTION_HIP, bool(on)
+    return old
+
+
+def _mha_train_problem(q, k, v, pad_mask, heads) -> Optional[str]:
+    """None when dsp_mha_train_fwd / _bwd take these tensors as they are, else what is in the way"""
+    if not (isinstance(q, Tensor) and q.dim() == 3 and isinstance(k, Tensor) and k.dim() == 3 and isinstance(v, Tensor)):
+        return "q has to be a [B,N,C] tensor, k and v [B,M,C] tensors"
+    B, N, C = q.shape
+    M = k.shape[1]
+    dt, dev = q.dtype, q.device
+    if dt not in _HALF_CODES:
+        return f"q, k and v have to be fp16 or bf16, got {dt} (fp32 keeps the torch lines; float64 is refused, never narrowed)"
+    if heads < 1 or C != heads * 64:
+        return f"head width {C // max(heads, 1)}: only 64 is served"
+    if not (1 <= N <= MHA_TRAIN_MAX_LEN and 1 <= M <= MHA_TRAIN_MAX_LEN):
+        return f"N = {N}, M = {M} outside 1 .. {MHA_TRAIN_MAX_LEN}"
+    if not q.is_cuda:
+        return _NOT_GPU
+    if k.shape != (B, M, C) or v.shape != k.shape or k.dtype != dt or v.dtype != dt or k.device != dev or v.device != dev:
+        return "q [B,N,C], k and v [B,M,C] need one dtype and device"
+    ldq, ldkv = q.stride(1), k.stride(1)
+    if q.stride(2) != 1 or (B > 1 and q.stride(0) != N * ldq) or q.data_ptr() % 16:
+        return _LAYOUT + ": q needs unit column stride, samples N rows apart and 16-byte alignment"
+    for t in (k, v):
+        if t.stride(2) != 1 or t.stride(1) != ldkv or (B > 1 and t.stride(0) != M * ldkv) or t.data_ptr() % 16:
+            return _LAYOUT + ": k, v need unit column stride, one common row stride and 16-byte alignment"
+    if ldq < C or ldq % 8 or ldkv < C or ldkv % 8:
+        return _LAYOUT + f": row strides {ldq} (q) and {ldkv} (k, v) have to be multiples of 8 elements"
+    if pad_mask is not None and (tuple(pad_mask.shape) != (B, M) or pad_mask.device != dev):
+        return "pad_mask has to be [B,M] on the device of q"
+    return None
+
+
+def mha_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pad_mask: Optional[Tensor], heads: int) -> bool:
+    """True when mha_attention_autograd serves the training branch of _MHA / _SelfAttention on these arguments: the switch is on, autocast off,
+    q [B,N,heads*64] and k, v [B,M,heads*64] GPU tensors in fp16 or bf16 (row strides multiples of 8 elements, one for k and v), N, M <= 4096,
+    pad_mask [B,M] or None, and the current stream not capturing a graph (the random offset is reserved on the host).  Everything else — fp32
+    data, CPU tensors, another head width — keeps the torch lines."""
+    if not MHA_ATTENTION_HIP or torch.is_autocast_enabled():
+        return False
+    if _mha_train_problem(q, k, v, pad_mask, heads) is not None:
+        return False
+    return not _capturing()
+
+
+class _MhaTrainFn(torch.autograd.Function):
+    """dsp_mha_train_fwd / _bwd.  Saved for the backward: q, k, v, the fp32 lse and the mask bytes — no probabilities and no dropout mask: the
+    backward recomputes both (and D_i = dO_i . o_i from them in fp32, so o is not kept here either: out_proj keeps it as its input)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads, p, seed, offset):
+        B, N, C = q.shape
+        M = k.shape[1]
+        thr, scale = _dropout_thr_scale(p)
+        lib = _lib.load()
+        dev = q.device
+        o = torch.empty((B, N, C), dtype=q.dtype, device=dev)
+        lse = torch.empty((B, heads, N), dtype=torch.float32, device=dev)
+        _launch(dev, lib.dsp_mha_train_fwd, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), scale, thr, seed, offset,
+                o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype], B, N, M, heads)
+        ctx.save_for_backward(q, k, v, lse, mask)
+        ctx.call = (heads, scale, thr, seed, offset)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, do, _dlse):
+        q, k, v, lse, mask = ctx.saved_tensors
+        heads, scale, thr, seed, offset = ctx.call
+        need = ctx.needs_input_grad
+        if do is None or not any(need[:3]):
+            return (None,) * 8
+        B, N, C = q.shape
+        M = k.shape[1]
+        if not do.is_contiguous() or do.data_ptr() % 16:
+            do = _dense16(do)
+        lib = _lib.load()
+        dev = q.device
+        dq = torch.empty((B, N, C), dtype=q.dtype, device=dev) if need[0] else None
+        dk = torch.empty((B, M, C), dtype=q.dtype, device=dev) if need[1] else None
+        dv = torch.empty((B, M, C), dtype=q.dtype, device=dev) if need[2] else None
+        nbytes = int(lib.dsp_mha_train_workspace_bytes(B, N, M, heads))     # D [B,H,N] fp32, rounded up to 16 bytes: the library's own answer
+        ws = _workspace(dev, nbytes)
+        _launch(dev, lib.dsp_mha_train_bwd, do.data_ptr(), q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), lse.data_ptr(),
+                scale, thr, seed, offset, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], B, N, M, heads)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def mha_attention_checked(q, k, v, pad_mask, heads, p=0.0, training=True, return_lse=False):
+    """INTERNAL to _MHA / _SelfAttention: mha_attention_autograd WITHOUT its argument checks, valid only on arguments that
+    mha_attention_autograd_served accepted.  The kernels trust what they are handed: any other caller uses mha_attention_autograd."""
+    p_eff, seed, offset = _dropout_call(p, training, q.device)
+    o, lse = _MhaTrainFn.apply(q, k, v, _mask_bytes(pad_mask), heads, p_eff, seed, offset)
+    return (o, lse) if return_lse else o
+
+
+def mha_attention_autograd(q: Tensor, k: Tensor, v: Tensor, pad_mask: Optional[Tensor], heads: int, p: float = 0.0, training: bool = True,
+                           return_lse: bool = False):
+    """Multi-head attention (fairseq multihead_attention.py between the projections and out_proj: the NAT decoder's self- and encoder
+    attention, the FFT layers) under autograd, one HIP launch forward and two backward (include/daspeech_decode.h: dsp_mha_train_fwd / _bwd):
+        o_i = sum_j dropout(softmax_j(q_i . k_j / 8; pad_mask[b,j]: -inf), p)_ij v_j      per head of width 64
+    differentiable w.r.t. q, k and v.  q [B,N,heads*64], k and v [B,M,heads*64] fp16 / bf16 (N and M independent; views into a stacked q|k|v or
+    k|v projection are taken as they are: row strides that are multiples of 8 elements, one for k and v), pad_mask [B,M] bool or None.  Returns
+    o [B,N,heads*64] (with return_lse: and the fp32 log-sum-exp [B,heads,N]).  No [B,h,N,M] tensor is kept: the backward recomputes the
+    probabilities.  Dropout is active with `training and p > 0`; the mask is the one dropout_keep_mask(seed, offset, p, (B, heads, N, Mp),
+    device)[..., :M] gives, Mp = M rounded up to 4, for the (seed, offset) the call reserves from the device's default CUDA generator (its
+    offset moves on by 4; calls with p = 0 do not touch the generator).  Bit-reproducible forward and backward.  Raises on what is not served."""
+    q, k, v = _settled("mha_attention_autograd", _mha_train_problem, (q, k, v, pad_mask, heads), 3, p)[:3]
+    return mha_attention_checked(q, k, v, pad_mask, heads, p, training, return_lse)
+
+
 # ------------------------------------------------------------------------------------------------ channels-last Conv1d under autograd (csrc/conv1d_train.hip)
-CONV1D_TRAIN_HIP = True          # set_conv1d_train_hip(False): _ConvFFN / VariancePredictor keep their torch lines in training on every input
+CONV1D_TRAIN_HIP = True         # set_conv1d_train_hip(False): _ConvFFN / VariancePredictor keep their torch lines in training on every input
 CONV1D_TRAIN_ROW_TILE = 64       # DSP_CONV1D_TRAIN_ROW_TILE: rows of one sample per workgroup of the forward and of dx
 CONV1D_TRAIN_WGRAD_ROWS = 1024   # DSP_CONV1D_TRAIN_WGRAD_ROWS: rows of the flattened B*T per split of the weight gradient (one workspace partial each)
 CONV1D_TRAIN_MAX_K = 15          # DSP_CONV1D_TRAIN_MAX_K

@@ -376,9 +376,15 @@ class _MHA(nn.Module):
                 return L_(o, self.out_proj, residual=residual, lens=lens)
             q, k, v = (t.reshape(B, -1, self.h, C // self.h).transpose(1, 2) for t in (qf, kf, vf))
         else:
-            q = L_(x, self.q_proj).view(B, N, self.h, -1).transpose(1, 2)
-            k = L_(mem, self.k_proj).view(B, M, self.h, -1).transpose(1, 2)
-            v = L_(mem, self.v_proj).view(B, M, self.h, -1).transpose(1, 2)
+            q, k, v = L_(x, self.q_proj), L_(mem, self.k_proj), L_(mem, self.v_proj)
+            if decode_ops.mha_attention_autograd_served(q, k, v, mem_pad, self.h):
+                # fp16 / bf16 on the GPU: the projections as they are ([B,.,C], no transposes, no additive mask tensor), scores + mask +
+                # soft-max + dropout + value product as one HIP operator (csrc/mha_train.hip), its output straight into out_proj
+                o = decode_ops.mha_attention_checked(q, k, v, mem_pad, self.h, p=self.p_attn, training=True)
+                return decode_ops.linear(o, self.out_proj, residual=residual)
+            q = q.view(B, N, self.h, -1).transpose(1, 2)
+            k = k.view(B, M, self.h, -1).transpose(1, 2)
+            v = v.view(B, M, self.h, -1).transpose(1, 2)
         mask = None
         if mem_pad is not None:
             mask = torch.zeros(B, 1, 1, M, dtype=x.dtype, device=x.device).masked_fill(mem_pad.view(B, 1, 1, M), float("-inf"))

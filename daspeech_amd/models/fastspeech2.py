@@ -83,9 +83,15 @@ class _SelfAttention(nn.Module):
                 return L_(o, self.out_proj, residual=residual, lens=lens, slack=slack)
             q, k, v = (t.reshape(B, N, h, C // h).transpose(1, 2) for t in (qf, kf, vf))
         else:
-            q = L_(x, self.q_proj).view(B, N, h, C // h).transpose(1, 2)
-            k = L_(x, self.k_proj).view(B, N, h, C // h).transpose(1, 2)
-            v = L_(x, self.v_proj).view(B, N, h, C // h).transpose(1, 2)
+            from ..decode_ops import mha_attention_autograd_served, mha_attention_checked
+            q, k, v = L_(x, self.q_proj), L_(x, self.k_proj), L_(x, self.v_proj)
+            if mha_attention_autograd_served(q, k, v, padding_mask, h):
+                # fp16 / bf16 on the GPU: the projections as they are ([B,N,C], no transposes, no additive mask tensor), scores + mask +
+                # soft-max + dropout + value product as one HIP operator (csrc/mha_train.hip), its output straight into out_proj
+                return L_(mha_attention_checked(q, k, v, padding_mask, h, p=self.p_attn, training=True), self.out_proj, residual=residual)
+            q = q.view(B, N, h, C // h).transpose(1, 2)
+            k = k.view(B, N, h, C // h).transpose(1, 2)
+            v = v.view(B, N, h, C // h).transpose(1, 2)
         mask = None
         if padding_mask is not None:
             mask = torch.zeros(B, 1, 1, N, dtype=x.dtype, device=x.device).masked_fill(padding_mask.view(B, 1, 1, N), float("-inf"))

@@ -380,6 +380,41 @@ int dsp_relpos_attention_train_bwd(const void* dout, const void* q, const void* 
                                    void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H,
                                    dsp_stream_t stream);
 
+/* Multi-head attention under autograd (csrc/mha_train.hip), fp16 / bf16 data, head width 64 — the relative-position entries above without the
+ * position term and with a key length of its own (self-attention: M = N; encoder attention: M = the memory's length):
+ *     s(b,h,i,j) = q_i . k_j / 8,  keys with pad_mask[b,j] != 0: -inf
+ *     P = softmax_j(s);  lse(b,h,i) = log sum_j exp s;  A = keep ? P * keep_scale : 0;  out_i = sum_j A_ij v_j
+ *   q [B,N,H,64] with row stride ldq, k and v [B,M,H,64] with one common row stride ldkv (elements; >= 64 H, multiples of 8; samples N*ldq and
+ *   M*ldkv apart: contiguous tensors, or the column slices of a stacked q|k|v or k|v projection), pad_mask [B,M] bytes or NULL, out [B,N,H*64]
+ *   contiguous in the data dtype, lse [B,H,N] fp32 (saved for the backward).  Scores, soft-max statistics and accumulators are fp32; P o keep
+ *   is rounded to the data dtype once, where it becomes a matrix-core operand, and keep_scale multiplies the fp32 result.  Every query row is computed, padded ones too.  A sample whose keys are all
+ *   masked gets NaN in its own rows, as torch's soft-max gives, and harms no other; no mask leads to an access out of range.
+ *   The mask follows dsp_resnorm_train_fwd's rule (above) on the element index e = ((b*H + h)*N + i)*Mp + j, Mp = M rounded up to a multiple of
+ *   4: dsp_dropout_keep_mask over n = B*H*N*Mp elements, read as [B,H,N,Mp], is the mask applied.  thr == 0: no mask path.
+ *   backward from dout [B,N,H*64] contiguous with the forward's inputs, lse and (keep_scale, thr, seed, offset); with m = keep * keep_scale,
+ *   dP = (dout V^T) o m and D_i = sum_j P_ij dP_ij (= dout_i . out_i with out in fp32: the forward's out is NOT read — its rounding to the data
+ *   dtype would cost a row whose P sits on one key the cancellation of dS, which torch's soft-max backward has):
+ *     dV = (P o m)^T dout;  dS = P o (dP - D) / 8;  dK = dS^T q;  dq = dS K.
+ *   P is recomputed; no [B,H,N,M] tensor is written to memory in either direction.  dq [B,N,H*64], dk and dv [B,M,H*64] contiguous in the data
+ *   dtype.  workspace (backward, always): dsp_mha_train_workspace_bytes(B, N, M, H) bytes of device memory, 16-byte aligned (DSP_ENOSPC if
+ *   smaller) — D [B,H,N] in fp32, written by the pass that owns the queries and read by the one that owns the keys; host arithmetic only, 0 for
+ *   an empty problem, monotone in each argument, a multiple of 16.  act_dtype is DSP_F16 or DSP_BF16 (fp32 data is not served).  All pointers 16-byte aligned.  EVERY
+ *   OUTPUT ELEMENT IS WRITTEN.  A workgroup owns DSP_MHA_TRAIN_OWN_ROWS queries (forward, dq) or keys (dk, dv) of one (sample, head) and walks the
+ *   other side in tiles of DSP_MHA_TRAIN_TILE_ROWS in ascending order.  NO FLOAT ATOMICS and no hand-off between workgroups: the same inputs
+ *   give the same bits on every call.  Each of the three gradients may be NULL, and leaving one out does not change the bits of the others.
+ *   1 <= N, M <= DSP_MHA_TRAIN_MAX_LEN, 1 <= H <= 1024, B*H <= 2^25.  Bad sizes, null required pointers, misalignment, a stride that is not a
+ *   multiple of 8 or is below 64 H, an output that aliases an input: DSP_EINVAL before any launch; B == 0: DSP_OK. */
+#define DSP_MHA_TRAIN_MAX_LEN 4096
+#define DSP_MHA_TRAIN_OWN_ROWS 128
+#define DSP_MHA_TRAIN_TILE_ROWS 32
+int dsp_mha_train_fwd(const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask, float keep_scale,
+                      unsigned int thr, uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype, int B, int N, int M, int H,
+                      dsp_stream_t stream);
+size_t dsp_mha_train_workspace_bytes(int B, int N, int M, int H);
+int dsp_mha_train_bwd(const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
+                      const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
+                      void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream);
+
 /* Conv1d(Cin, Cout, K, stride 1, dilation 1, groups 1, padding P = (K-1)/2) on CHANNELS-LAST data under autograd (csrc/conv1d_train.hip),
  * fp16 / bf16 data — the FastSpeech2 feed-forward and variance-predictor convolutions of the training step without their transposes:
  *     y [b,t,co]  = [bias[co] +] sum_k sum_ci x[b, t+k-P, ci] * W[co,ci,k]        rows outside [0, T) of a sample count as zeros
