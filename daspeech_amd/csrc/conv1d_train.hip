@@ -16,6 +16,7 @@
 //                     t0-P .. t0+63+P are staged once (rows outside the sample as zeros) and a tap is a row offset into that image; the
 //                     128 x 64 weight tile of each (channel block, tap) goes through registers (loaded while the tile before it is multiplied)
 //                     into LDS.  Columns past Cout (Cout = 64, 192) are staged as zeros and not stored.
+// The operand types, cv_pack_kernel and the kernels of dW and db live in conv1d_train.h, shared with conv1d_stride2_train.hip:
 //   cv_wgrad_kernel   a workgroup of 4 waves owns (128 co x 128 ci, one tap, one split of DSP_CONV1D_TRAIN_WGRAD_ROWS rows of the flattened
 //                     B*T); it walks its rows 64 at a time in ascending order, dy and the tap-shifted x staged TRANSPOSED (row index
 //                     contiguous, two rows per 32-bit LDS write), and writes one fp32 partial [split][K][Cout][Cin];
@@ -23,57 +24,11 @@
 //   cv_db_part_kernel / cv_db_merge_kernel   column sums of dy over chunks of 256 rows, then the chunks in ascending order.
 // No float atomics, no hand-off between workgroups: the same inputs give the same bits on every call, and dx, dW, db are separate launches, so
 // leaving one out does not change the others.  Every row is computed, padded frames included.
-#include "common.h"
-#include "../../include/daspeech_decode.h"
+#include "conv1d_train.h"
 
 namespace dsp {
 
-typedef _Float16 cv_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cv_b8 __attribute__((ext_vector_type(8)));
-typedef float cv_acc __attribute__((ext_vector_type(16)));
-typedef unsigned short cv_u16;
-
-constexpr int CV_ROWS = DSP_CONV1D_TRAIN_ROW_TILE;        // rows of a sample per workgroup of cv_conv_kernel
-constexpr int CV_COLS = 128;                              // output columns per workgroup
-constexpr int CV_KC = 64;                                 // reduction channels per staged image
-constexpr int CV_PITCH = 72;                              // pitch (elements) of an LDS image with 64 k values: 144 bytes, 16-byte aligned rows
-constexpr int CV_MAX_K = DSP_CONV1D_TRAIN_MAX_K;
 constexpr int CV_XROWS = CV_ROWS + CV_MAX_K - 1;          // the row tile and its halo
-constexpr int CV_WG_ROWS = DSP_CONV1D_TRAIN_WGRAD_ROWS;   // rows per split of the weight gradient (one workspace partial each)
-constexpr int CV_WG_TILE = 128;                           // co and ci per workgroup of cv_wgrad_kernel
-constexpr int CV_DB_CHUNK = 256;                          // rows per partial of the bias gradient
-constexpr int CV_MAX_C = DSP_CONV1D_TRAIN_MAX_C;
-static_assert(CV_ROWS == 64 && CV_WG_ROWS % 64 == 0, "the wave layout below is written for 64-row tiles");
-#define CV_ROW(reg, hi) (((reg) & 3) + 8 * ((reg) >> 2) + 4 * (hi))
-
-template <typename E> struct Cv;
-template <> struct Cv<__half> {
-    using V = cv_h8;
-    static __device__ __forceinline__ cv_acc mma(V a, V b, cv_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Cv<__hip_bfloat16> {
-    using V = cv_b8;
-    static __device__ __forceinline__ cv_acc mma(V a, V b, cv_acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-
-// the 16-byte operand of lane `lane` for k step s of an image row block starting at img (k contiguous, CV_PITCH)
-template <typename E> __device__ __forceinline__ typename Cv<E>::V cv_frag(const cv_u16* img, int s, int lane)
-{
-    return *reinterpret_cast<const typename Cv<E>::V*>(img + (lane & 31) * CV_PITCH + 16 * s + 8 * (lane >> 5));
-}
-
-// ---------------------------------------------------------------- weight re-lay: [Cout][Cin][K] -> [K][Cout][Cin], or [K][Cin][Cout] with the taps reversed
-__global__ __launch_bounds__(256) void cv_pack_kernel(const cv_u16* __restrict__ w, cv_u16* __restrict__ wp, int Cin, int Cout, int K, int transposed)
-{
-    const long n = (long)K * Cin * Cout, e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    const int k = (int)(e / ((long)Cin * Cout));
-    const int rem = (int)(e - (long)k * Cin * Cout);
-    int co, ci, tap;
-    if (!transposed) { co = rem / Cin; ci = rem - co * Cin; tap = k; }
-    else { ci = rem / Cout; co = rem - ci * Cout; tap = K - 1 - k; }
-    wp[e] = w[((long)co * Cin + ci) * K + tap];
-}
 
 // ---------------------------------------------------------------- forward, and dx on dy with the transposed, tap-reversed weight
 // out[b,t,n] = [bias[n] +] sum_k sum_c in[b, t+k-P, c] . wp[k][n][c]
@@ -139,133 +94,6 @@ __global__ __launch_bounds__(256) void cv_conv_kernel(const E* __restrict__ in, 
         }
     }
 }
-
-// ---------------------------------------------------------------- weight gradient: one fp32 partial per split of the rows
-// two rows (r, r + 1) of 8 channels -> eight 32-bit words of the transposed image [channel][row]
-__device__ __forceinline__ void cv_put_t(cv_u16* dst, uint4 u0, uint4 u1, int g, int p)
-{
-    const uint32_t w0[4] = {u0.x, u0.y, u0.z, u0.w}, w1[4] = {u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        *reinterpret_cast<uint32_t*>(dst + (8 * g + 2 * x) * CV_PITCH + 2 * p) = (w0[x] & 0xffffu) | (w1[x] << 16);
-        *reinterpret_cast<uint32_t*>(dst + (8 * g + 2 * x + 1) * CV_PITCH + 2 * p) = (w0[x] >> 16) | (w1[x] & 0xffff0000u);
-    }
-}
-
-template <typename E>
-__global__ __launch_bounds__(256) void cv_wgrad_kernel(const E* __restrict__ dy, long ld_dy, const E* __restrict__ x, long ld_x,
-                                                       float* __restrict__ part, int T, int BT, int Cin, int Cout, int K, int ci_tiles)
-{
-    __shared__ __attribute__((aligned(16))) cv_u16 Ds[CV_WG_TILE * CV_PITCH], Xs[CV_WG_TILE * CV_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave & 1, wc = wave >> 1;
-    const int ci0 = ((int)blockIdx.x % ci_tiles) * CV_WG_TILE, co0 = ((int)blockIdx.x / ci_tiles) * CV_WG_TILE;
-    const int k = blockIdx.y, split = blockIdx.z, sh = k - (K - 1) / 2;
-    const int r_begin = split * CV_WG_ROWS, r_end = r_begin + CV_WG_ROWS < BT ? r_begin + CV_WG_ROWS : BT;
-    // a thread stages row pair p of channel groups g0 and g0 + 8 (8 channels each) of both images
-    const int p = tid & 31, g0 = tid >> 5;
-    uint4 dreg[2][2], xreg[2][2];
-#define CV_LOAD_ROWS(r0)                                                                                                           \
-    _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                                                \
-        const int r = (r0) + 2 * p + q;                                                                                            \
-        const bool in = r < r_end;                                                                                                 \
-        const int bb = in ? r / T : 0, ts = r - bb * T + sh;                                                                       \
-        const bool xin = in && ts >= 0 && ts < T;                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                            \
-            const int g = g0 + 8 * j;                                                                                              \
-            dreg[j][q] = (in && co0 + 8 * g < Cout) ? *reinterpret_cast<const uint4*>(dy + (size_t)r * (size_t)ld_dy + co0 + 8 * g) \
-                                                    : make_uint4(0u, 0u, 0u, 0u);                                                  \
-            xreg[j][q] = (xin && ci0 + 8 * g < Cin) ? *reinterpret_cast<const uint4*>(x + (size_t)(r + sh) * (size_t)ld_x + ci0 + 8 * g) \
-                                                    : make_uint4(0u, 0u, 0u, 0u);                                                  \
-        }                                                                                                                          \
-    }
-    cv_acc acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) acc[i][j][reg] = 0.f;
-    CV_LOAD_ROWS(r_begin)
-#pragma unroll 1
-    for (int r0 = r_begin; r0 < r_end; r0 += 64) {
-        __syncthreads();                                                    // the products of the rows before these have read both images
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            cv_put_t(Ds, dreg[j][0], dreg[j][1], g0 + 8 * j, p);
-            cv_put_t(Xs, xreg[j][0], xreg[j][1], g0 + 8 * j, p);
-        }
-        __syncthreads();
-        if (r0 + 64 < r_end) { CV_LOAD_ROWS(r0 + 64) }                      // in flight while these rows are multiplied
-        const cv_u16* A = Ds + 64 * wr * CV_PITCH;
-        const cv_u16* Bt = Xs + 64 * wc * CV_PITCH;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const typename Cv<E>::V va0 = cv_frag<E>(A, s, lane), va1 = cv_frag<E>(A + 32 * CV_PITCH, s, lane);
-            const typename Cv<E>::V vb0 = cv_frag<E>(Bt, s, lane), vb1 = cv_frag<E>(Bt + 32 * CV_PITCH, s, lane);
-            acc[0][0] = Cv<E>::mma(va0, vb0, acc[0][0]);
-            acc[0][1] = Cv<E>::mma(va0, vb1, acc[0][1]);
-            acc[1][0] = Cv<E>::mma(va1, vb0, acc[1][0]);
-            acc[1][1] = Cv<E>::mma(va1, vb1, acc[1][1]);
-        }
-    }
-#undef CV_LOAD_ROWS
-    const int col = lane & 31, hi = lane >> 5;
-    float* pk = part + ((size_t)split * K + k) * (size_t)Cout * (size_t)Cin;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ci = ci0 + 64 * wc + 32 * j + col;
-            if (ci >= Cin) continue;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int co = co0 + 64 * wr + 32 * i + CV_ROW(reg, hi);
-                if (co < Cout) pk[(size_t)co * Cin + ci] = acc[i][j][reg];
-            }
-        }
-}
-
-// the splits in ascending order; [K][Cout][Cin] fp32 -> [Cout][Cin][K] in the data dtype, rounded once
-template <typename E>
-__global__ __launch_bounds__(256) void cv_wgrad_merge_kernel(const float* __restrict__ part, int nsplit, int Cin, int Cout, int K, E* __restrict__ dw)
-{
-    const long n = (long)K * Cin * Cout, e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float acc = 0.f;
-    for (int s = 0; s < nsplit; ++s) acc += part[(size_t)s * n + e];
-    const int k = (int)(e / ((long)Cin * Cout));
-    const int rem = (int)(e - (long)k * Cin * Cout);
-    const int co = rem / Cin, ci = rem - co * Cin;
-    dw[((size_t)co * Cin + ci) * K + k] = from_f<E>(acc);
-}
-
-// ---------------------------------------------------------------- bias gradient: column sums in a fixed order
-// a workgroup owns 64 columns x CV_DB_CHUNK rows; thread (tx, ty) adds rows ty, ty + 4, ... in ascending order, then the four in ascending ty
-template <typename E>
-__global__ __launch_bounds__(256) void cv_db_part_kernel(const E* __restrict__ dy, long ld_dy, int BT, int Cout, float* __restrict__ part)
-{
-    __shared__ float red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, c = (int)blockIdx.y * 64 + tx;
-    const int r0 = (int)blockIdx.x * CV_DB_CHUNK, r1 = r0 + CV_DB_CHUNK < BT ? r0 + CV_DB_CHUNK : BT;
-    float a = 0.f;
-    for (int r = r0 + ty; r < r1; r += 4) a += to_f(dy[(size_t)r * (size_t)ld_dy + c]);
-    red[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0) part[(size_t)blockIdx.x * Cout + c] = ((red[0][tx] + red[1][tx]) + red[2][tx]) + red[3][tx];
-}
-__global__ __launch_bounds__(256) void cv_db_merge_kernel(const float* __restrict__ part, int nchunks, int Cout, void* __restrict__ db, int bdtype)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= Cout) return;
-    float acc = 0.f;
-    for (int k = 0; k < nchunks; ++k) acc += part[(size_t)k * Cout + c];
-    param_store(db, bdtype, c, acc);
-}
-
-static size_t cv_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-static size_t cv_pack_bytes(int Cin, int Cout, int K) { return cv_align16((size_t)K * Cin * Cout * 2); }
-static int cv_splits(long BT) { return (int)((BT + CV_WG_ROWS - 1) / CV_WG_ROWS); }
-static int cv_db_chunks(long BT) { return (int)((BT + CV_DB_CHUNK - 1) / CV_DB_CHUNK); }
 
 // what the entry points check; 1: nothing to do (no rows), 0: go on, < 0: refused
 static int cv_check(const char* who, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, long ld_a, int Ca, long ld_b, int Cb)
@@ -358,27 +186,15 @@ extern "C" int dsp_conv1d_train_bwd(const void* dy, long ld_dy, const void* x, l
         set_error("%s: workspace of dsp_conv1d_train_workspace_bytes(1, ...) bytes (16-byte aligned) needed", who);
         return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
     }
-    const int BT = B * T, nsplit = cv_splits(BT), nchunks = cv_db_chunks(BT);
-    const size_t nw = (size_t)K * Cin * Cout;
+    const int BT = B * T;
     char* base = (char*)workspace;
     void* wp = base;
     float* part_w = (float*)(base + cv_pack_bytes(Cin, Cout, K));
-    float* part_b = (float*)((char*)part_w + cv_align16((size_t)nsplit * nw * sizeof(float)));
+    float* part_b = (float*)((char*)part_w + cv_align16((size_t)cv_splits(BT) * (size_t)K * Cin * Cout * sizeof(float)));
     hipStream_t st = as_stream(stream);
     if (dx)      // the forward kernel on dy: Nin = Cout, Nout = Cin, the weight [K][Cin][Cout] with the taps reversed
         DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_conv<E>(st, dy, ld_dy, w, wp, 1, nullptr, bias_dtype, dx, (long)Cin, B, T, Cout, Cin, Cin, Cout, K));
-    if (dw) {
-        const int ci_tiles = (Cin + CV_WG_TILE - 1) / CV_WG_TILE, co_tiles = (Cout + CV_WG_TILE - 1) / CV_WG_TILE;
-        DSP_DISPATCH_ELEM_16(act_dtype, E, {
-            hipLaunchKernelGGL((cv_wgrad_kernel<E>), dim3((unsigned)(ci_tiles * co_tiles), (unsigned)K, (unsigned)nsplit), dim3(256), 0, st, (const E*)dy,
-                               ld_dy, (const E*)x, ld_x, part_w, T, BT, Cin, Cout, K, ci_tiles);
-            hipLaunchKernelGGL((cv_wgrad_merge_kernel<E>), dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, part_w, nsplit, Cin, Cout, K, (E*)dw);
-        });
-    }
-    if (db) {
-        DSP_DISPATCH_ELEM_16(act_dtype, E, hipLaunchKernelGGL((cv_db_part_kernel<E>), dim3((unsigned)nchunks, (unsigned)(Cout / 64)), dim3(256), 0, st,
-                                                              (const E*)dy, ld_dy, BT, Cout, part_b));
-        hipLaunchKernelGGL(cv_db_merge_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, st, part_b, nchunks, Cout, db, bias_dtype);
-    }
+    if (dw) DSP_DISPATCH_ELEM_16(act_dtype, E, (cv_launch_wgrad<E, 1>(st, dy, ld_dy, x, ld_x, part_w, dw, T, T, BT, Cin, Cout, K)));
+    if (db) DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_db<E>(st, dy, ld_dy, part_b, db, bias_dtype, BT, Cout));
     return check_launch(who);
 }

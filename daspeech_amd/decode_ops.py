@@ -52,11 +52,17 @@ Host-side mirror of the reference code these replace:
                       the weight and bias gradients fixed-order sums without float atomics; _ConvFFN / VariancePredictor keep their torch lines
                       where conv1d_channels_last_served says no (set_conv1d_train_hip(False): always); conv1d_channels_last_checked /
                       _sites_served are internal to those layers
+  conv1d_stride2_channels_last_autograd  fairseq speech_to_text/modules/convolution.py:13-59 — the two Conv1d(K 5, STRIDE 2, padding 2) of the
+                      encoder's Conv1dSubsampler in TRAINING mode on the channels-last tensor, without the transposes
+                      (csrc/conv1d_stride2_train.hip): the same contract as conv1d_channels_last_autograd with T_out = (T-1)//2 + 1 rows of y, Cin
+                      a multiple of 16 (the 80 filterbank channels) and Cout of 64; Conv1dSubsampler keeps its torch lines where
+                      conv1d_stride2_channels_last_served says no (set_conv1d_stride2_train_hip(False): always);
+                      conv1d_stride2_channels_last_checked / _sites_served are internal to that layer
 No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
 caller's torch lines run; the alignment gates of the C ABI are never reached with something they refuse.
-The six training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
+The training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
 that returns None or the reason — the ..._served() predicate asks it behind the switch and autocast gates, the raising ..._autograd() function
 raises the reason (_settled: after a dense copy where the reason begins with _LAYOUT) — and every autograd.Function launches through _launch
 (device, raw stream, return code), with _dropout_call / _dropout_thr_scale for the generator bookkeeping, _row_pitch for row-pitched views, the
@@ -1830,6 +1836,8 @@ CONV1D_TRAIN_ROW_TILE = 64       # DSP_CONV1D_TRAIN_ROW_TILE: rows of one sample
 CONV1D_TRAIN_WGRAD_ROWS = 1024   # DSP_CONV1D_TRAIN_WGRAD_ROWS: rows of the flattened B*T per split of the weight gradient (one workspace partial each)
 CONV1D_TRAIN_MAX_K = 15          # DSP_CONV1D_TRAIN_MAX_K
 CONV1D_TRAIN_MAX_C = 8192        # DSP_CONV1D_TRAIN_MAX_C
+CONV1D_STRIDE2_TRAIN_HIP = True  # set_conv1d_stride2_train_hip(False): Conv1dSubsampler keeps its torch lines in training on every input
+CONV1D_STRIDE2_CIN_GRID = 16     # the stride-2 operator's input channels: multiples of one k step of the matrix-core product (80 = 64 + 16)
 
 
 def set_conv1d_train_hip(on: bool) -> bool:
@@ -1840,13 +1848,13 @@ def set_conv1d_train_hip(on: bool) -> bool:
     return old
 
 
-def _conv1d_module_problem(conv) -> Optional[str]:
-    """None when `conv` is a convolution the operator computes, else what is in the way"""
+def _conv1d_module_problem(conv, stride: int = 1) -> Optional[str]:
+    """None when `conv` is a convolution the operator of this stride computes, else what is in the way"""
     if not isinstance(conv, torch.nn.Conv1d):
         return "conv has to be an nn.Conv1d"
     K = conv.kernel_size[0]
-    if conv.stride != (1,):
-        return f"stride {conv.stride[0]}: only 1 is served"
+    if conv.stride != (stride,):
+        return f"stride {conv.stride[0]}: only {stride} is served"
     if conv.dilation != (1,):
         return f"dilation {conv.dilation[0]}: only 1 is served"
     if conv.groups != 1:
@@ -1858,13 +1866,13 @@ def _conv1d_module_problem(conv) -> Optional[str]:
     return None
 
 
-def _conv1d_channels_ok(C: int) -> bool:
-    return 64 <= C <= CONV1D_TRAIN_MAX_C and C % 64 == 0
+def _conv1d_channels_ok(C: int, grid: int = 64) -> bool:
+    return grid <= C <= CONV1D_TRAIN_MAX_C and C % grid == 0
 
 
-def _conv1d_train_problem(x, weight, bias) -> Optional[str]:
-    """None when dsp_conv1d_train_fwd / _bwd take these tensors as they are, else what is in the way (a layout of x that a dense copy settles
-    begins with _LAYOUT)"""
+def _conv1d_train_problem(x, weight, bias, stride: int = 1) -> Optional[str]:
+    """None when dsp_conv1d_train_fwd / _bwd (stride 2: dsp_conv1d_s2_train_fwd / _bwd) take these tensors as they are, else what is in the way
+    (a layout of x that a dense copy settles begins with _LAYOUT)"""
     if not (isinstance(x, Tensor) and x.dim() == 3):
         return "x has to be a [B,T,Cin] tensor"
     if not (isinstance(weight, Tensor) and weight.dim() == 3):
@@ -1876,7 +1884,10 @@ def _conv1d_train_problem(x, weight, bias) -> Optional[str]:
     Cout, Cw, K = weight.shape
     if Cw != Cin:
         return f"weight {tuple(weight.shape)} does not fit x with {Cin} channels (groups 1: [Cout, {Cin}, K])"
-    if not (_conv1d_channels_ok(Cin) and _conv1d_channels_ok(Cout)):
+    if stride == 2 and not (_conv1d_channels_ok(Cin, CONV1D_STRIDE2_CIN_GRID) and _conv1d_channels_ok(Cout)):
+        return (f"Cin = {Cin} / Cout = {Cout}: Cin a multiple of {CONV1D_STRIDE2_CIN_GRID} and Cout a multiple of 64, both up to "
+                f"{CONV1D_TRAIN_MAX_C}, are served")
+    if stride == 1 and not (_conv1d_channels_ok(Cin) and _conv1d_channels_ok(Cout)):
         return f"Cin = {Cin} / Cout = {Cout}: multiples of 64 up to {CONV1D_TRAIN_MAX_C} are served"
     if K % 2 == 0 or not 1 <= K <= CONV1D_TRAIN_MAX_K:
         return f"kernel size {K}: odd sizes from 1 to {CONV1D_TRAIN_MAX_K} are served"
@@ -1899,7 +1910,7 @@ def conv1d_channels_last_served(x: Tensor, conv: "torch.nn.Conv1d") -> bool:
     autocast off, x a GPU tensor in fp16 or bf16 with unit column stride, one row stride on the 16-byte grid and a 16-byte aligned start,
     conv an nn.Conv1d(Cin, Cout, K) with stride 1, dilation 1, groups 1 and zero padding (K-1)//2, K odd and at most 15, both channel counts
     multiples of 64, weight and bias contiguous and aligned in the dtype of x (bias: or fp32).  Everything else — CPU tensors, fp32, float64,
-    the postnet's 80 channels, the subsampler's stride 2 — keeps the torch lines."""
+    the postnet's 80 channels — keeps the torch lines; the subsampler's stride 2 is conv1d_stride2_channels_last_served's question."""
     if not CONV1D_TRAIN_HIP or torch.is_autocast_enabled():
         return False
     if _conv1d_module_problem(conv) is not None or _conv1d_train_problem(x, conv.weight, conv.bias) is not None:
@@ -1924,24 +1935,30 @@ def conv1d_channels_last_sites_served(x: Tensor, convs) -> bool:
     return True
 
 
+_CONV1D_ENTRIES = {1: ("dsp_conv1d_train_workspace_bytes", "dsp_conv1d_train_fwd", "dsp_conv1d_train_bwd"),
+                   2: ("dsp_conv1d_s2_train_workspace_bytes", "dsp_conv1d_s2_train_fwd", "dsp_conv1d_s2_train_bwd")}      # by stride
+
+
 class _Conv1dTrainFn(torch.autograd.Function):
-    """dsp_conv1d_train_fwd / _bwd.  Saved for the backward: x and weight, nothing else — the re-laid weight lives in a workspace that does
-    not outlive the call, so no copy can go stale when the optimizer changes the weight."""
+    """dsp_conv1d_train_fwd / _bwd, and with stride 2 dsp_conv1d_s2_train_fwd / _bwd (y and dy then have (T - 1) // 2 + 1 rows a sample).  Saved
+    for the backward: x and weight, nothing else — the re-laid weight lives in a workspace that does not outlive the call, so no copy can go
+    stale when the optimizer changes the weight."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, ld):
+    def forward(ctx, x, weight, bias, ld, stride=1):
         B, T, Cin = x.shape
         Cout, _, K = weight.shape
         lib = _lib.load()
+        ws_bytes, fwd, _ = _CONV1D_ENTRIES[stride]
         dev = x.device
-        y = torch.empty((B, T, Cout), dtype=x.dtype, device=dev)
+        y = torch.empty((B, (T - 1) // stride + 1, Cout), dtype=x.dtype, device=dev)
         if B * T:
-            nbytes = int(lib.dsp_conv1d_train_workspace_bytes(0, B, T, Cin, Cout, K))
+            nbytes = int(getattr(lib, ws_bytes)(0, B, T, Cin, Cout, K))
             ws = _workspace(dev, nbytes)
-            _launch(dev, lib.dsp_conv1d_train_fwd, x.data_ptr(), ld, weight.data_ptr(), _ptr(bias), y.data_ptr(), Cout, _ptr(ws), nbytes,
+            _launch(dev, getattr(lib, fwd), x.data_ptr(), ld, weight.data_ptr(), _ptr(bias), y.data_ptr(), Cout, _ptr(ws), nbytes,
                     _HALF_CODES[x.dtype], _FLOAT_CODES[(x if bias is None else bias).dtype], B, T, Cin, Cout, K)
         ctx.save_for_backward(x, weight)
-        ctx.call = (ld, None if bias is None else bias.dtype)
+        ctx.call = (ld, None if bias is None else bias.dtype, stride)
         ctx.set_materialize_grads(False)
         return y
 
@@ -1949,31 +1966,32 @@ class _Conv1dTrainFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        ld, bias_dtype = ctx.call
+        ld, bias_dtype, stride = ctx.call
         need = ctx.needs_input_grad
         want_dx, want_dw, want_db = need[0], need[1], bias_dtype is not None and need[2]
         if dy is None or not (want_dx or want_dw or want_db):
-            return None, None, None, None
+            return None, None, None, None, None
         B, T, Cin = x.shape
         Cout, _, K = weight.shape
         ld_dy = _row_pitch(dy)
         if ld_dy is None or ld_dy < Cout or ld_dy % 8 or dy.data_ptr() % 16:       # a transpose, a broadcast, a narrow at an odd offset
             dy, ld_dy = dy.clone(memory_format=torch.contiguous_format), Cout
         lib = _lib.load()
+        ws_bytes, _, bwd = _CONV1D_ENTRIES[stride]
         dev = x.device
         dx = torch.empty((B, T, Cin), dtype=x.dtype, device=dev) if want_dx else None
         dw = torch.empty((Cout, Cin, K), dtype=x.dtype, device=dev) if want_dw else None
         db = torch.empty((Cout,), dtype=bias_dtype, device=dev) if want_db else None
         if B * T:
-            nbytes = int(lib.dsp_conv1d_train_workspace_bytes(1, B, T, Cin, Cout, K))
+            nbytes = int(getattr(lib, ws_bytes)(1, B, T, Cin, Cout, K))
             ws = _workspace(dev, nbytes)
-            _launch(dev, lib.dsp_conv1d_train_bwd, dy.data_ptr(), ld_dy, x.data_ptr(), ld, weight.data_ptr(), _ptr(dx), _ptr(dw), _ptr(db),
+            _launch(dev, getattr(lib, bwd), dy.data_ptr(), ld_dy, x.data_ptr(), ld, weight.data_ptr(), _ptr(dx), _ptr(dw), _ptr(db),
                     _ptr(ws), nbytes, _HALF_CODES[x.dtype], _FLOAT_CODES[bias_dtype or x.dtype], B, T, Cin, Cout, K)
         else:
             for t in (dw, db):                                              # no rows: the empty sums
                 if t is not None:
                     t.zero_()
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def conv1d_channels_last_checked(x, weight, bias=None):
@@ -1998,6 +2016,77 @@ def conv1d_channels_last_autograd(x: Tensor, weight: Tensor, bias: Optional[Tens
     gradient's run in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
     x, weight, bias = _settled("conv1d_channels_last_autograd", _conv1d_train_problem, (x, weight, bias), 1)
     return conv1d_channels_last_checked(x, _dense16(weight), _dense16(bias))
+
+
+# ------------------------------------------------------------------------------------------------ stride-2 channels-last Conv1d under autograd (csrc/conv1d_stride2_train.hip)
+def set_conv1d_stride2_train_hip(on: bool) -> bool:
+    """Switch the HIP stride-2 channels-last convolution of Conv1dSubsampler's training branch on or off; returns the previous setting.  Off:
+    conv1d_stride2_channels_last_served answers False and the torch lines run."""
+    global CONV1D_STRIDE2_TRAIN_HIP
+    old, CONV1D_STRIDE2_TRAIN_HIP = CONV1D_STRIDE2_TRAIN_HIP, bool(on)
+    return old
+
+
+def _conv1d_s2_module_problem(conv) -> Optional[str]:
+    """_conv1d_module_problem for the stride-2 operator: the same rule with stride 2"""
+    return _conv1d_module_problem(conv, 2)
+
+
+def _conv1d_s2_train_problem(x, weight, bias) -> Optional[str]:
+    """_conv1d_train_problem for dsp_conv1d_s2_train_fwd / _bwd: the same rule with Cin on the grid of 16"""
+    return _conv1d_train_problem(x, weight, bias, 2)
+
+
+def conv1d_stride2_channels_last_served(x: Tensor, conv: "torch.nn.Conv1d") -> bool:
+    """True when conv1d_stride2_channels_last_autograd serves a training branch for `conv` on the channels-last x [B,T,Cin] as it is: the
+    switch is on, autocast off, x a GPU tensor in fp16 or bf16 with unit column stride, one row stride on the 16-byte grid and a 16-byte
+    aligned start, conv an nn.Conv1d(Cin, Cout, K) with stride 2, dilation 1, groups 1 and zero padding (K-1)//2, K odd and at most 15, Cin
+    a multiple of 16 and Cout of 64, weight and bias contiguous and aligned in the dtype of x (bias: or fp32).  Everything else — CPU
+    tensors, fp32, float64, another stride — keeps the torch lines."""
+    if not CONV1D_STRIDE2_TRAIN_HIP or torch.is_autocast_enabled():
+        return False
+    if _conv1d_s2_module_problem(conv) is not None or _conv1d_s2_train_problem(x, conv.weight, conv.bias) is not None:
+        return False
+    return _as_handed_over(conv.weight, conv.bias)
+
+
+def conv1d_stride2_channels_last_sites_served(x: Tensor, convs) -> bool:
+    """conv1d_stride2_channels_last_served for the CHAIN of convolutions of Conv1dSubsampler, asked once per forward before the tensors
+    between them exist: the first reads x, each later one a fresh dense tensor with the dtype and device of x and HALF the channels its
+    predecessor leaves (the GLU between them)."""
+    if not CONV1D_STRIDE2_TRAIN_HIP or torch.is_autocast_enabled() or not conv1d_stride2_channels_last_served(x, convs[0]):
+        return False
+    C = convs[0].out_channels // 2
+    for conv in convs[1:]:
+        w, b = conv.weight, conv.bias
+        if (_conv1d_s2_module_problem(conv) is not None or conv.in_channels != C or not _conv1d_channels_ok(C, CONV1D_STRIDE2_CIN_GRID)
+                or not _conv1d_channels_ok(conv.out_channels) or w.dtype != x.dtype or w.device != x.device or not _as_handed_over(w, b)):
+            return False
+        if b is not None and ((b.dtype != x.dtype and b.dtype != torch.float32) or b.device != x.device):
+            return False
+        C = conv.out_channels // 2
+    return True
+
+
+def conv1d_stride2_channels_last_checked(x, weight, bias=None):
+    """INTERNAL to the package's layers: conv1d_stride2_channels_last_autograd WITHOUT its argument checks, valid only on arguments that
+    conv1d_stride2_channels_last_served / _sites_served accepted."""
+    ld = _row_pitch(x)
+    if ld is None or ld % 8 or x.data_ptr() % 16:       # _sites_served asked before x existed; an operator's output is dense, a view of it is copied
+        x, ld = x.clone(memory_format=torch.contiguous_format), x.shape[-1]
+    return _Conv1dTrainFn.apply(x, weight, bias, ld, 2)
+
+
+def conv1d_stride2_channels_last_autograd(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """y[b,t,co] = [bias[co] +] sum_k sum_ci x[b, 2t+k-P, ci] weight[co,ci,k] for t in [0, (T-1)//2 + 1), P = (K-1)/2, rows outside [0, T) of
+    a sample as zeros — what F.conv1d(x.transpose(1, 2), weight, bias, stride=2, padding=P).transpose(1, 2) computes, on the channels-last
+    tensor without the transposes, and differentiable w.r.t. x, weight and bias (include/daspeech_decode.h: dsp_conv1d_s2_train_fwd / _bwd).
+    x [B,T,Cin] fp16 / bf16 on the GPU (fp32 keeps the torch lines; float64 is refused, never narrowed), weight [Cout,Cin,K] in nn.Conv1d's
+    layout and the dtype of x, bias [Cout] in that dtype or fp32, Cin a multiple of 16, Cout a multiple of 64, K odd and at most 15.  Views,
+    rounding, the saved tensors (x and weight only) and bit-reproducibility are conv1d_channels_last_autograd's; a gradient of x that
+    autograd does not ask for (the filterbank input of the first layer) is not computed.  Raises RuntimeError on what is not served."""
+    x, weight, bias = _settled("conv1d_stride2_channels_last_autograd", _conv1d_s2_train_problem, (x, weight, bias), 1)
+    return conv1d_stride2_channels_last_checked(x, _dense16(weight), _dense16(bias))
 
 
 class SplitConv1d:

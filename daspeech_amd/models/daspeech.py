@@ -100,6 +100,17 @@ class Conv1dSubsampler(nn.Module):
                     if Cp != 2 * C: x2 = F.pad(x2, (0, Cp - 2 * C))
                     x = F.glu(conv(x2.contiguous()), dim=-1)
                 return x, self.out_lengths(lens)
+        if (self.training or torch.is_grad_enabled()) and decode_ops.conv1d_stride2_channels_last_sites_served(x, self.conv_layers):
+            # training, fp16 / bf16: the stride-2 convolutions under autograd on the channels-last tensor (csrc/conv1d_stride2_train.hip), no
+            # transposes, no MIOpen; bias + GLU as the HIP operator between the GEMMs where it is served (else the bias in the convolution)
+            fused = decode_ops.bias_act_dropout_sites_served(x, [(c.out_channels, c.bias, "glu") for c in self.conv_layers])
+            for conv in self.conv_layers:
+                if fused:
+                    x = decode_ops.conv1d_stride2_channels_last_checked(x, conv.weight)
+                    x = decode_ops.bias_act_dropout_checked(x, conv.bias, "glu", 0.0, self.training)
+                else:
+                    x = F.glu(decode_ops.conv1d_stride2_channels_last_checked(x, conv.weight, conv.bias), dim=-1)
+            return x, self.out_lengths(lens)
         x = x.transpose(1, 2)                        # B x C x T
         for conv in self.conv_layers:
             x = F.glu(conv(x), dim=1)

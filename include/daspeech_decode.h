@@ -447,6 +447,26 @@ int dsp_conv1d_train_fwd(const void* x, long ld_x, const void* w, const void* bi
 int dsp_conv1d_train_bwd(const void* dy, long ld_dy, const void* x, long ld_x, const void* w, void* dx, void* dw, void* db, void* workspace,
                          size_t workspace_bytes, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, dsp_stream_t stream);
 
+/* The same convolution with STRIDE 2 (csrc/conv1d_stride2_train.hip) — the two layers of the encoder's Conv1dSubsampler in the training step:
+ *     T_out = (T - 1) / 2 + 1 (integer division)
+ *     y [b,t,co]  = [bias[co] +] sum_k sum_ci x[b, 2t+k-P, ci] * W[co,ci,k]        t in [0, T_out); rows outside [0, T) of a sample count as zeros
+ *     dx[b,u,ci]  = sum over the k with (u+P-k) even and 0 <= (u+P-k)/2 < T_out of sum_co dy[b, (u+P-k)/2, co] * W[co,ci,k]
+ *     dW[co,ci,k] = sum_b sum_t  dy[b,t,co] * x[b, 2t+k-P, ci]
+ *     db[co]      = sum_b sum_t  dy[b,t,co]
+ *   The argument lists, layouts, dtypes, rounding, return codes and the workspace contract are those of dsp_conv1d_train_*; T is the INPUT
+ *   length: x and dx have T rows a sample, y and dy T_out.  Rows of dx that no tap reaches (K = 1: the odd rows) and taps of dW that never land
+ *   inside a sample (T = 1: all but the centre) are written as zeros.
+ *   Served: Cin a multiple of 16 from 16 (the last block of 64 reduction channels may hold 16 / 32 / 48: memory behind column Cin of a row is
+ *   never read), Cout a multiple of 64, both up to DSP_CONV1D_TRAIN_MAX_C, K odd, 1 <= K <= DSP_CONV1D_TRAIN_MAX_K, T >= 1, B*T <= 2^24.
+ *   A workgroup of the forward owns DSP_CONV1D_TRAIN_ROW_TILE rows of y of ONE sample, one of dx as many rows of one parity of ONE sample; dW
+ *   and db are cut over the flattened B*T_out rows as the stride-1 operator cuts B*T.  No float atomics, no hand-off between workgroups: the
+ *   same inputs give the same bits on every call, and leaving out one of dx / dW / db does not change the bits of the others. */
+size_t dsp_conv1d_s2_train_workspace_bytes(int phase, int B, int T, int Cin, int Cout, int K);
+int dsp_conv1d_s2_train_fwd(const void* x, long ld_x, const void* w, const void* bias, void* y, long ld_y, void* workspace, size_t workspace_bytes,
+                            int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, dsp_stream_t stream);
+int dsp_conv1d_s2_train_bwd(const void* dy, long ld_dy, const void* x, long ld_x, const void* w, void* dx, void* dw, void* db, void* workspace,
+                            size_t workspace_bytes, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, dsp_stream_t stream);
+
 /* fp32-accurate Conv1d ("same" padding, stride 1) on the fp16 matrix cores by operand splitting (x = xh + xl/2048, w = wh + wl/2048;
  * the products xh.wh, xh.wl, xl.wh are exact in the fp32 accumulator, the dropped xl.wl term is 2^-22 relative) — for the
  * FastSpeech2 FFT feed-forward convolutions (fairseq fastspeech2.py:42-63), which MIOpen runs at 60-70 TFLOP/s in fp32.
