@@ -252,7 +252,12 @@ def _lengths_to_mask(lens: Tensor, n: int = None) -> Tensor:
 
 
 class S2SDAGFastSpeech2Loss(NATDAGLoss):
-    """registered name: s2s_dag_fastspeech2_loss (s2s_dag_fastspeech2_loss.py:26)."""
+    """registered name: s2s_dag_fastspeech2_loss (s2s_dag_fastspeech2_loss.py:26).
+
+    The l1 / duration / pitch / energy losses come from decode_ops.tts_losses_checked (one HIP operator under autograd, the masks taken from the
+    lengths on the device) where decode_ops.tts_losses_served accepts the tensors, from the reference's torch lines otherwise (CPU tensors,
+    float64, autocast, decode_ops.set_tts_loss_hip(False)).  The operator's losses are fp32 whatever the model's dtype: with an fp16 model
+    the four losses, tts-loss and loss are then fp32 tensors, where the torch lines give fp16."""
 
     def _lazy_softmax(self) -> bool:
         # argmax strategy, reference GPU behaviour: the gather must really overwrite the logits with their soft-max, because the
@@ -318,17 +323,24 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
             features_padding_mask = ~_lengths_to_mask(sample["target_text_lengths"] - 1, input_to_tts.shape[1])
         _feat_out, _feat_out_post, _, log_dur_out, pitch_out, energy_out = model.tts(
             input_to_tts, features_padding_mask, durations=sample["durations"], pitches=sample["pitches"], energies=sample["energies"])
-        src_mask = _lengths_to_mask(sample["target_text_lengths"] - 1, log_dur_out.shape[1])                 # -1: no <bos>
-        F_ = min(_feat_out.shape[1], sample["target_audio"].shape[1])
-        tgt_mask = _lengths_to_mask(sample["target_audio_lengths"].clamp(max=F_), F_)
-        feat_out, feat = _feat_out[:, :F_][tgt_mask], sample["target_audio"][:, :F_][tgt_mask]
-        l1_loss = F.l1_loss(feat_out, feat, reduction="mean")
-        if _feat_out_post is not None:                                                                       # --add-postnet (:281-282)
-            l1_loss = l1_loss + F.l1_loss(_feat_out_post[:, :F_][tgt_mask], feat, reduction="mean")
-        pitch_loss = F.mse_loss(pitch_out[src_mask], sample["pitches"][src_mask], reduction="mean")
-        energy_loss = F.mse_loss(energy_out[src_mask], sample["energies"][src_mask], reduction="mean")
-        log_dur = torch.log(sample["durations"].to(log_dur_out.dtype) + 1)[src_mask]
-        dur_loss = F.mse_loss(log_dur_out[src_mask], log_dur, reduction="mean")
+        tts_args = (_feat_out, _feat_out_post, sample["target_audio"], sample["target_audio_lengths"], log_dur_out, pitch_out, energy_out,
+                    sample["durations"], sample["pitches"], sample["energies"], sample["target_text_lengths"] - 1)      # -1: no <bos>
+        if decode_ops.tts_losses_served(*tts_args):
+            # one HIP operator under autograd, the masks taken from the lengths on the device: no mask tensor, no selection, no host read,
+            # fp32 sums in a fixed order — the four losses are fp32 also for an fp16 model
+            l1_loss, dur_loss, pitch_loss, energy_loss = decode_ops.tts_losses_checked(*tts_args).unbind(0)
+        else:
+            src_mask = _lengths_to_mask(sample["target_text_lengths"] - 1, log_dur_out.shape[1])             # -1: no <bos>
+            F_ = min(_feat_out.shape[1], sample["target_audio"].shape[1])
+            tgt_mask = _lengths_to_mask(sample["target_audio_lengths"].clamp(max=F_), F_)
+            feat_out, feat = _feat_out[:, :F_][tgt_mask], sample["target_audio"][:, :F_][tgt_mask]
+            l1_loss = F.l1_loss(feat_out, feat, reduction="mean")
+            if _feat_out_post is not None:                                                                   # --add-postnet (:281-282)
+                l1_loss = l1_loss + F.l1_loss(_feat_out_post[:, :F_][tgt_mask], feat, reduction="mean")
+            pitch_loss = F.mse_loss(pitch_out[src_mask], sample["pitches"][src_mask], reduction="mean")
+            energy_loss = F.mse_loss(energy_out[src_mask], sample["energies"][src_mask], reduction="mean")
+            log_dur = torch.log(sample["durations"].to(log_dur_out.dtype) + 1)[src_mask]
+            dur_loss = F.mse_loss(log_dur_out[src_mask], log_dur, reduction="mean")
         tts_loss = l1_loss + dur_loss + pitch_loss + energy_loss
         loss = dag_loss["loss"] + tts_loss * self.cfg.tts_loss_weight
         sample_size = 1

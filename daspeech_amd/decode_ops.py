@@ -58,6 +58,12 @@ Host-side mirror of the reference code these replace:
                       a multiple of 16 (the 80 filterbank channels) and Cout of 64; Conv1dSubsampler keeps its torch lines where
                       conv1d_stride2_channels_last_served says no (set_conv1d_stride2_train_hip(False): always);
                       conv1d_stride2_channels_last_checked / _sites_served are internal to that layer
+  tts_losses_autograd   DASpeech/criterions/s2s_dag_fastspeech2_loss.py:266-290 — the l1 (+ postnet), duration, pitch and energy losses of the
+                      released objective as one operator under autograd (csrc/tts_loss_train.hip): fp32 / fp16 / bf16 data, fp32 arithmetic and
+                      four fp32 results, the masks taken from the lengths on the device (no mask tensor, no boolean selection, no host read),
+                      the mel tensors read through their strides (no [:, :F_] slice), sums in a fixed order without float atomics, a backward of
+                      one launch that recomputes the differences and writes dense gradients; S2SDAGFastSpeech2Loss keeps its torch lines
+                      where tts_losses_served says no (set_tts_loss_hip(False): always); tts_losses_checked is internal to that criterion
 No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
@@ -2087,6 +2093,169 @@ def conv1d_stride2_channels_last_autograd(x: Tensor, weight: Tensor, bias: Optio
     autograd does not ask for (the filterbank input of the first layer) is not computed.  Raises RuntimeError on what is not served."""
     x, weight, bias = _settled("conv1d_stride2_channels_last_autograd", _conv1d_s2_train_problem, (x, weight, bias), 1)
     return conv1d_stride2_channels_last_checked(x, _dense16(weight), _dense16(bias))
+
+
+# ------------------------------------------------------------------------------------------------ the four TTS losses under autograd (csrc/tts_loss_train.hip)
+TTS_LOSS_HIP = True          # set_tts_loss_hip(False): S2SDAGFastSpeech2Loss keeps its torch lines (masks, selections, F.l1_loss / F.mse_loss) on every input
+TTSLOSS_CHUNK_ROWS = 32      # DSP_TTSLOSS_CHUNK_ROWS: mel rows per reduction chunk of the forward (one workspace partial each)
+TTSLOSS_CHUNK_ELEMS = 1024   # DSP_TTSLOSS_CHUNK_ELEMS: [B,N] elements per reduction chunk
+TTSLOSS_MAX_ELEMS = 1 << 30  # DSP_TTSLOSS_MAX_ELEMS
+_INT_LENS = (torch.int64, torch.int32)
+
+
+def set_tts_loss_hip(on: bool) -> bool:
+    """Switch the HIP TTS-loss operator of S2SDAGFastSpeech2Loss on or off; returns the previous setting.  Off: tts_losses_served answers
+    False and the criterion's torch lines run."""
+    global TTS_LOSS_HIP
+    old, TTS_LOSS_HIP = TTS_LOSS_HIP, bool(on)
+    return old
+
+
+def _tts_loss_problem(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                      src_lens) -> Optional[str]:
+    """None when dsp_tts_loss_fwd / _bwd take these tensors as they are, else what is in the way (a layout that a dense copy settles begins
+    with _LAYOUT)"""
+    mel = (feat_out, target_audio) if feat_post is None else (feat_out, target_audio, feat_post)
+    var = (log_dur_out, pitch_out, energy_out, pitches, energies)
+    for t in mel + var + (audio_lens, durations, src_lens):
+        if not isinstance(t, Tensor):
+            return "every argument except feat_post has to be a tensor"
+    dt, dev = feat_out.dtype, feat_out.device
+    if dt not in _FLOAT_CODES:
+        return f"the data has to be fp32, fp16 or bf16, got {dt} (float64 is refused, never narrowed)"
+    for t in mel + var:
+        if t.dtype != dt:
+            return f"one floating dtype for all data tensors: {dt} and {t.dtype}"
+    if durations.dtype not in _INT_LENS or audio_lens.dtype not in _INT_LENS or src_lens.dtype not in _INT_LENS:
+        return "durations and both length vectors have to be int64 or int32"
+    if feat_out.dim() != 3 or target_audio.dim() != 3 or log_dur_out.dim() != 2:
+        return "feat_out [B,F,C], target_audio [B,Fa,C] and the variance tensors [B,N] expected"
+    B, F, C = feat_out.shape
+    Fa, N = target_audio.shape[1], log_dur_out.shape[1]
+    if target_audio.shape[0] != B or target_audio.shape[2] != C or (feat_post is not None and feat_post.shape != feat_out.shape):
+        return (f"feat_out {tuple(feat_out.shape)}, target_audio {tuple(target_audio.shape)} and feat_post have to share B and C, "
+                f"feat_post the whole shape of feat_out")
+    for t in var + (durations,):
+        if t.shape != (B, N):
+            return f"the six variance tensors have to share the shape [{B},{N}], got {tuple(t.shape)}"
+    if audio_lens.shape != (B,) or src_lens.shape != (B,):
+        return f"both length vectors have to be [{B}]"
+    if min(B, F, Fa, C, N) < 1 or B * max(F, Fa) * C > TTSLOSS_MAX_ELEMS or B * N > TTSLOSS_MAX_ELEMS:
+        return f"sizes outside the operator's limits (every dimension >= 1, B*F*C and B*N at most 2^30): B={B} F={F} Fa={Fa} C={C} N={N}"
+    if target_audio.requires_grad or pitches.requires_grad or energies.requires_grad:
+        return "the targets must not require grad (they get no gradient)"
+    for t in mel + var + (audio_lens, durations, src_lens):
+        if not t.is_cuda:
+            return _NOT_GPU
+        if t.device != dev:
+            return "all tensors have to be on one device"
+    for t in mel:
+        if (t.stride(2) != 1 and C > 1) or t.data_ptr() % t.element_size():
+            return _LAYOUT + ": feat_out, feat_post and target_audio need unit column stride and a start on the element grid"
+    for t in var + (durations, audio_lens, src_lens):
+        if not t.is_contiguous() or t.data_ptr() % t.element_size():
+            return _LAYOUT + ": the [B,N] tensors and the length vectors have to be contiguous"
+    return None
+
+
+def tts_losses_served(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                      src_lens) -> bool:
+    """True when tts_losses_autograd serves these arguments as they are: the switch is on, autocast off, GPU tensors of one floating dtype
+    (fp32 / fp16 / bf16), feat_out [B,F,C], feat_post None or shaped like it, target_audio [B,Fa,C] — each with unit column stride, any batch
+    and row stride —, the six [B,N] tensors of one shape and contiguous (durations int64 / int32), both length vectors [B] int64 / int32 and
+    contiguous, no target that requires grad, every dimension >= 1 and B*F*C, B*N at most 2^30.  There is no randomness: a capturing stream
+    is no reason to decline.  Everything else — CPU tensors, float64, mixed dtypes, another layout — keeps the torch lines."""
+    if not TTS_LOSS_HIP or torch.is_autocast_enabled():
+        return False
+    return _tts_loss_problem(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                             src_lens) is None
+
+
+def _tts_loss_forward(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                      src_lens):
+    """dsp_tts_loss_fwd: (losses fp32 [4], inv_counts fp32 [2], call) — `call` is what both entry points take between the pointers"""
+    B, F, C = feat_out.shape
+    F_, N = min(F, target_audio.shape[1]), log_dur_out.shape[1]
+    dev = feat_out.device
+    lib = _lib.load()
+    losses = torch.empty((4,), dtype=torch.float32, device=dev)
+    inv = torch.empty((2,), dtype=torch.float32, device=dev)
+    nbytes = int(lib.dsp_tts_loss_workspace_bytes(B, F_, N))
+    ws = _workspace(dev, nbytes)
+    post = (None, 0, 0) if feat_post is None else (feat_post.data_ptr(), feat_post.stride(0), feat_post.stride(1))
+    ins = (feat_out.data_ptr(), feat_out.stride(0), feat_out.stride(1)) + post + \
+        (target_audio.data_ptr(), target_audio.stride(0), target_audio.stride(1), audio_lens.data_ptr(), log_dur_out.data_ptr(),
+         pitch_out.data_ptr(), energy_out.data_ptr(), durations.data_ptr(), pitches.data_ptr(), energies.data_ptr(), src_lens.data_ptr(),
+         int(audio_lens.dtype == torch.int64), int(durations.dtype == torch.int64))
+    _launch(dev, lib.dsp_tts_loss_fwd, *ins, losses.data_ptr(), inv.data_ptr(), _ptr(ws), nbytes, _FLOAT_CODES[feat_out.dtype], B, F_, C, N)
+    return losses, inv, ins
+
+
+class _TtsLossFn(torch.autograd.Function):
+    """dsp_tts_loss_fwd / _bwd.  Saved for the backward: the inputs and the two reciprocals — no mask, no difference."""
+
+    @staticmethod
+    def forward(ctx, feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies, src_lens):
+        losses, inv, ins = _tts_loss_forward(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations,
+                                             pitches, energies, src_lens)
+        ctx.save_for_backward(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                              src_lens, inv)
+        ctx.ins = ins
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        feat_out, feat_post, log_dur_out, inv = saved[0], saved[1], saved[4], saved[11]
+        need = ctx.needs_input_grad
+        dev = feat_out.device
+        if g.dtype != torch.float32 or not g.is_contiguous():              # a broadcast gradient (losses.sum()), another dtype
+            g = g.to(torch.float32).contiguous()
+        B, F, C = feat_out.shape
+        F_, N = min(F, saved[2].shape[1]), log_dur_out.shape[1]
+        d_fo = torch.empty((B, F, C), dtype=feat_out.dtype, device=dev) if need[0] else None
+        d_fp = torch.empty((B, F, C), dtype=feat_out.dtype, device=dev) if feat_post is not None and need[1] else None
+        d_var = [torch.empty((B, N), dtype=feat_out.dtype, device=dev) if need[i] else None for i in (4, 5, 6)]
+        _launch(dev, _lib.load().dsp_tts_loss_bwd, g.data_ptr(), inv.data_ptr(), *ctx.ins, _ptr(d_fo), _ptr(d_fp), _ptr(d_var[0]), _ptr(d_var[1]),
+                _ptr(d_var[2]), _FLOAT_CODES[feat_out.dtype], B, F, F_, C, N)
+        return d_fo, d_fp, None, None, d_var[0], d_var[1], d_var[2], None, None, None, None
+
+
+def tts_losses_checked(feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies,
+                       src_lens):
+    """INTERNAL to the package's criterion: tts_losses_autograd WITHOUT its argument checks, valid only on arguments that tts_losses_served
+    accepted.  The kernels trust what they are handed: any other caller uses tts_losses_autograd."""
+    if audio_lens.dtype != src_lens.dtype:                                  # one width for both length vectors
+        audio_lens, src_lens = audio_lens.to(torch.int64), src_lens.to(torch.int64)
+    args = (feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out, energy_out, durations, pitches, energies, src_lens)
+    if torch.is_grad_enabled() and (feat_out.requires_grad or log_dur_out.requires_grad or pitch_out.requires_grad or energy_out.requires_grad
+                                    or (feat_post is not None and feat_post.requires_grad)):
+        return _TtsLossFn.apply(*args)
+    return _tts_loss_forward(*args)[0]                                      # nothing is saved
+
+
+def tts_losses_autograd(feat_out: Tensor, feat_post: Optional[Tensor], target_audio: Tensor, audio_lens: Tensor, log_dur_out: Tensor,
+                        pitch_out: Tensor, energy_out: Tensor, durations: Tensor, pitches: Tensor, energies: Tensor, src_lens: Tensor) -> Tensor:
+    """The four TTS losses of the released objective as one fp32 tensor [4] = (l1, dur, pitch, energy), differentiable w.r.t. feat_out,
+    feat_post, log_dur_out, pitch_out and energy_out (include/daspeech_decode.h: dsp_tts_loss_fwd / _bwd).  With F_ = min(F, Fa),
+    m_b = min(audio_lens[b], F_), s_b = min(src_lens[b], N), n_mel = C * sum_b m_b, n_src = sum_b s_b:
+        l1     = sum_{b, f<m_b, c} |feat_out - target_audio| / n_mel   (+ the same sum over feat_post when it is given, also / n_mel)
+        dur    = sum_{b, n<s_b} (log_dur_out - log(durations + 1))^2 / n_src;   pitch, energy: the same on (pitch_out, pitches), (energy_out, energies)
+    — what the criterion's masks, boolean selections, F.l1_loss and F.mse_loss compute, with the masks taken from the lengths on the device:
+    no mask tensor, no selection, NO HOST READ of device data in forward or backward.  feat_out [B,F,C], feat_post None or like it,
+    target_audio [B,Fa,C] in fp32 / fp16 / bf16 (one dtype; float64 is refused, never narrowed) on the GPU, the six [B,N] tensors of one shape
+    (durations int64 / int32), lengths [B] int64 / int32; the targets must not require grad.  The mel tensors are read through their batch and
+    row strides (the [:, :F_] slices never exist; F != Fa needs no copy); a layout the kernels do not take — another column stride, a
+    non-contiguous [B,N] tensor — is copied to a dense tensor, gradients pass through.  All arithmetic is fp32 on the exactly widened inputs
+    and the result is fp32 for every data dtype; an empty selection gives NaN as torch's mean of nothing; non-finite inputs propagate.  The
+    sums run in a fixed order without float atomics: forward and backward are bit-reproducible.  Gradients are dense, every element written
+    (exact zeros beyond the lengths), rounded once to the data dtype; sign(0) = sign(NaN) = 0 in the L1 gradient as in torch.  Saved for the
+    backward: the inputs and two reciprocals; under torch.no_grad(), or when no input requires grad, nothing.  Raises RuntimeError on what is
+    not served."""
+    args = _settled("tts_losses_autograd", _tts_loss_problem, (feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out,
+                                                               energy_out, durations, pitches, energies, src_lens), 11)
+    return tts_losses_checked(*args)
 
 
 class SplitConv1d:

@@ -345,6 +345,54 @@ int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_h, const vo
                               uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes, int act_dtype,
                               int param_dtype, int64_t R, int Cin, dsp_stream_t stream);
 
+/* The four TTS losses of the training objective under autograd (csrc/tts_loss_train.hip), the masks taken from the lengths: no mask tensor,
+ * no selection, no host read.  feat_out [B,F,C], feat_post (NULL, or shaped like feat_out) and target [B,Fa,C] are given as a base pointer,
+ * a batch stride and a row stride in elements (>= 0; unit column stride), so that the rows f < F_ = min(F, Fa) are read in place; the six
+ * [B,N] tensors (log_dur_out, pitch_out, energy_out, pitches, energies in the data dtype; durations int64 with dur64 != 0, else int32) are
+ * contiguous; audio_lens and src_lens are [B], int64 with len64 != 0, else int32.  With m_b = min(max(audio_lens[b], 0), F_),
+ * s_b = min(max(src_lens[b], 0), N), n_mel = C * sum_b m_b and n_src = sum_b s_b (integers):
+ *     losses[0] = l1     = sum_{b, f < m_b, c} |feat_out[b,f,c] - target[b,f,c]| / n_mel  (+ the same sum over feat_post, also / n_mel)
+ *     losses[1] = dur    = sum_{b, n < s_b} (log_dur_out[b,n] - log(durations[b,n] + 1))^2 / n_src
+ *     losses[2] = pitch  = sum_{b, n < s_b} (pitch_out[b,n]  - pitches[b,n])^2 / n_src
+ *     losses[3] = energy = sum_{b, n < s_b} (energy_out[b,n] - energies[b,n])^2 / n_src
+ *   Data is DSP_F32 / DSP_F16 / DSP_BF16 (one code for all floating tensors); everything is computed in fp32 on the exactly widened inputs —
+ *   the difference, the log, the squares — and the four results are fp32.  Rows at or beyond a length are never read.  An empty selection
+ *   gives 0 / 0 = NaN; non-finite inputs propagate.  inv_counts[0] = 1 / n_mel, inv_counts[1] = 1 / n_src (fp32) is what the backward keeps.
+ *   forward, two launches.  The rows (b, f) of the [B,F_] grid, in that order, are cut into chunks of DSP_TTSLOSS_CHUNK_ROWS rows, the B*N
+ *   elements of the [B,N] grid into chunks of DSP_TTSLOSS_CHUNK_ELEMS; one wave owns a chunk: lane l adds the valid terms of its elements in
+ *   ascending order (16-byte form: the groups l, l + 64, ... of the chunk's rows * C / V groups, V = 4 or 8 elements, each group element by
+ *   element; scalar form: the elements l, l + 64, ...), the 64 lanes fold by xor butterfly, and the chunk's fp32 partials go to slot `chunk` of
+ *   the workspace — [l1 | post | dur | pitch | energy] — with plain stores.  The chunk -> slot mapping follows from the shapes alone, not from
+ *   the lengths, the grid or the schedule.  The tail (one workgroup of 256) adds each array's slots t, t + 256, ... in ascending order in
+ *   thread t, folds each wave, adds the four waves in order, forms n_mel and n_src from the lengths and divides once.  NO FLOAT ATOMICS, no
+ *   hand-off between workgroups inside a launch, and the workspace is never assumed to be zero: the same inputs give the same bits.
+ *   backward, one launch, from grad_losses (fp32 [4], device) and inv_counts with the forward's inputs; the differences are recomputed:
+ *     d_feat_out = d_feat_post = grad[0] * sign(a - b) / n_mel   (sign(0) = sign(NaN) = 0);   d_x = grad[i] * 2 (a - b) / n_src  for the
+ *   three [B,N] predictions, each value rounded once to the data dtype.  d_feat_out and d_feat_post are contiguous [B,F,C], d_log_dur, d_pitch
+ *   and d_energy contiguous [B,N]; EVERY ELEMENT of every gradient given IS WRITTEN — rows at or beyond m_b / s_b and rows F_ .. F-1 get exact
+ *   zeros.  Targets get no gradient.  Every gradient pointer may be NULL without changing the bits of the others (d_feat_post needs feat_post).
+ *   16-byte accesses per lane are used where C is a multiple of the elements in 16 bytes and every mel pointer and stride is on that grid,
+ *   a scalar path otherwise; pointers need the alignment of their element type only.
+ *   workspace (forward): dsp_tts_loss_workspace_bytes(B, F_, N) bytes, 16-byte aligned (DSP_ENOSPC if smaller) — host arithmetic only, 0 for
+ *   an empty problem, monotone in each argument, a multiple of 16.
+ *   Bad sizes (B < 0, F_ < 1, F_ > F, C < 1, N < 1, B*F*C or B*N above DSP_TTSLOSS_MAX_ELEMS), an unknown dtype, a negative stride, a null
+ *   pointer other than feat_post and the gradients, a pointer off the grid of its element type, an output that aliases an input or another
+ *   output: DSP_EINVAL (dsp_last_error says which) before any launch.  B == 0, or a backward with every gradient NULL: DSP_OK without a
+ *   launch (nothing is written). */
+#define DSP_TTSLOSS_CHUNK_ROWS 32
+#define DSP_TTSLOSS_CHUNK_ELEMS 1024
+#define DSP_TTSLOSS_MAX_ELEMS (1L << 30)
+size_t dsp_tts_loss_workspace_bytes(int B, int F_, int N);
+int dsp_tts_loss_fwd(const void* feat_out, long fo_sb, long fo_sr, const void* feat_post, long fp_sb, long fp_sr, const void* target, long tg_sb,
+                     long tg_sr, const void* audio_lens, const void* log_dur_out, const void* pitch_out, const void* energy_out,
+                     const void* durations, const void* pitches, const void* energies, const void* src_lens, int len64, int dur64, float* losses,
+                     float* inv_counts, void* workspace, size_t workspace_bytes, int dtype, int B, int F_, int C, int N, dsp_stream_t stream);
+int dsp_tts_loss_bwd(const float* grad_losses, const float* inv_counts, const void* feat_out, long fo_sb, long fo_sr, const void* feat_post,
+                     long fp_sb, long fp_sr, const void* target, long tg_sb, long tg_sr, const void* audio_lens, const void* log_dur_out,
+                     const void* pitch_out, const void* energy_out, const void* durations, const void* pitches, const void* energies,
+                     const void* src_lens, int len64, int dur64, void* d_feat_out, void* d_feat_post, void* d_log_dur, void* d_pitch,
+                     void* d_energy, int dtype, int B, int F, int F_, int C, int N, dsp_stream_t stream);
+
 /* Conformer relative-position self-attention under autograd (csrc/relpos_attention_train.hip), fp16 / bf16 data, head width 64:
  *     s(b,h,i,j) = ((q_i + u_h).k_j + (q_i + v_h).pos[T-1-i+j]) / 8,  keys with pad_mask[b,j] != 0: -inf
  *     P = softmax_j(s);  lse(b,h,i) = log sum_j exp s;  A = keep ? P * keep_scale : 0;  out_i = sum_j A_ij v_j
