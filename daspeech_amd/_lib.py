@@ -130,6 +130,16 @@ SIGNATURES = {
                                            _c_int, _c_int, _c_i64, _c_int, _c_p]),
     "dsp_act_dropout_train_bwd": (_c_int, [_c_p, _c_p, ctypes.c_long, _c_p, _c_int, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
                                            _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_i64, _c_int, _c_p]),
+    "dsp_embed_entry_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64,
+                                     ctypes.c_uint64, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_embed_entry_bwd_workspace_bytes": (_c_sz, [_c_i64, _c_int, _c_int, _c_int, ctypes.c_uint]),
+    "dsp_embed_entry_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
+                                     _c_p, _c_p, _c_p, _c_sz, _c_int, _c_i64, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_pos_add_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_int, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64,
+                                 _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "dsp_pos_add_bwd_workspace_bytes": (_c_sz, [_c_i64]),
+    "dsp_pos_add_bwd": (_c_int, [_c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64, ctypes.c_uint64, _c_p, _c_p, _c_p, _c_sz,
+                                 _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_p]),
     "dsp_tts_loss_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
     "dsp_tts_loss_fwd": (_c_int, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long] +
                          [_c_p] * 8 + [_c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),

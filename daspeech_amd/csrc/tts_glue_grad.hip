@@ -6,55 +6,10 @@
 //
 // All of it is HBM-/latency-bound row traffic: 16-byte accesses per lane when the rows and pointers allow it, a scalar path otherwise.
 #include "common.h"
+#include "embed_rows.h"          // wave_sum_rows, embed_chunk_sum_kernel, chunk_range: shared with embed_entry_train.hip
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
-
-constexpr int EG_CHUNK = DSP_EMBED_GRAD_CHUNK;        // rows of one bucket that one wave sums
-constexpr int GG_MAX_WG = 1024;                       // 4 waves each: a launch serves at most 4096 rows per trip of its grid-stride loop
-
-static inline bool aligned16(const void* a, const void* b, size_t row_a, size_t row_b)
-{
-    return (((uintptr_t)a | (uintptr_t)b | row_a | row_b) & 15) == 0;
-}
-
-// dst[0..C) = sum over i in [0, m) of src[row(i), 0..C) — one wave, list order, fp32 accumulation, one rounding to TO; m == 0 writes zeros.
-// Four rows are in flight at a time; the adds stay in list order.
-template <typename TI, typename TO, typename RowFn>
-__device__ __forceinline__ void wave_sum_rows(const TI* __restrict__ src, TO* __restrict__ dst, int C, bool vec, int lane, long m, RowFn row)
-{
-    constexpr int V = 16 / (int)(sizeof(TI) < sizeof(TO) ? sizeof(TI) : sizeof(TO));
-    if (vec) {
-        for (int c = lane * V; c < C; c += 64 * V) {
-            float acc[V];
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc[j] = 0.f;
-            long i = 0;
-            for (; i + 4 <= m; i += 4) {
-                float f0[V], f1[V], f2[V], f3[V];
-                load_f<TI, V>(src + row(i) * C + c, f0);
-                load_f<TI, V>(src + row(i + 1) * C + c, f1);
-                load_f<TI, V>(src + row(i + 2) * C + c, f2);
-                load_f<TI, V>(src + row(i + 3) * C + c, f3);
-#pragma unroll
-                for (int j = 0; j < V; ++j) acc[j] = (((acc[j] + f0[j]) + f1[j]) + f2[j]) + f3[j];
-            }
-            for (; i < m; ++i) {
-                float f0[V];
-                load_f<TI, V>(src + row(i) * C + c, f0);
-#pragma unroll
-                for (int j = 0; j < V; ++j) acc[j] += f0[j];
-            }
-            store_f<TO, V>(dst + c, acc);
-        }
-    } else {
-        for (int c = lane; c < C; c += 64) {
-            float acc = 0.f;
-            for (long i = 0; i < m; ++i) acc += to_f(src[row(i) * C + c]);
-            dst[c] = from_f<TO>(acc);
-        }
-    }
-}
 
 // ---------------------------------------------------------------- F6b': out = x + emb[bucketize(v)], idx kept; one wave per row
 template <typename T>
@@ -124,27 +79,7 @@ __global__ __launch_bounds__(256) void embed_index_kernel(const int32_t* __restr
     }
 }
 
-// step 3: one wave per chunk of EG_CHUNK list entries: partial[w,:] = sum of the chunk's gradient rows in list order (fp32)
-template <typename T>
-__global__ __launch_bounds__(256) void embed_chunk_sum_kernel(const T* __restrict__ g, const int32_t* __restrict__ counts,
-                                                              const int32_t* __restrict__ offs, const int32_t* __restrict__ cstart,
-                                                              const int32_t* __restrict__ perm, float* __restrict__ partial,
-                                                              int K, int C, long max_chunks, bool vec)
-{
-    const int lane = threadIdx.x & 63;
-    long total = cstart[K];
-    if (total > max_chunks) total = max_chunks;             // cannot happen (sum of ceil(count / chunk) <= n / chunk + K); keeps the writes in
-    for (long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6); w < total; w += (long)gridDim.x * 4) {
-        int lo = 0, hi = K - 1;                             // the last bucket whose first chunk is <= w: the one that owns chunk w
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (cstart[mid] <= w) lo = mid; else hi = mid - 1; }
-        const int j = (int)(w - cstart[lo]);
-        const int base = offs[lo] + j * EG_CHUNK;
-        int m = counts[lo] - j * EG_CHUNK;
-        m = m < 0 ? 0 : (m > EG_CHUNK ? EG_CHUNK : m);
-        const int32_t* list = perm + base;
-        wave_sum_rows<T, float>(g, partial + (size_t)w * C, C, vec, lane, m, [&](long i) { return (size_t)list[i]; });
-    }
-}
+// step 3: embed_chunk_sum_kernel (embed_rows.h): one wave per chunk of EG_CHUNK list entries, partial[w,:] = the chunk's rows in list order
 
 // step 4: one wave per bucket: its chunk sums in chunk order, one rounding to the table's dtype; no rows: zeros
 template <typename T>
@@ -153,9 +88,8 @@ __global__ __launch_bounds__(256) void embed_reduce_kernel(const float* __restri
 {
     const int lane = threadIdx.x & 63;
     for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < K; k += gridDim.x * 4) {
-        long c0 = cstart[k], c1 = cstart[k + 1];
-        if (c1 > max_chunks) c1 = max_chunks;
-        if (c0 > c1) c0 = c1;
+        long c0, c1;
+        chunk_range(cstart, k, max_chunks, c0, c1);
         wave_sum_rows<float, T>(partial, out + (size_t)k * C, C, vec, lane, c1 - c0, [&](long i) { return (size_t)(c0 + i); });
     }
 }
@@ -176,7 +110,6 @@ __global__ __launch_bounds__(256) void lr_bwd_kernel(const T* __restrict__ g, co
     }
 }
 
-static unsigned wave_grid(long waves) { const long g = (waves + 3) / 4; return (unsigned)(g < 1 ? 1 : (g > GG_MAX_WG ? GG_MAX_WG : g)); }
 static size_t eg_int_bytes(int64_t n, int K) { return (((size_t)3 * K + 1 + (size_t)n) * sizeof(int32_t) + 15) & ~(size_t)15; }
 static long eg_max_chunks(int64_t n, int K) { return (long)((n + EG_CHUNK - 1) / EG_CHUNK) + K; }
 

@@ -64,6 +64,18 @@ Host-side mirror of the reference code these replace:
                       the mel tensors read through their strides (no [:, :F_] slice), sums in a fixed order without float atomics, a backward of
                       one launch that recomputes the differences and writes dense gradients; S2SDAGFastSpeech2Loss keeps its torch lines
                       where tts_losses_served says no (set_tts_loss_hip(False): always); tts_losses_checked is internal to that criterion
+  embed_entry_autograd   DASpeech/models (fairseq nonautoregressive_transformer.py:340-349) — the entry of DAGDecoder.extract_features,
+                      dropout(embed_scale * embed_tokens(tokens) + embed_positions(positions(tokens))), as one launch under autograd
+                      (csrc/embed_entry_train.hip): fp32 / fp16 / bf16 tables, positions from a cumulative count (left padding, interior
+                      pads, all-pad rows), the mask on the shared Philox rule, and a backward that builds ONE inverted index for both table
+                      gradients (integer atomic counts, a scan, sorted or ballot-compacted lists) and adds a table row's gradient rows in
+                      ascending order in fp32 without float atomics; DAGDecoder keeps its torch lines where embed_entry_served says no
+                      (set_embed_entry_hip(False): always); embed_entry_checked is internal to that layer
+  positional_add_dropout_autograd   fastspeech2_noemb.py:150-151,166 — dropout(x + alpha * pos_table[positions(mask)]) of FastSpeech2NoEmb, one
+                      launch under autograd (csrc/embed_entry_train.hip): row-pitched x, the table in the data dtype or fp32, dx = dy * mask
+                      (dy itself without dropout) and the gradient of the one-element alpha as a fixed-order two-stage sum; the model keeps
+                      its torch lines where positional_add_dropout_served says no (the same switch); positional_add_dropout_checked is
+                      internal to that model
 No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
@@ -1578,6 +1590,250 @@ def bias_act_dropout_autograd(h: Tensor, bias: Optional[Tensor], act: str, p: fl
     in a fixed order without float atomics: forward and backward are bit-reproducible.  Raises RuntimeError on what is not served."""
     h, bias, act = _settled("bias_act_dropout_autograd", _actdrop_problem, (h, bias, act), 1, p)
     return bias_act_dropout_checked(h, _dense16(bias), act, p, training)
+
+
+# ------------------------------------------------------------------------------------------------ decoder and TTS input embeddings under autograd (csrc/embed_entry_train.hip)
+EMBED_ENTRY_HIP = True       # set_embed_entry_hip(False): DAGDecoder.extract_features and FastSpeech2NoEmb.forward keep their torch lines
+EMBED_ENTRY_MAX_C = 2048     # DSP_EMBED_ENTRY_MAX_C
+EMBED_ENTRY_SORT_MAX = 64    # DSP_EMBED_ENTRY_SORT_MAX: a key with more rows than this takes the ballot compaction, else the sorted fill
+POS_ADD_CHUNK_ROWS = 32      # DSP_POS_ADD_CHUNK_ROWS: rows per fp32 partial of dalpha
+
+
+def set_embed_entry_hip(on: bool) -> bool:
+    """Switch the HIP embedding-entry operators of the training branches (DAGDecoder.extract_features, FastSpeech2NoEmb.forward) on or off;
+    returns the previous setting.  Off: embed_entry_served and positional_add_dropout_served answer False and the torch lines run."""
+    global EMBED_ENTRY_HIP
+    old, EMBED_ENTRY_HIP = EMBED_ENTRY_HIP, bool(on)
+    return old
+
+
+def _entry_width_ok(C: int, itemsize: int) -> bool:
+    V = 16 // itemsize
+    return V <= C <= EMBED_ENTRY_MAX_C and C % V == 0
+
+
+def _embed_entry_problem(tokens, E, P, pad) -> Optional[str]:
+    """None when dsp_embed_entry_fwd / _bwd take these tensors (tokens through its row stride or a contiguous copy), else what is in the way
+    (tables that a dense copy settles: the reason begins with _LAYOUT)"""
+    if not (isinstance(tokens, Tensor) and tokens.dim() == 2 and tokens.dtype == torch.int64):
+        return "tokens has to be a [B, L] int64 tensor"
+    if not (isinstance(E, Tensor) and isinstance(P, Tensor) and E.dim() == 2 and P.dim() == 2 and E.shape[1] == P.shape[1]):
+        return "the token table [V, C] and the position table [NP, C] have to be matrices of one width"
+    if E.dtype not in _FLOAT_CODES or P.dtype != E.dtype:
+        return f"both tables have to be in one of fp32 / fp16 / bf16, got {E.dtype} and {P.dtype} (float64 is refused, never narrowed)"
+    (B, L), C, NP = tokens.shape, E.shape[1], P.shape[0]
+    if not (_entry_width_ok(C, E.element_size()) and E.shape[0] >= 1 and 0 <= pad < NP and L + pad + 1 <= NP and B * L <= (1 << 24)):
+        return (f"tokens {tuple(tokens.shape)} / tables {tuple(E.shape)}, {tuple(P.shape)} / pad {pad} are not served (C a multiple of "
+                f"{16 // E.element_size()} elements, C <= {EMBED_ENTRY_MAX_C}, L + pad + 1 <= NP, B * L <= 2^24)")
+    why = _gpu_problem(tokens, E, P)
+    if why is not None:
+        return why
+    if not (tokens.device == E.device == P.device):
+        return "tokens and both tables have to be on one device"
+    if not _as_handed_over(E, P):
+        return _LAYOUT + ": the tables have to be contiguous and start on a 16-byte boundary"
+    return None
+
+
+def embed_entry_served(tokens: Tensor, embed_tokens: "torch.nn.Embedding", embed_positions: "torch.nn.Embedding") -> bool:
+    """True when embed_entry_autograd serves a training branch on these arguments as they are: the switch is on, autocast off, tokens a GPU
+    int64 tensor [B, L], both nn.Embedding weights on that device in one of fp32 / fp16 / bf16, contiguous and on the 16-byte grid (a view
+    into a flat parameter buffer at an odd offset is NOT served: the torch lines run), one padding_idx, C a multiple of the elements in 16
+    bytes and at most 2048, L + pad + 1 <= NP, B * L <= 2^24, and the current stream not capturing a graph (the random offset is reserved on
+    the host).  Everything else keeps the torch lines."""
+    if not EMBED_ENTRY_HIP or torch.is_autocast_enabled():
+        return False
+    pad = embed_tokens.padding_idx
+    if pad is None or embed_positions.padding_idx != pad:
+        return False
+    if _embed_entry_problem(tokens, embed_tokens.weight, embed_positions.weight, pad) is not None:
+        return False
+    return not _capturing()
+
+
+class _EmbedEntryFn(torch.autograd.Function):
+    """dsp_embed_entry_fwd / _bwd.  Saved for the backward: tok32 and pos32 (int32 [B*L]) — no mask, no y."""
+
+    @staticmethod
+    def forward(ctx, tokens, E, P, pad, embed_scale, ld, p, seed, offset):
+        B, L = tokens.shape
+        V, C = E.shape
+        NP = P.shape[0]
+        thr, scale = _dropout_thr_scale(p)
+        lib = _lib.load()
+        dev = E.device
+        y = torch.empty((B, L, C), dtype=E.dtype, device=dev)
+        idx = torch.empty((2, B * L), dtype=torch.int32, device=dev)
+        if B * L:
+            _launch(dev, lib.dsp_embed_entry_fwd, tokens.data_ptr(), ld, E.data_ptr(), P.data_ptr(), pad, embed_scale, scale, thr, seed, offset,
+                    y.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), _FLOAT_CODES[E.dtype], B, L, V, NP, C)
+        ctx.save_for_backward(idx)
+        ctx.call = (pad, embed_scale, scale, thr, seed, offset, V, NP, C, E.dtype)
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        pad, embed_scale, scale, thr, seed, offset, V, NP, C, dt = ctx.call
+        need = ctx.needs_input_grad
+        if dy is None or not (need[1] or need[2]):
+            return (None,) * 9
+        if not dy.is_contiguous() or dy.data_ptr() % 16:                    # a broadcast, a transpose, a narrow at an odd offset
+            dy = _dense16(dy)
+        n = idx.shape[1]
+        lib = _lib.load()
+        dev = idx.device
+        dE = torch.empty((V, C), dtype=dt, device=dev) if need[1] else None
+        dP = torch.empty((NP, C), dtype=dt, device=dev) if need[2] else None
+        nbytes = int(lib.dsp_embed_entry_bwd_workspace_bytes(n, V, NP, C, thr))
+        ws = _workspace(dev, nbytes)
+        _launch(dev, lib.dsp_embed_entry_bwd, dy.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), pad, embed_scale, scale, thr, seed, offset,
+                _ptr(dE), _ptr(dP), _ptr(ws), nbytes, _FLOAT_CODES[dt], n, V, NP, C)
+        return None, dE, dP, None, None, None, None, None, None
+
+
+def embed_entry_checked(tokens, E, P, pad, embed_scale, p=0.0, training=True):
+    """INTERNAL to the package's layers: embed_entry_autograd WITHOUT its argument checks, valid only on arguments that embed_entry_served
+    accepted.  The kernels trust what they are handed: any other caller uses embed_entry_autograd."""
+    B, L = tokens.shape
+    if (L > 1 and tokens.stride(1) != 1) or (B > 1 and tokens.stride(0) < L):      # a transpose, a broadcast: the rows of a column slice are read in place
+        tokens = tokens.contiguous()
+    ld = tokens.stride(0) if B > 1 else L
+    p_eff, seed, offset = _dropout_call(p, training, E.device)
+    return _EmbedEntryFn.apply(tokens, E, P, int(pad), float(embed_scale), ld, p_eff, seed, offset)
+
+
+def embed_entry_autograd(tokens: Tensor, E: Tensor, P: Tensor, pad: int, scale: float, p: float = 0.0, training: bool = True) -> Tensor:
+    """y [B, L, C] = dropout(scale * E[tokens] + P[positions(tokens)], p)  — the entry of DAGDecoder.extract_features (token embedding times
+    embed_scale plus learned positions, fairseq nonautoregressive_transformer.py:340-349), differentiable w.r.t. both tables
+    (include/daspeech_decode.h: dsp_embed_entry_fwd / _bwd).  positions = pad + keep * cumsum(keep) with keep = tokens != pad, so left
+    padding, interior pads and all-pad rows are served; a token outside [0, V) gives a zero embedding row (torch raises there) and still
+    counts as non-pad.  tokens [B, L] int64 on the GPU (a column slice of a wider tensor is read in place); E [V, C] and P [NP, C] in one of
+    fp32 / fp16 / bf16 (float64 is refused, never narrowed) with L + pad + 1 <= NP; tables that are not contiguous or start off the 16-byte
+    grid (views into a flat parameter buffer) are COPIED to dense tensors, gradients pass through.  fp32 arithmetic, one rounding.  The
+    gradients add the rows of a table row in ascending order in fp32 without float atomics, row `pad` of both is zero (padding_idx):
+    forward and backward are bit-reproducible.  Dropout is active with `training and p > 0`; the mask is the one
+    dropout_keep_mask(seed, offset, p, (B * L, C), device) gives for the (seed, offset) the call reserves from the default CUDA generator of
+    the tables' device (its offset moves on by 4; calls with p = 0 or training=False leave the generator alone).  The masks are not torch's
+    F.dropout masks.  Raises RuntimeError on what is not served."""
+    tokens, E, P, pad = _settled("embed_entry_autograd", _embed_entry_problem, (tokens, E, P, pad), 3, p)
+    return embed_entry_checked(tokens, E, P, pad, scale, p, training)
+
+
+def _posadd_problem(x, table, padding_mask, alpha) -> Optional[str]:
+    """None when dsp_pos_add_fwd / _bwd take these tensors as they are, else what is in the way (a layout of x or the table that a dense copy
+    settles begins with _LAYOUT)"""
+    if not (isinstance(x, Tensor) and x.dim() == 3):
+        return "x has to be a [B, N, C] tensor"
+    dt = x.dtype
+    if dt not in _FLOAT_CODES:
+        return f"x has to be fp32, fp16 or bf16, got {dt} (float64 is refused, never narrowed)"
+    B, N, C = x.shape
+    if not (isinstance(padding_mask, Tensor) and padding_mask.shape == (B, N) and padding_mask.dtype in (torch.bool, torch.uint8)):
+        return f"padding_mask has to be a [{B}, {N}] bool tensor"
+    if not (isinstance(table, Tensor) and table.dim() == 2 and table.shape[1] == C and table.shape[0] >= 1 and table.dtype in (dt, torch.float32)
+            and not table.requires_grad):
+        return f"the table has to be [NT, {C}] in the dtype of x or in fp32, without gradient"
+    if not (isinstance(alpha, Tensor) and alpha.numel() == 1 and alpha.dtype in (dt, torch.float32)):
+        return "alpha has to be one element in the dtype of x or in fp32"
+    if not _entry_width_ok(C, x.element_size()) or B * N > (1 << 24) or table.numel() >= (1 << 31):
+        return (f"x {tuple(x.shape)} is not served (C a multiple of {16 // x.element_size()} elements, C <= {EMBED_ENTRY_MAX_C}, "
+                "at most 2^24 rows)")
+    why = _gpu_problem(x, padding_mask, table, alpha)
+    if why is not None:
+        return why
+    if not (x.device == padding_mask.device == table.device == alpha.device):
+        return "x, padding_mask, the table and alpha have to be on one device"
+    ld = _row_pitch(x)
+    if ld is None or ld < C or ld % (16 // x.element_size()) or x.data_ptr() % 16 or not _as_handed_over(table):
+        return _LAYOUT + ": x needs unit column stride, one row pitch on the 16-byte grid and 16-byte alignment, the table a dense aligned start"
+    return None
+
+
+def positional_add_dropout_served(x: Tensor, padding_mask: Tensor, table: Tensor, alpha: Tensor) -> bool:
+    """True when positional_add_dropout_autograd serves a training branch on these arguments as they are: the switch (set_embed_entry_hip)
+    is on, autocast off, x a GPU tensor [B, N, C] in fp32 / fp16 / bf16 with C a multiple of the elements in 16 bytes and at most 2048, unit
+    column stride, rows one common pitch apart and a 16-byte aligned start, padding_mask [B, N] bool, the table [NT, C] contiguous and aligned
+    in that dtype or fp32 without gradient, alpha one element in that dtype or fp32, everything on one device, and the current stream not
+    capturing a graph.  Everything else keeps the torch lines."""
+    if not EMBED_ENTRY_HIP or torch.is_autocast_enabled():
+        return False
+    if _posadd_problem(x, table, padding_mask, alpha) is not None:
+        return False
+    return not _capturing()
+
+
+class _PosAddDropoutFn(torch.autograd.Function):
+    """dsp_pos_add_fwd / _bwd.  Saved for the backward: the table and pos32 — no mask, no y."""
+
+    @staticmethod
+    def forward(ctx, x, mask, table, alpha, ld, p, seed, offset):
+        B, N, C = x.shape
+        NT = table.shape[0]
+        thr, scale = _dropout_thr_scale(p)
+        lib = _lib.load()
+        dev = x.device
+        y = torch.empty((B, N, C), dtype=x.dtype, device=dev)
+        pos = torch.empty((B * N,), dtype=torch.int32, device=dev)
+        codes = (_FLOAT_CODES[x.dtype], _FLOAT_CODES[table.dtype], _FLOAT_CODES[alpha.dtype])
+        if B * N:
+            _launch(dev, lib.dsp_pos_add_fwd, x.data_ptr(), ld, mask.data_ptr(), table.data_ptr(), alpha.data_ptr(), 1, scale, thr, seed, offset,
+                    y.data_ptr(), pos.data_ptr(), codes[0], codes[1], codes[2], B, N, NT, C)
+        ctx.save_for_backward(table, pos)
+        ctx.call = (scale, thr, seed, offset, codes, alpha.shape)
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        table, pos = ctx.saved_tensors
+        scale, thr, seed, offset, codes, ashape = ctx.call
+        need = ctx.needs_input_grad
+        want_dx, want_da = need[0], need[3]
+        if dy is None or not (want_dx or want_da):
+            return (None,) * 8
+        if not (want_da or thr):
+            return dy, None, None, None, None, None, None, None            # dx = dy: no launch
+        if not dy.is_contiguous() or dy.data_ptr() % 16:                    # a broadcast, a transpose, a narrow at an odd offset
+            dy = _dense16(dy)
+        R, C = pos.shape[0], dy.shape[-1]
+        lib = _lib.load()
+        dev = dy.device
+        dx = dy if not thr else (torch.empty(dy.shape, dtype=dy.dtype, device=dev) if want_dx else None)
+        dalpha = torch.empty(ashape, dtype=[torch.float32, torch.float16, torch.bfloat16][codes[2]], device=dev) if want_da else None
+        if R:
+            nbytes = int(lib.dsp_pos_add_bwd_workspace_bytes(R)) if want_da else 0
+            ws = _workspace(dev, nbytes)
+            _launch(dev, lib.dsp_pos_add_bwd, dy.data_ptr(), table.data_ptr(), pos.data_ptr(), scale, thr, seed, offset,
+                    _ptr(dx) if thr else None, _ptr(dalpha), _ptr(ws), nbytes, codes[0], codes[1], codes[2], R, table.shape[0], C)
+        elif dalpha is not None:
+            dalpha.zero_()                                                 # no rows: the empty sum
+        return (dx if want_dx else None), None, None, dalpha, None, None, None, None
+
+
+def positional_add_dropout_checked(x, padding_mask, table, alpha, p=0.0, training=True):
+    """INTERNAL to the package's layers: positional_add_dropout_autograd WITHOUT its argument checks, valid only on arguments that
+    positional_add_dropout_served accepted."""
+    p_eff, seed, offset = _dropout_call(p, training, x.device)
+    return _PosAddDropoutFn.apply(x, _mask_bytes(padding_mask), table, alpha, _row_pitch(x), p_eff, seed, offset)
+
+
+def positional_add_dropout_autograd(x: Tensor, padding_mask: Tensor, table: Tensor, alpha: Tensor, p: float = 0.0,
+                                    training: bool = True) -> Tensor:
+    """y = dropout(x + alpha * table[min(positions_from_padding_mask(padding_mask), NT - 1)], p)  — the two positional sites of
+    FastSpeech2NoEmb.forward (fastspeech2_noemb.py:150-151,166), differentiable w.r.t. x and the one-element alpha
+    (include/daspeech_decode.h: dsp_pos_add_fwd / _bwd).  x [B, N, C] fp32 / fp16 / bf16 on the GPU (float64 is refused, never narrowed),
+    padding_mask [B, N] bool (True: padding), table [NT, C] and alpha in that dtype or fp32, the table without gradient.  A row-pitched view
+    of x is read in place; any other layout (x[:, 1:] of a batch, a transpose, a start off the 16-byte grid) and a table that is a view are
+    copied to dense tensors, gradients pass through.  y has the dtype of x (torch's own lines promote to fp32 when the table is fp32 and x is
+    not).  fp32 arithmetic, one rounding; dalpha is a fixed-order two-stage fp32 sum: forward and backward are bit-reproducible.  Dropout as
+    in embed_entry_autograd, the mask that of dropout_keep_mask(seed, offset, p, (B * N, C), device); without dropout dx is dy itself.
+    Raises RuntimeError on what is not served."""
+    x, table, padding_mask, alpha = _settled("positional_add_dropout_autograd", _posadd_problem, (x, table, padding_mask, alpha), 2, p)
+    return positional_add_dropout_checked(x, padding_mask, table, alpha, p, training)
 
 
 # ------------------------------------------------------------------------------------------------ relative-position attention under autograd (csrc/relpos_attention_train.hip)

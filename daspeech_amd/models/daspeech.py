@@ -470,8 +470,14 @@ class DAGDecoder(nn.Module):
         return None
 
     def extract_features(self, prev_output_tokens: Tensor, enc: Dict[str, Tensor], lens: Optional[Tensor] = None) -> Tensor:
-        x = self.embed_scale * self.embed_tokens(prev_output_tokens) + self.embed_positions(self.positions(prev_output_tokens))
-        x = _drop(x, self.a.dropout, self.training)                                       # nonautoregressive_transformer.py:349
+        if (self.training or torch.is_grad_enabled()) and decode_ops.embed_entry_served(prev_output_tokens, self.embed_tokens, self.embed_positions):
+            # token embedding, learned positions and the embedding dropout as one HIP operator (csrc/embed_entry_train.hip); its backward
+            # builds one inverted index for both tables (nearly every graph vertex is <unk>)
+            x = decode_ops.embed_entry_checked(prev_output_tokens, self.embed_tokens.weight, self.embed_positions.weight, PAD, self.embed_scale,
+                                               self.a.dropout, self.training)
+        else:
+            x = self.embed_scale * self.embed_tokens(prev_output_tokens) + self.embed_positions(self.positions(prev_output_tokens))
+            x = _drop(x, self.a.dropout, self.training)                                   # nonautoregressive_transformer.py:349
         pad = prev_output_tokens.eq(PAD)
         enc_lens = None if lens is None else decode_ops.valid_lengths(enc["encoder_padding_mask"])
         for layer in self.layers:

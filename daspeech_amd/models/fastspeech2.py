@@ -161,6 +161,17 @@ class FFTLayer(nn.Module):
         return self.ffn(x, lens, slack)
 
 
+def _ln_drop(h: Tensor, ln: nn.LayerNorm, p: float, training: bool) -> Tensor:
+    """dropout(ln(h)) of the VariancePredictor's training branch: the LayerNorm through the residual-norm operator without a residual
+    (csrc/residual_norm_train.hip), the dropout through the identity activation of csrc/act_dropout_train.hip — each where its own served
+    rule takes the tensor, else the torch line"""
+    from .. import decode_ops as _dops
+    y = _dops.residual_dropout_layer_norm_checked(None, h, ln) if _dops.residual_dropout_layer_norm_served(None, h, ln) else ln(h)
+    if _dops.bias_act_dropout_served(y, None, "identity"):
+        return _dops.bias_act_dropout_checked(y, None, "identity", p, training)
+    return _drop(y, p, training)
+
+
 class VariancePredictor(nn.Module):
     """Conv1d-ReLU-LN-Conv1d-ReLU-LN-Linear (fastspeech2.py:117-151); dropout is identity at inference."""
 
@@ -194,8 +205,8 @@ class VariancePredictor(nn.Module):
         if (self.training or torch.is_grad_enabled()) and _dops.conv1d_channels_last_sites_served(x, (c1, c2)):
             # both convolutions as HIP operators on the channels-last tensor (csrc/conv1d_train.hip), bias + ReLU behind each; conv2's padding
             # of 1 is (K-1)/2 only with K = 3, which is what the question above asks
-            x = _drop(self.ln1(_conv_bias_relu(x, c1, self.training)), self.p, self.training)
-            x = _drop(self.ln2(_conv_bias_relu(x, c2, self.training)), self.p, self.training)
+            x = _ln_drop(_conv_bias_relu(x, c1, self.training), self.ln1, self.p, self.training)
+            x = _ln_drop(_conv_bias_relu(x, c2, self.training), self.ln2, self.p, self.training)
             return self.proj(x).squeeze(2)
         x = _drop(self.ln1(self.conv1(x.transpose(1, 2)).transpose(1, 2)), self.p, self.training)
         x = _drop(self.ln2(self.conv2(x.transpose(1, 2)).transpose(1, 2)), self.p, self.training)
@@ -354,13 +365,23 @@ class FastSpeech2NoEmb(nn.Module):
             z = x.new_zeros(x.shape[0], 0)
             mel0 = x.new_zeros(x.shape[0], 0, self.args.out_dim)
             return mel0, (mel0 if self.postnet is not None else None), x.new_zeros(x.shape[0], dtype=torch.long), z, z, z
-        x = _drop(x + self.pos_emb_alpha * self._pos(padding_mask), self.args.dropout, self.training)       # fastspeech2_noemb.py:150-151
+        from .. import decode_ops as _dops
+        # both positional sites as HIP operators (csrc/embed_entry_train.hip) where served; a table or alpha in another dtype than x keeps the
+        # torch lines, whose result is then promoted
+        hip_pos = (self.training or torch.is_grad_enabled()) and self.pos_table.dtype == x.dtype == self.pos_emb_alpha.dtype
+        if hip_pos and _dops.positional_add_dropout_served(x, padding_mask, self.pos_table, self.pos_emb_alpha):
+            x = _dops.positional_add_dropout_checked(x, padding_mask, self.pos_table, self.pos_emb_alpha, self.args.dropout, self.training)
+        else:
+            x = _drop(x + self.pos_emb_alpha * self._pos(padding_mask), self.args.dropout, self.training)   # fastspeech2_noemb.py:150-151
         for layer in self.encoder_fft_layers:
             x = layer(x, padding_mask)
         x, out_lens, log_dur, pitch, energy = self.var_adaptor(x, padding_mask, durations, pitches, energies)
         F_ = x.shape[1]
         dec_mask = torch.arange(F_, device=x.device).unsqueeze(0) >= out_lens.unsqueeze(1)
-        x = x + self.dec_pos_emb_alpha * self._pos(dec_mask)
+        if hip_pos and x.dtype == self.dec_pos_emb_alpha.dtype and _dops.positional_add_dropout_served(x, dec_mask, self.pos_table, self.dec_pos_emb_alpha):
+            x = _dops.positional_add_dropout_checked(x, dec_mask, self.pos_table, self.dec_pos_emb_alpha)
+        else:
+            x = x + self.dec_pos_emb_alpha * self._pos(dec_mask)
         # Ragged batch: the reference computes every padded frame (fastspeech2.py:86-98 masks attention keys only, the two K=9 convolutions
         # of an FFT layer read 8 frames past an utterance's end), so a valid frame depends on padding frames up to 8 per remaining layer
         # (+ the postnet's 5 x 2).  Frames beyond that bound influence nothing valid: their tiles are skipped (zeros).  Valid frames keep

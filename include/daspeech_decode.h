@@ -345,6 +345,65 @@ int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_h, const vo
                               uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes, int act_dtype,
                               int param_dtype, int64_t R, int Cin, dsp_stream_t stream);
 
+/* The input embeddings of the decoder and of the TTS half under autograd (csrc/embed_entry_train.hip).  Both operators take the positions
+ * from a cumulative count of the kept elements of a sample's row — correct for left padding, interior pads and all-pad rows —, compute in fp32,
+ * round once, and apply the dropout mask of dsp_resnorm_train_fwd's rule (above) on the element index e = r*C + c of the contiguous output
+ * (dsp_dropout_keep_mask over n*C elements, read as [n,C], is the mask applied; thr == 0: no mask path at all, keep_scale is not read).
+ *
+ *   dsp_embed_entry_fwd: tokens [B,L] int64 with unit column stride and ld_tok elements between rows (8-byte aligned); E [V,C] and P [NP,C]
+ *     in one dtype code, which is also y's.  keep = tokens != pad;  pos[b,t] = pad + keep * #{ t' <= t : tokens[b,t'] != pad }
+ *     (DAGDecoder.positions);  y[b,t,:] = m * (embed_scale * E[tok] + P[pos]), y [B*L,C] contiguous.  Row `pad` of either table is read as it
+ *     is stored.  A token outside [0, V) contributes a zero embedding row and still counts as non-pad; nothing outside a table is read (the
+ *     caller keeps L + pad + 1 <= NP; a larger position would be clamped to NP - 1).  Outputs for the backward: tok32 [B*L] int32 (-1 for a
+ *     token outside [0, V)) and pos32 [B*L] int32.  One launch.
+ *
+ *   dsp_embed_entry_bwd: with g = dy * m (dy [n,C] contiguous, n = B*L):
+ *       dE[v,:] = embed_scale * sum over the rows r with tok32[r] == v of g[r,:]        dP[q,:] = sum over the rows r with pos32[r] == q of g[r,:]
+ *     rows added in ASCENDING r in fp32, embed_scale applied in fp32, ONE rounding.  Every row of dE [V,C] and dP [NP,C] is written; row `pad`
+ *     of both (padding_idx), rows without a source and the share of out-of-range tokens are exact zeros.  Either of dE / dP may be NULL, and
+ *     one alone has the bits it has next to the other; both NULL: DSP_OK without a launch.  g is written once as fp32 [n,C] into the workspace
+ *     when thr != 0 (with thr == 0 the sums read dy).  Both gradients come from ONE inverted index over 2n list entries and V + NP keys:
+ *     integer atomic counts, one exclusive scan, then per key — at most DSP_EMBED_ENTRY_SORT_MAX rows: slots taken in any order and the list
+ *     sorted ascending by the key's wave; more rows: a workgroup writes the list by ballot compaction over all entries (at most 2n / 65 such
+ *     keys exist) — and the chunk sums (DSP_EMBED_GRAD_CHUNK rows a chunk) and per-key reduce that dsp_embed_grad uses.  The cost does not grow
+ *     as V * n / 64.  NO FLOAT ATOMICS and no hand-off between workgroups: the same inputs give the same bits on every call.
+ *     workspace: dsp_embed_entry_bwd_workspace_bytes(n, V, NP, C, thr) bytes of device memory, 16-byte aligned (DSP_ENOSPC if smaller), may
+ *     hold anything on entry; host arithmetic only, 0 for an empty problem, a multiple of 16.
+ *
+ *   dsp_pos_add_fwd: x [B,N,C] read as B*N rows of unit column stride ld_x elements apart (>= C, a multiple of the elements in 16 bytes),
+ *     padding_mask [B,N] bytes (non-zero: padding), tab [NT,C] in the data dtype or fp32, alpha ONE element on the device in the data dtype
+ *     or fp32.  keep = !mask;  pos = min(pad + keep * cumsum(keep), NT - 1) (positions_from_padding_mask, then the clamp);
+ *     y = m * (x + alpha * tab[pos]), y [B*N,C] contiguous; pos32 [B*N] int32 is kept for the backward.  One launch.
+ *
+ *   dsp_pos_add_bwd: dx = dy * m (dx NULL: not computed — with thr == 0 it is dy itself and the caller hands dy on; a non-NULL dx with
+ *     thr == 0 gets a copy), dalpha = sum over rows and columns of g * tab[pos] with g = dy * m: one wave per chunk of DSP_POS_ADD_CHUNK_ROWS
+ *     rows writes a partial (a lane adds its columns over the rows in row order, then a butterfly over the lanes), a one-workgroup tail
+ *     adds the partials in index order and rounds once to alpha's dtype.  The lanes and the tail accumulate in double and a partial is
+ *     stored as two fp32 values (head, tail): dalpha is one number out of R*C products of either sign, and fp32 accumulators would leave it
+ *     with an ulp of partial sums far larger than the result.  dalpha NULL: skipped (tab and pos32 are then not read).
+ *     workspace (needed for dalpha only): dsp_pos_add_bwd_workspace_bytes(R) bytes, 16-byte aligned, may hold anything on entry.
+ *
+ *   All four: fp32 / fp16 / bf16, C a multiple of the elements in 16 bytes (4 or 8), C <= DSP_EMBED_ENTRY_MAX_C, at most 2^24 rows, tables,
+ *   data tensors and gradients 16-byte aligned.  EVERY OUTPUT ELEMENT IS WRITTEN.  Bad sizes, null or aliased pointers, misalignment:
+ *   DSP_EINVAL before any launch; no rows: DSP_OK (the gradients of the tables / of alpha are then zeros). */
+#define DSP_EMBED_ENTRY_MAX_C 2048
+#define DSP_EMBED_ENTRY_SORT_MAX 64
+#define DSP_POS_ADD_CHUNK_ROWS 32
+int dsp_embed_entry_fwd(const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale, float keep_scale,
+                        unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* tok32, int32_t* pos32, int dtype, int B, int L, int V,
+                        int NP, int C, dsp_stream_t stream);
+size_t dsp_embed_entry_bwd_workspace_bytes(int64_t n, int V, int NP, int C, unsigned int thr);
+int dsp_embed_entry_bwd(const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
+                        unsigned int thr, uint64_t seed, uint64_t offset, void* dE, void* dP, void* workspace, size_t workspace_bytes, int dtype,
+                        int64_t n, int V, int NP, int C, dsp_stream_t stream);
+int dsp_pos_add_fwd(const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad, float keep_scale,
+                    unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* pos32, int act_dtype, int tab_dtype, int alpha_dtype, int B,
+                    int N, int NT, int C, dsp_stream_t stream);
+size_t dsp_pos_add_bwd_workspace_bytes(int64_t R);
+int dsp_pos_add_bwd(const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset,
+                    void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype, int tab_dtype, int alpha_dtype, int64_t R, int NT,
+                    int C, dsp_stream_t stream);
+
 /* The four TTS losses of the training objective under autograd (csrc/tts_loss_train.hip), the masks taken from the lengths: no mask tensor,
  * no selection, no host read.  feat_out [B,F,C], feat_post (NULL, or shaped like feat_out) and target [B,Fa,C] are given as a base pointer,
  * a batch stride and a row stride in elements (>= 0; unit column stride), so that the rows f < F_ = min(F, Fa) are read in place; the six
