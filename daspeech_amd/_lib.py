@@ -145,6 +145,10 @@ SIGNATURES = {
                          [_c_p] * 8 + [_c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "dsp_tts_loss_bwd": (_c_int, [_c_p, _c_p, _c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long,
                                   ctypes.c_long] + [_c_p] * 8 + [_c_int, _c_int] + [_c_p] * 5 + [_c_int] * 6 + [_c_p]),
+    "dsp_path_features_fwd": (_c_int, [_c_p, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_int,
+                                       _c_int, _c_int, _c_int, _c_p]),
+    "dsp_path_features_bwd": (_c_int, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long, _c_int, _c_int, _c_p, _c_int, _c_int,
+                                       _c_int, _c_int, _c_int, _c_p]),
     "dsp_relpos_attention_train_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
     "dsp_relpos_attention_train_fwd": (_c_int, [_c_p, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, ctypes.c_float, ctypes.c_uint, ctypes.c_uint64,
                                                 ctypes.c_uint64, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),

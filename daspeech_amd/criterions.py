@@ -257,7 +257,11 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
     The l1 / duration / pitch / energy losses come from decode_ops.tts_losses_checked (one HIP operator under autograd, the masks taken from the
     lengths on the device) where decode_ops.tts_losses_served accepts the tensors, from the reference's torch lines otherwise (CPU tensors,
     float64, autocast, decode_ops.set_tts_loss_hip(False)).  The operator's losses are fp32 whatever the model's dtype: with an fp16 model
-    the four losses, tts-loss and loss are then fp32 tensors, where the torch lines give fp16."""
+    the four losses, tts-loss and loss are then fp32 tensors, where the torch lines give fp16.
+
+    The argmax strategy's features_on_path and its padding mask come from decode_ops.path_features_checked (one HIP launch each way, the
+    width tgt_tokens.shape[1] - 1 a host integer: no argsort, no host read) where decode_ops.path_features_served accepts the tensors, from
+    the reference's torch lines otherwise (CPU tensors, float64, autocast, decode_ops.set_path_features_hip(False)), with the same bits."""
 
     def _lazy_softmax(self) -> bool:
         # argmax strategy, reference GPU behaviour: the gather must really overwrite the logits with their soft-max, because the
@@ -303,14 +307,23 @@ class S2SDAGFastSpeech2Loss(NATDAGLoss):
                     path = custom_ops.torch_dag_best_alignment(match.clone(), decode_ops.restore_valid_links(links_d), output_length, target_length)
                 else:
                     path = custom_ops.dag_best_alignment(match, links_d, output_length, target_length)
-                path = path.clone()
-                path[:, 0] = -1                                                                              # mask <bos>  (:241)
-                features_mask = path >= 0
-                n_on = features_mask.sum(-1)
-                order = torch.argsort((~features_mask).to(torch.int8), dim=1, stable=True)[:, : int(n_on.max())]
-                features_padding_mask = ~_lengths_to_mask(n_on, order.shape[1])
-            features_on_path = features.gather(1, order.unsqueeze(-1).expand(-1, -1, features.shape[-1])) \
-                .masked_fill(features_padding_mask.unsqueeze(-1), 0)                                         # _collate_frames (:244-246)
+            width = tgt_tokens.shape[1] - 1                                                                  # the widest count: no <bos>
+            if decode_ops.path_features_served(features, path, width):
+                # one HIP launch each way under autograd: vertex 0 (<bos>) skipped, the rows of the vertices on the path compacted in
+                # vertex order, zeros and True behind a sample's count; the width is a host integer, so this branch holds no host read.
+                # A batch whose longest target is shorter than the padded width gets trailing all-pad columns here, where the torch
+                # lines give a narrower tensor, which then disagrees with `durations`.
+                features_on_path, features_padding_mask, _ = decode_ops.path_features_checked(features, path, width)
+            else:
+                with torch.no_grad():
+                    path = path.clone()
+                    path[:, 0] = -1                                                                          # mask <bos>  (:241)
+                    features_mask = path >= 0
+                    n_on = features_mask.sum(-1)
+                    order = torch.argsort((~features_mask).to(torch.int8), dim=1, stable=True)[:, : int(n_on.max())]
+                    features_padding_mask = ~_lengths_to_mask(n_on, order.shape[1])
+                features_on_path = features.gather(1, order.unsqueeze(-1).expand(-1, -1, features.shape[-1])) \
+                    .masked_fill(features_padding_mask.unsqueeze(-1), 0)                                     # _collate_frames (:244-246)
             input_to_tts = model.adaptor(features_on_path)
         else:
             # expect: z_i = sum_j P(a_i = j | x, y) v_j   (:252-265)

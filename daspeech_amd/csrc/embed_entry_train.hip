@@ -5,8 +5,9 @@
 // arithmetic, one rounding, and their backward passes (include/daspeech_decode.h: dsp_embed_entry_fwd / _bwd, dsp_pos_add_fwd / _bwd).
 //
 // Forward, one launch each: a workgroup of four waves owns EE_TILE = 16 consecutive positions of one sample.  Its 256 threads count the kept
-// elements BEFORE the tile (one strided pass over the row's prefix, one LDS exchange), every wave takes the keep flags of the tile itself as
-// one ballot, and a row's position is that count plus a prefix popcount: left padding, interior pads and all-pad rows need nothing else.
+// elements BEFORE the tile (tile_positions of row_compact.h: one strided pass over the row's prefix, one LDS exchange), every wave takes the
+// keep flags of the tile itself as one ballot, and a row's position is that count plus a prefix popcount: left padding, interior pads and
+// all-pad rows need nothing else.
 // Then each wave moves four rows with 16-byte accesses.  tok32 (-1: a token outside [0, V), which contributes a zero row) and pos32 are kept
 // for the backward.
 //
@@ -43,6 +44,7 @@
 #include "common.h"
 #include "philox.h"
 #include "embed_rows.h"
+#include "row_compact.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -52,23 +54,6 @@ constexpr int EE_SORT_MAX = DSP_EMBED_ENTRY_SORT_MAX;
 constexpr int EE_MAX_C = DSP_EMBED_ENTRY_MAX_C;
 constexpr int PA_CHUNK = DSP_POS_ADD_CHUNK_ROWS;
 static_assert(EE_SORT_MAX <= 64, "a key's wave sorts one value per lane");
-
-// kept elements of sample row [0, t0) (`before`, the same in every thread) and the keep flags of the tile [t0, t0 + EE_TILE) as a mask
-// (bit i: position t0 + i).  All 256 threads of the workgroup call it.
-template <typename KeepFn>
-__device__ __forceinline__ void tile_positions(KeepFn keep, int t0, int L, int& before, unsigned& flags)
-{
-    __shared__ int wsum[4];
-    int c = 0;
-    for (int t = threadIdx.x; t < t0; t += 256) c += keep(t) ? 1 : 0;
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    before = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    const int lane = threadIdx.x & 63, t = t0 + lane;
-    const bool k = lane < EE_TILE && t < L && keep(t);
-    flags = (unsigned)__ballot(k);
-}
 
 // ---------------------------------------------------------------- token entry, forward
 template <typename T>
@@ -81,7 +66,7 @@ __global__ __launch_bounds__(256) void ee_fwd_kernel(const int64_t* __restrict__
     const int b = (int)(blockIdx.x / (unsigned)tiles), t0 = (int)(blockIdx.x % (unsigned)tiles) * EE_TILE;
     const int64_t* row = tokens + (size_t)b * (size_t)ld_tok;
     int before; unsigned flags;
-    tile_positions([&](int t) { return row[t] != pad; }, t0, L, before, flags);
+    tile_positions<EE_TILE>([&](int t) { return row[t] != pad; }, t0, L, before, flags);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll 1
     for (int j = 0; j < EE_TILE / 4; ++j) {
@@ -235,7 +220,7 @@ __global__ __launch_bounds__(1024) void ee_order_kernel(EeKeys ks, int e0, int e
                 const long me = e + lane;
                 const bool hit = me < hi && ks.key((int)me) == k;
                 const unsigned long long bal = __ballot(hit);
-                const int dst = at + __popcll(bal & ((1ull << lane) - 1ull));
+                const int dst = at + lanes_before(bal, lane);
                 if (hit && dst < end) perm[dst] = ks.row((int)me);
                 at += __popcll(bal);
             }
@@ -281,7 +266,7 @@ __global__ __launch_bounds__(256) void pa_fwd_kernel(const T* __restrict__ x, lo
     const int b = (int)(blockIdx.x / (unsigned)tiles), t0 = (int)(blockIdx.x % (unsigned)tiles) * EE_TILE;
     const unsigned char* row = mask + (size_t)b * (size_t)N;
     int before; unsigned flags;
-    tile_positions([&](int t) { return row[t] == 0; }, t0, N, before, flags);
+    tile_positions<EE_TILE>([&](int t) { return row[t] == 0; }, t0, N, before, flags);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float a = param_load(alpha, alpha_dtype, 0);
 #pragma unroll 1

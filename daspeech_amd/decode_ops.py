@@ -76,6 +76,12 @@ Host-side mirror of the reference code these replace:
                       (dy itself without dropout) and the gradient of the one-element alpha as a fixed-order two-stage sum; the model keeps
                       its torch lines where positional_add_dropout_served says no (the same switch); positional_add_dropout_checked is
                       internal to that model
+  path_features_autograd   DASpeech/criterions/s2s_dag_fastspeech2_loss.py:241-246 — the argmax strategy's features_on_path and its padding mask
+                      as one launch under autograd (csrc/path_features_train.hip): fp32 / fp16 / bf16, a stable compaction of the feature rows
+                      of the vertices on the path by ballots and popcounts, the width a host integer (no argsort, no host read of the widest
+                      count), rows copied bit for bit, a backward of one launch that writes every gradient row once without atomics, path
+                      and the sizes the only things saved; S2SDAGFastSpeech2Loss keeps its torch lines where path_features_served says no
+                      (set_path_features_hip(False): always); path_features_checked is internal to that criterion
 No CPU fallback elsewhere: GPU tensors only.
 Layouts: whatever the equivalent torch expression takes — views at odd storage offsets, pitched or transposed tensors, broadcast
 gradients — is served with its strides, copied to a dense 16-byte-aligned tensor (_dense16), or answered "not served" (_on_grid) so that the
@@ -2512,6 +2518,143 @@ def tts_losses_autograd(feat_out: Tensor, feat_post: Optional[Tensor], target_au
     args = _settled("tts_losses_autograd", _tts_loss_problem, (feat_out, feat_post, target_audio, audio_lens, log_dur_out, pitch_out,
                                                                energy_out, durations, pitches, energies, src_lens), 11)
     return tts_losses_checked(*args)
+
+
+# ------------------------------------------------------------------------------------------------ the argmax strategy's path features under autograd (csrc/path_features_train.hip)
+PATH_FEATURES_HIP = True         # set_path_features_hip(False): S2SDAGFastSpeech2Loss keeps its torch lines (argsort, host read of the width, gather) on every input
+PATH_FEATURES_TILE_W = 8         # DSP_PATH_FEATURES_TILE_W: rows of the result per forward workgroup
+PATH_FEATURES_TILE_L = 16        # DSP_PATH_FEATURES_TILE_L: vertices per backward workgroup
+PATH_FEATURES_MAX_L = 65536      # DSP_PATH_FEATURES_MAX_L
+PATH_FEATURES_MAX_ROWS = 1 << 24
+
+
+def set_path_features_hip(on: bool) -> bool:
+    """Switch the HIP path-features operator of S2SDAGFastSpeech2Loss's argmax strategy on or off; returns the previous setting.  Off:
+    path_features_served answers False and the criterion's torch lines run."""
+    global PATH_FEATURES_HIP
+    old, PATH_FEATURES_HIP = PATH_FEATURES_HIP, bool(on)
+    return old
+
+
+def _path_features_problem(features, path, width) -> Optional[str]:
+    """None when dsp_path_features_fwd / _bwd take these tensors as they are, else what is in the way (a layout of the features that a dense
+    copy settles begins with _LAYOUT; path is read through its strides in any layout)"""
+    if not (isinstance(features, Tensor) and isinstance(path, Tensor)):
+        return "features and path have to be tensors"
+    if features.dtype not in _FLOAT_CODES:
+        return f"features has to be fp32, fp16 or bf16, got {features.dtype} (float64 is refused, never narrowed)"
+    if features.dim() != 3:
+        return "features [B, L, C] expected"
+    B, L, C = features.shape
+    if path.dtype not in _INT_LENS or path.shape != (B, L):
+        return f"path has to be a [{B}, {L}] int64 or int32 tensor"
+    if not isinstance(width, int) or isinstance(width, bool) or width < 0:
+        return f"the width has to be a host integer >= 0, got {width!r}"
+    per = 16 // features.element_size()
+    if not (B >= 1 and 1 <= L <= PATH_FEATURES_MAX_L and C >= per and C % per == 0 and B * L <= PATH_FEATURES_MAX_ROWS
+            and B * width <= PATH_FEATURES_MAX_ROWS and C * features.element_size() <= PATH_FEATURES_MAX_ROWS):
+        return (f"features {tuple(features.shape)} / width {width} are not served (B, L >= 1, L <= {PATH_FEATURES_MAX_L}, C a multiple of {per} "
+                f"elements, B * L and B * width at most 2^24)")
+    why = _gpu_problem(features, path)
+    if why is not None:
+        return why
+    if features.device != path.device:
+        return "features and path have to be on one device"
+    ld = _row_pitch(features)
+    if ld is None or ld < C or ld % per or features.data_ptr() % 16:
+        return _LAYOUT + ": features needs unit column stride, one row pitch on the 16-byte grid and a 16-byte aligned start"
+    return None
+
+
+def path_features_served(features: Tensor, path: Tensor, width: int) -> bool:
+    """True when path_features_autograd serves these arguments as they are: the switch is on, autocast off, features a GPU tensor [B, L, C]
+    in fp32 / fp16 / bf16 with C a multiple of the elements in 16 bytes, unit column stride, rows one common pitch apart and a 16-byte aligned
+    start and pitch, path [B, L] int64 / int32 on that device (any strides), B, L >= 1, L <= 65 536, width a host integer >= 0, B * L and
+    B * width at most 2^24.  There is no randomness and no host read: a capturing stream is no reason to decline.  Everything else — CPU
+    tensors, float64, another layout — keeps the torch lines."""
+    if not PATH_FEATURES_HIP or torch.is_autocast_enabled():
+        return False
+    return _path_features_problem(features, path, width) is None
+
+
+def _path_strides(path: Tensor) -> Tuple[int, int]:
+    """batch and column stride of path [B, L] for the C ABI: the stride of a dimension of length 1 is never used, and torch leaves it arbitrary"""
+    return (path.stride(0) if path.shape[0] > 1 else 0), (path.stride(1) if path.shape[1] > 1 else 0)
+
+
+def _path_features_forward(features, path, width, skip_first, ld):
+    """dsp_path_features_fwd: (out [B,W,C], pad [B,W] bool, n [B] int64), width >= 1"""
+    B, L, C = features.shape
+    dev = features.device
+    out = torch.empty((B, width, C), dtype=features.dtype, device=dev)
+    pad = torch.empty((B, width), dtype=torch.bool, device=dev)
+    n = torch.empty((B,), dtype=torch.int64, device=dev)
+    _launch(dev, _lib.load().dsp_path_features_fwd, features.data_ptr(), ld, path.data_ptr(), *_path_strides(path), int(path.dtype == torch.int64),
+            int(skip_first), out.data_ptr(), pad.data_ptr(), n.data_ptr(), _FLOAT_CODES[features.dtype], B, L, width, C)
+    return out, pad, n
+
+
+class _PathFeaturesFn(torch.autograd.Function):
+    """dsp_path_features_fwd / _bwd.  Saved for the backward: path and the sizes — no index, no rank, no feature."""
+
+    @staticmethod
+    def forward(ctx, features, path, width, skip_first, ld):
+        out, pad, n = _path_features_forward(features, path, width, skip_first, ld)
+        ctx.save_for_backward(path)
+        ctx.call = (tuple(features.shape), features.dtype, width, skip_first)
+        ctx.mark_non_differentiable(pad, n)
+        ctx.set_materialize_grads(False)
+        return out, pad, n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dpad, _dn):
+        (path,) = ctx.saved_tensors
+        (B, L, C), dt, width, skip_first = ctx.call
+        if dy is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if dy.dtype != dt:
+            dy = dy.to(dt)
+        per = 16 // dy.element_size()
+        sb, sr = (dy.stride(0) if B > 1 else 0), (dy.stride(1) if width > 1 else 0)      # a broadcast (stride 0) is read in place
+        if (dy.stride(2) != 1 and C > 1) or dy.data_ptr() % 16 or sb % per or sr % per:      # a transpose, a narrow at an odd offset or pitch
+            dy = dy.clone(memory_format=torch.contiguous_format)
+            sb, sr = width * C, C
+        dev = dy.device
+        dfeatures = torch.empty((B, L, C), dtype=dt, device=dev)
+        _launch(dev, _lib.load().dsp_path_features_bwd, dy.data_ptr(), sb, sr, path.data_ptr(), *_path_strides(path),
+                int(path.dtype == torch.int64), int(skip_first), dfeatures.data_ptr(), _FLOAT_CODES[dt], B, L, width, C)
+        return dfeatures, None, None, None, None
+
+
+def path_features_checked(features, path, width, skip_first=True):
+    """INTERNAL to the package's criterion: path_features_autograd WITHOUT its argument checks, valid only on arguments that
+    path_features_served accepted.  The kernels trust what they are handed: any other caller uses path_features_autograd."""
+    if width == 0:                                                          # empty tensors, no launch: a view keeps the gradient's route
+        B = features.shape[0]
+        return (features[:, :0], torch.empty((B, 0), dtype=torch.bool, device=features.device),
+                torch.zeros((B,), dtype=torch.int64, device=features.device))
+    ld = _row_pitch(features)
+    if torch.is_grad_enabled() and features.requires_grad:
+        return _PathFeaturesFn.apply(features, path, width, bool(skip_first), ld)
+    return _path_features_forward(features, path, width, bool(skip_first), ld)      # nothing is saved
+
+
+def path_features_autograd(features: Tensor, path: Tensor, width: int, skip_first: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+    """(out [B, W, C], pad [B, W] bool, n [B] int64): the feature rows of the vertices on the path, compacted in vertex order — the argmax
+    strategy's features_on_path and features_padding_mask (DASpeech/criterions/s2s_dag_fastspeech2_loss.py:241-246), differentiable w.r.t.
+    features (include/daspeech_decode.h: dsp_path_features_fwd / _bwd).  With on[b,j] = path[b,j] >= 0 and (j > 0 or not skip_first) and
+    n[b] = min(sum_j on[b,j], W):  out[b,r] = features[b, j_r] for r < n[b], j_r the r-th vertex with `on` set; exact zeros (written, not
+    multiplied: NaN in a row that is not selected never shows) and pad = True for r >= n[b].  W is a HOST integer — in the criterion
+    tgt_tokens.shape[1] - 1 —, so forward and backward hold NO HOST READ of device data; vertices on the path beyond W are dropped, and
+    only the sign of a path value is read.  features [B, L, C] fp32 / fp16 / bf16 on the GPU (float64 is refused, never narrowed), C a
+    multiple of the elements in 16 bytes; a row-pitched view is read in place, any other layout (a transpose, a start off the 16-byte grid)
+    is copied to a dense tensor, gradients pass through; path int64 / int32 in any layout.  Rows are copied bit for bit, one launch each way,
+    no sort, no atomics: the gradient of a feature row is the one row of dy it was copied to, or exact zero, every element written.  Saved
+    for the backward: path and the sizes; under torch.no_grad(), or when features does not require grad, nothing.  W == 0 returns empty
+    tensors without a launch.  pad and n are not differentiable.  Raises RuntimeError on what is not served."""
+    features, path, width = _settled("path_features_autograd", _path_features_problem, (features, path, width), 1)
+    return path_features_checked(features, path, width, skip_first)
 
 
 class SplitConv1d:

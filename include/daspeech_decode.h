@@ -452,6 +452,31 @@ int dsp_tts_loss_bwd(const float* grad_losses, const float* inv_counts, const vo
                      const void* src_lens, int len64, int dur64, void* d_feat_out, void* d_feat_post, void* d_log_dur, void* d_pitch,
                      void* d_energy, int dtype, int B, int F, int F_, int C, int N, dsp_stream_t stream);
 
+/* The argmax strategy's features_on_path under autograd (csrc/path_features_train.hip): a stable compaction of feature rows, no sort, no
+ * atomics, no width read from the device.  features [B,L,C] in DSP_F32 / DSP_F16 / DSP_BF16, read as B*L rows of unit column stride ld_f
+ * elements apart (>= C, a multiple of the elements in 16 bytes); path [B,L] int64 (path64 != 0) or int32 through its batch and column
+ * strides in elements (>= 0), of which ONLY THE SIGN of a value is read; W >= 0 the width of the result, a host integer.
+ *     on[b,j] = path[b,j] >= 0 && (j > 0 || !skip_first)          n[b] = min(sum_j on[b,j], W)
+ *   dsp_path_features_fwd, one launch that writes all three outputs completely (no memset, no workspace):
+ *     out[b,r,:] = features[b, j_r, :] for r < n[b], j_r the r-th vertex with `on` set in ascending j; EXACT ZEROS for r >= n[b] — written,
+ *     not multiplied: NaN or Inf in a row that is not selected never shows.  out [B,W,C] contiguous, pad [B,W] bytes (1: r >= n[b]),
+ *     n [B] int64.  A path with more than W vertices on drops the surplus.  W == 0 (or B == 0): DSP_OK without a launch, nothing is written.
+ *   dsp_path_features_bwd, one launch that writes EVERY element of dfeatures [B,L,C] (contiguous) exactly once, without float atomics:
+ *     dfeatures[b,j,:] = dy[b,r,:] where j = j_r for some r < n[b], else exact zeros.  dy [B,W,C] is read through its batch and row strides
+ *     in elements (>= 0, multiples of the elements in 16 bytes; unit column stride; 0 for a broadcast); with W == 0 dy is not read.
+ *   Rows move as 16-byte quads, bit for bit: the result does not depend on the dtype beyond its element size.  A workgroup of the forward
+ *   owns DSP_PATH_FEATURES_TILE_W rows of one sample's result, one of the backward DSP_PATH_FEATURES_TILE_L vertices; each rescans its
+ *   sample's path row (ballots and popcounts over chunks of 64 vertices, a prefix over the chunk counts).
+ *   Bad sizes (B < 0, L < 1, L > DSP_PATH_FEATURES_MAX_L, W < 0, C no multiple of the elements in 16 bytes, B*L or B*W above 2^24), an unknown
+ *   dtype, a negative stride, a null or aliased pointer, features / out / dy / dfeatures off the 16-byte grid: DSP_EINVAL before any launch. */
+#define DSP_PATH_FEATURES_TILE_W 8
+#define DSP_PATH_FEATURES_TILE_L 16
+#define DSP_PATH_FEATURES_MAX_L 65536
+int dsp_path_features_fwd(const void* features, long ld_f, const void* path, long path_sb, long path_sc, int path64, int skip_first, void* out,
+                          unsigned char* pad, int64_t* n, int dtype, int B, int L, int W, int C, dsp_stream_t stream);
+int dsp_path_features_bwd(const void* dy, long dy_sb, long dy_sr, const void* path, long path_sb, long path_sc, int path64, int skip_first,
+                          void* dfeatures, int dtype, int B, int L, int W, int C, dsp_stream_t stream);
+
 /* Conformer relative-position self-attention under autograd (csrc/relpos_attention_train.hip), fp16 / bf16 data, head width 64:
  *     s(b,h,i,j) = ((q_i + u_h).k_j + (q_i + v_h).pos[T-1-i+j]) / 8,  keys with pad_mask[b,j] != 0: -inf
  *     P = softmax_j(s);  lse(b,h,i) = log sum_j exp s;  A = keep ? P * keep_scale : 0;  out_i = sum_j A_ij v_j
