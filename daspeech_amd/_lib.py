@@ -199,6 +199,13 @@ SIGNATURES = {
     "dsp_dag_last_fallback_count": (ctypes.c_uint, []),
     "dsp_dag_debug_words": (ctypes.POINTER(ctypes.c_uint), []),
 }
+# the masked launches with the dropout state on the device: the entry of the same name with `const uint64_t* rng_state` before the stream
+STATE_ENTRIES = ("dsp_resnorm_train_fwd", "dsp_resnorm_train_bwd", "dsp_dropout_keep_mask", "dsp_act_dropout_train_fwd",
+                 "dsp_act_dropout_train_bwd", "dsp_embed_entry_fwd", "dsp_embed_entry_bwd", "dsp_pos_add_fwd", "dsp_pos_add_bwd",
+                 "dsp_relpos_attention_train_fwd", "dsp_relpos_attention_train_bwd", "dsp_mha_train_fwd", "dsp_mha_train_bwd")
+for _name in STATE_ENTRIES:
+    SIGNATURES[_name + "_state"] = (SIGNATURES[_name][0], SIGNATURES[_name][1][:-1] + [_c_p, _c_p])
+SIGNATURES["dsp_dropout_state_advance"] = (_c_int, [_c_p, ctypes.c_uint64, _c_p])
 
 _lib = None
 

@@ -56,9 +56,10 @@ static_assert(AD_FWD_ROWS * AD_FWD_WAVES == AD_CHUNK, "the waves of the forward 
 template <typename T, int ACT>
 __global__ __launch_bounds__(64 * AD_FWD_WAVES) void ad_fwd_kernel(const T* __restrict__ h, long ld_h, const void* __restrict__ bias, int pdtype,
                                                                    float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset,
-                                                                   T* __restrict__ y, long R, int Cout)
+                                                                   const uint64_t* __restrict__ rng_state, T* __restrict__ y, long R, int Cout)
 {
     constexpr int V = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     constexpr bool GLU = ACT == DSP_ACT_GLU;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = ((int)blockIdx.y * AD_SLAB + lane) * V;
@@ -105,9 +106,11 @@ __global__ __launch_bounds__(64 * AD_FWD_WAVES) void ad_fwd_kernel(const T* __re
 template <typename T, int ACT>
 __global__ __launch_bounds__(64) void ad_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ h, long ld_h,
                                                     const void* __restrict__ bias, int pdtype, float keep_scale, uint32_t thr, uint64_t seed,
-                                                    uint64_t offset, T* __restrict__ dh, float* __restrict__ part, long R, int Cout)
+                                                    uint64_t offset, const uint64_t* __restrict__ rng_state, T* __restrict__ dh,
+                                                    float* __restrict__ part, long R, int Cout)
 {
     constexpr int V = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     constexpr bool GLU = ACT == DSP_ACT_GLU;
     const int Cin = GLU ? 2 * Cout : Cout;
     const int c = ((int)blockIdx.y * AD_SLAB + (int)threadIdx.x) * V;
@@ -194,8 +197,10 @@ __global__ __launch_bounds__(256) void ad_dbias_merge_kernel(const float* __rest
 static long ad_chunks(long R) { return (R + AD_CHUNK - 1) / AD_CHUNK; }
 
 // what both entry points check; 1: nothing to do (R == 0), 0: go on, < 0: refused
-static int ad_check(const char* who, int act, int act_dtype, int param_dtype, long R, int Cin, long ld_h, unsigned int thr)
+static int ad_check(const char* who, int act, int act_dtype, int param_dtype, long R, int Cin, long ld_h, unsigned int thr,
+                    const uint64_t* rng_state)
 {
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int es = elem_size(act_dtype);
     if (!es || !elem_size(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (h, y and their gradients) / %d (bias, dbias: the same, or fp32)", who, act_dtype, param_dtype);
@@ -234,11 +239,10 @@ extern "C" size_t dsp_act_dropout_train_workspace_bytes(int64_t R, int Cin)
     return ((size_t)ad_chunks((long)R) * (size_t)Cin * sizeof(float) + 15) & ~(size_t)15;
 }
 
-extern "C" int dsp_act_dropout_train_fwd(const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
-                                         uint64_t offset, void* y, int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
+static int ad_fwd(const char* who, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
+                  uint64_t offset, const uint64_t* rng_state, void* y, int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
 {
-    const char* who = "act_dropout_train_fwd";
-    const int rc = ad_check(who, act, act_dtype, param_dtype, (long)R, Cin, ld_h, thr);
+    const int rc = ad_check(who, act, act_dtype, param_dtype, (long)R, Cin, ld_h, thr, rng_state);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!h || !y || y == h || (bias && (bias == h || bias == y))) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
     if ((((uintptr_t)h) | ((uintptr_t)bias) | ((uintptr_t)y)) & 15) { set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL; }
@@ -246,16 +250,29 @@ extern "C" int dsp_act_dropout_train_fwd(const void* h, long ld_h, const void* b
     const dim3 grid((unsigned)ad_chunks((long)R), (unsigned)((Cout / V + AD_SLAB - 1) / AD_SLAB));
     hipStream_t st = as_stream(stream);
     AD_DISPATCH(act_dtype, act, hipLaunchKernelGGL((ad_fwd_kernel<E, ACT>), grid, dim3(64 * AD_FWD_WAVES), 0, st, (const E*)h, ld_h, bias, param_dtype, keep_scale,
-                                                   (uint32_t)thr, seed, offset, (E*)y, (long)R, Cout));
+                                                   (uint32_t)thr, seed, offset, rng_state, (E*)y, (long)R, Cout));
     return check_launch(who);
 }
 
-extern "C" int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
-                                         uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes,
-                                         int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
+extern "C" int dsp_act_dropout_train_fwd(const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
+                                         uint64_t offset, void* y, int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
 {
-    const char* who = "act_dropout_train_bwd";
-    const int rc = ad_check(who, act, act_dtype, param_dtype, (long)R, Cin, ld_h, thr);
+    return ad_fwd("act_dropout_train_fwd", h, ld_h, bias, act, keep_scale, thr, seed, offset, nullptr, y, act_dtype, param_dtype, R, Cin, stream);
+}
+
+extern "C" int dsp_act_dropout_train_fwd_state(const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
+                                               uint64_t seed, uint64_t offset, void* y, int act_dtype, int param_dtype, int64_t R, int Cin,
+                                               const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return ad_fwd("act_dropout_train_fwd_state", h, ld_h, bias, act, keep_scale, thr, seed, offset, rng_state, y, act_dtype, param_dtype, R, Cin,
+                  stream);
+}
+
+static int ad_bwd(const char* who, const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
+                  uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dh, void* dbias, void* workspace, size_t workspace_bytes,
+                  int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
+{
+    const int rc = ad_check(who, act, act_dtype, param_dtype, (long)R, Cin, ld_h, thr, rng_state);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dh && !dbias) return DSP_OK;
     if (!dy || !h || (dh && (dh == dy || dh == h || dh == bias || dh == dbias)) || (dbias && (dbias == dy || dbias == h || dbias == bias))) {
@@ -274,8 +291,25 @@ extern "C" int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_
     float* part = dbias ? (float*)workspace : (float*)nullptr;
     hipStream_t st = as_stream(stream);
     AD_DISPATCH(act_dtype, act, hipLaunchKernelGGL((ad_bwd_kernel<E, ACT>), grid, dim3(64), 0, st, (const E*)dy, (const E*)h, ld_h, bias, param_dtype,
-                                                   keep_scale, (uint32_t)thr, seed, offset, (E*)dh, part, (long)R, Cout));
+                                                   keep_scale, (uint32_t)thr, seed, offset, rng_state, (E*)dh, part, (long)R, Cout));
     if (dbias)
         hipLaunchKernelGGL(ad_dbias_merge_kernel, dim3((unsigned)((Cin + 63) / 64)), dim3(256), 0, st, part, nchunks, dbias, param_dtype, Cin);
     return check_launch(who);
+}
+
+extern "C" int dsp_act_dropout_train_bwd(const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
+                                         uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes,
+                                         int act_dtype, int param_dtype, int64_t R, int Cin, dsp_stream_t stream)
+{
+    return ad_bwd("act_dropout_train_bwd", dy, h, ld_h, bias, act, keep_scale, thr, seed, offset, nullptr, dh, dbias, workspace, workspace_bytes,
+                  act_dtype, param_dtype, R, Cin, stream);
+}
+
+extern "C" int dsp_act_dropout_train_bwd_state(const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale,
+                                               unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace,
+                                               size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R, int Cin,
+                                               const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return ad_bwd("act_dropout_train_bwd_state", dy, h, ld_h, bias, act, keep_scale, thr, seed, offset, rng_state, dh, dbias, workspace,
+                  workspace_bytes, act_dtype, param_dtype, R, Cin, stream);
 }

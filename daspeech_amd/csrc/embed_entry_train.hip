@@ -59,10 +59,11 @@ static_assert(EE_SORT_MAX <= 64, "a key's wave sorts one value per lane");
 template <typename T>
 __global__ __launch_bounds__(256) void ee_fwd_kernel(const int64_t* __restrict__ tokens, long ld_tok, const T* __restrict__ E,
                                                      const T* __restrict__ P, int64_t pad, float embed_scale, float keep_scale, uint32_t thr,
-                                                     uint64_t seed, uint64_t offset, T* __restrict__ y, int32_t* __restrict__ tok32,
-                                                     int32_t* __restrict__ pos32, int L, int V, int NP, int C, int tiles)
+                                                     uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state, T* __restrict__ y,
+                                                     int32_t* __restrict__ tok32, int32_t* __restrict__ pos32, int L, int V, int NP, int C, int tiles)
 {
     constexpr int VE = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     const int b = (int)(blockIdx.x / (unsigned)tiles), t0 = (int)(blockIdx.x % (unsigned)tiles) * EE_TILE;
     const int64_t* row = tokens + (size_t)b * (size_t)ld_tok;
     int before; unsigned flags;
@@ -102,9 +103,10 @@ __global__ __launch_bounds__(256) void ee_fwd_kernel(const int64_t* __restrict__
 // ---------------------------------------------------------------- g = dy * m as fp32 (thr != 0 only)
 template <typename T, typename TO>
 __global__ __launch_bounds__(256) void ee_mask_kernel(const T* __restrict__ dy, TO* __restrict__ g, long groups, float keep_scale, uint32_t thr,
-                                                      uint64_t seed, uint64_t offset)
+                                                      uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state)
 {
     constexpr int VE = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < groups; q += (long)gridDim.x * 256) {
         float f[VE]; bool k[VE];
         load_f<T, VE>(dy + q * VE, f);
@@ -127,6 +129,14 @@ struct EeKeys {
     }
     __device__ __forceinline__ int row(int e) const { return e < n ? e : e - n; }
 };
+
+// step 0: counts and cursor to zero — a kernel, not a memset: as a node of a captured graph the launch is ordered with the kernels around it
+// exactly as on the stream, and everything below trusts these 2K integers (a stale cursor leaves list slots unwritten, and a list entry is a
+// row index that embed_chunk_sum_kernel reads through)
+__global__ __launch_bounds__(256) void ee_zero_kernel(int32_t* __restrict__ p, long n)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = 0;
+}
 
 // step 1: counts.  A wave adds once per distinct key of its 64 entries (the training pattern has one key in nearly all of them).
 __global__ __launch_bounds__(256) void ee_count_kernel(EeKeys ks, int e0, int e1, int32_t* __restrict__ counts)
@@ -260,9 +270,11 @@ template <typename T>
 __global__ __launch_bounds__(256) void pa_fwd_kernel(const T* __restrict__ x, long ld_x, const unsigned char* __restrict__ mask,
                                                      const void* __restrict__ tab, int tab_dtype, const void* __restrict__ alpha,
                                                      int alpha_dtype, int pad, float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset,
-                                                     T* __restrict__ y, int32_t* __restrict__ pos32, int N, int NT, int C, int tiles)
+                                                     const uint64_t* __restrict__ rng_state, T* __restrict__ y, int32_t* __restrict__ pos32, int N,
+                                                     int NT, int C, int tiles)
 {
     constexpr int VE = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     const int b = (int)(blockIdx.x / (unsigned)tiles), t0 = (int)(blockIdx.x % (unsigned)tiles) * EE_TILE;
     const unsigned char* row = mask + (size_t)b * (size_t)N;
     int before; unsigned flags;
@@ -301,9 +313,11 @@ __global__ __launch_bounds__(256) void pa_fwd_kernel(const T* __restrict__ x, lo
 template <typename T>
 __global__ __launch_bounds__(64) void pa_bwd_kernel(const T* __restrict__ dy, const void* __restrict__ tab, int tab_dtype,
                                                     const int32_t* __restrict__ pos32, float keep_scale, uint32_t thr, uint64_t seed,
-                                                    uint64_t offset, T* __restrict__ dx, float* __restrict__ part, long R, int NT, int C)
+                                                    uint64_t offset, const uint64_t* __restrict__ rng_state, T* __restrict__ dx,
+                                                    float* __restrict__ part, long R, int NT, int C)
 {
     constexpr int VE = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     const int lane = threadIdx.x;
     const long r0 = (long)blockIdx.x * PA_CHUNK, r1 = r0 + PA_CHUNK < R ? r0 + PA_CHUNK : R;
     double acc = 0.0;
@@ -398,11 +412,11 @@ static int pa_check(const char* who, int act_dtype, int tab_dtype, int alpha_dty
 
 using namespace dsp;
 
-extern "C" int dsp_embed_entry_fwd(const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale,
-                                   float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* tok32, int32_t* pos32,
-                                   int dtype, int B, int L, int V, int NP, int C, dsp_stream_t stream)
+static int ee_fwd(const char* who, const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale,
+                  float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* y, int32_t* tok32,
+                  int32_t* pos32, int dtype, int B, int L, int V, int NP, int C, dsp_stream_t stream)
 {
-    const char* who = "embed_entry_fwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     if (B < 0 || L < 0) { set_error("%s: bad sizes B=%d L=%d", who, B, L); return DSP_EINVAL; }
     const int rc = ee_check(who, dtype, (int64_t)B * L, V, NP, C, pad, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
@@ -414,8 +428,25 @@ extern "C" int dsp_embed_entry_fwd(const int64_t* tokens, long ld_tok, const voi
     const int tiles = (L + EE_TILE - 1) / EE_TILE;
     DSP_DISPATCH_ELEM(dtype, T, hipLaunchKernelGGL(ee_fwd_kernel<T>, dim3((unsigned)B * (unsigned)tiles), dim3(256), 0, as_stream(stream), tokens,
                                                    ld_tok, (const T*)E, (const T*)P, pad, embed_scale, keep_scale, (uint32_t)thr, seed, offset,
-                                                   (T*)y, tok32, pos32, L, V, NP, C, tiles));
+                                                   rng_state, (T*)y, tok32, pos32, L, V, NP, C, tiles));
     return check_launch(who);
+}
+
+extern "C" int dsp_embed_entry_fwd(const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale,
+                                   float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* tok32, int32_t* pos32,
+                                   int dtype, int B, int L, int V, int NP, int C, dsp_stream_t stream)
+{
+    return ee_fwd("embed_entry_fwd", tokens, ld_tok, E, P, pad, embed_scale, keep_scale, thr, seed, offset, nullptr, y, tok32, pos32, dtype, B, L, V,
+                  NP, C, stream);
+}
+
+extern "C" int dsp_embed_entry_fwd_state(const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale,
+                                         float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* tok32,
+                                         int32_t* pos32, int dtype, int B, int L, int V, int NP, int C, const uint64_t* rng_state,
+                                         dsp_stream_t stream)
+{
+    return ee_fwd("embed_entry_fwd_state", tokens, ld_tok, E, P, pad, embed_scale, keep_scale, thr, seed, offset, rng_state, y, tok32, pos32, dtype,
+                  B, L, V, NP, C, stream);
 }
 
 extern "C" size_t dsp_embed_entry_bwd_workspace_bytes(int64_t n, int V, int NP, int C, unsigned int thr)
@@ -425,11 +456,11 @@ extern "C" size_t dsp_embed_entry_bwd_workspace_bytes(int64_t n, int V, int NP, 
     return ee_int_bytes(n, K) + (thr ? up16((size_t)n * C * sizeof(float)) : 0) + up16((size_t)ee_max_chunks(n, K) * C * sizeof(float));
 }
 
-extern "C" int dsp_embed_entry_bwd(const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
-                                   unsigned int thr, uint64_t seed, uint64_t offset, void* dE, void* dP, void* workspace,
-                                   size_t workspace_bytes, int dtype, int64_t n, int V, int NP, int C, dsp_stream_t stream)
+static int ee_bwd(const char* who, const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
+                  unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dE, void* dP, void* workspace,
+                  size_t workspace_bytes, int dtype, int64_t n, int V, int NP, int C, dsp_stream_t stream)
 {
-    const char* who = "embed_entry_bwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = ee_check(who, dtype, n, V, NP, C, pad, thr);
     if (rc < 0) return rc;
     if (!dE && !dP) return DSP_OK;
@@ -464,13 +495,12 @@ extern "C" int dsp_embed_entry_bwd(const void* dy, const int32_t* tok32, const i
     float* partial = (float*)(fl + (thr ? up16((size_t)n * C * sizeof(float)) : 0));
     const int e0 = dE ? 0 : N, e1 = dP ? 2 * N : N;                        // the entries of a table that is not asked for do not exist
     const EeKeys ks{tok32, pos32, N, V, NP, (int)pad};
-    const hipError_t me = hipMemsetAsync(counts, 0, (size_t)2 * K * sizeof(int32_t), st);       // counts and cursor
-    if (me != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(me)); return (int)me; }
+    hipLaunchKernelGGL(ee_zero_kernel, dim3(wave_grid(((long)2 * K + 63) / 64)), dim3(256), 0, st, counts, (long)2 * K);      // counts and cursor
     if (thr) {
         const long groups = (long)n * C * es / 16;
         const unsigned grid = (unsigned)((groups + 255) / 256 > 4096 ? 4096 : (groups + 255) / 256);
         DSP_DISPATCH_ELEM(dtype, T, hipLaunchKernelGGL((ee_mask_kernel<T, float>), dim3(grid), dim3(256), 0, st, (const T*)dy, g32, groups,
-                                                       keep_scale, (uint32_t)thr, seed, offset));
+                                                       keep_scale, (uint32_t)thr, seed, offset, rng_state));
     }
     const long E = (long)e1 - e0;
     hipLaunchKernelGGL(ee_count_kernel, dim3(wave_grid((E + 63) / 64)), dim3(256), 0, st, ks, e0, e1, counts);
@@ -491,11 +521,28 @@ extern "C" int dsp_embed_entry_bwd(const void* dy, const int32_t* tok32, const i
     return check_launch(who);
 }
 
-extern "C" int dsp_pos_add_fwd(const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad,
-                               float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* pos32, int act_dtype,
-                               int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, dsp_stream_t stream)
+extern "C" int dsp_embed_entry_bwd(const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
+                                   unsigned int thr, uint64_t seed, uint64_t offset, void* dE, void* dP, void* workspace,
+                                   size_t workspace_bytes, int dtype, int64_t n, int V, int NP, int C, dsp_stream_t stream)
 {
-    const char* who = "pos_add_fwd";
+    return ee_bwd("embed_entry_bwd", dy, tok32, pos32, pad, embed_scale, keep_scale, thr, seed, offset, nullptr, dE, dP, workspace, workspace_bytes,
+                  dtype, n, V, NP, C, stream);
+}
+
+extern "C" int dsp_embed_entry_bwd_state(const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale,
+                                         float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dE, void* dP, void* workspace,
+                                         size_t workspace_bytes, int dtype, int64_t n, int V, int NP, int C, const uint64_t* rng_state,
+                                         dsp_stream_t stream)
+{
+    return ee_bwd("embed_entry_bwd_state", dy, tok32, pos32, pad, embed_scale, keep_scale, thr, seed, offset, rng_state, dE, dP, workspace,
+                  workspace_bytes, dtype, n, V, NP, C, stream);
+}
+
+static int pa_fwd(const char* who, const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad,
+                  float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* y, int32_t* pos32,
+                  int act_dtype, int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, dsp_stream_t stream)
+{
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     if (B < 0 || N < 0 || pad < 0) { set_error("%s: bad sizes B=%d N=%d pad=%d", who, B, N, pad); return DSP_EINVAL; }
     const int rc = pa_check(who, act_dtype, tab_dtype, alpha_dtype, (int64_t)B * N, NT, C, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
@@ -506,8 +553,24 @@ extern "C" int dsp_pos_add_fwd(const void* x, long ld_x, const unsigned char* pa
     const int tiles = (N + EE_TILE - 1) / EE_TILE;
     DSP_DISPATCH_ELEM(act_dtype, T, hipLaunchKernelGGL(pa_fwd_kernel<T>, dim3((unsigned)B * (unsigned)tiles), dim3(256), 0, as_stream(stream),
                                                        (const T*)x, ld_x, padding_mask, tab, tab_dtype, alpha, alpha_dtype, pad, keep_scale,
-                                                       (uint32_t)thr, seed, offset, (T*)y, pos32, N, NT, C, tiles));
+                                                       (uint32_t)thr, seed, offset, rng_state, (T*)y, pos32, N, NT, C, tiles));
     return check_launch(who);
+}
+
+extern "C" int dsp_pos_add_fwd(const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad,
+                               float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* pos32, int act_dtype,
+                               int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, dsp_stream_t stream)
+{
+    return pa_fwd("pos_add_fwd", x, ld_x, padding_mask, tab, alpha, pad, keep_scale, thr, seed, offset, nullptr, y, pos32, act_dtype, tab_dtype,
+                  alpha_dtype, B, N, NT, C, stream);
+}
+
+extern "C" int dsp_pos_add_fwd_state(const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad,
+                                     float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* pos32, int act_dtype,
+                                     int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return pa_fwd("pos_add_fwd_state", x, ld_x, padding_mask, tab, alpha, pad, keep_scale, thr, seed, offset, rng_state, y, pos32, act_dtype,
+                  tab_dtype, alpha_dtype, B, N, NT, C, stream);
 }
 
 extern "C" size_t dsp_pos_add_bwd_workspace_bytes(int64_t R)
@@ -516,11 +579,11 @@ extern "C" size_t dsp_pos_add_bwd_workspace_bytes(int64_t R)
     return up16((size_t)((R + PA_CHUNK - 1) / PA_CHUNK) * 2 * sizeof(float));
 }
 
-extern "C" int dsp_pos_add_bwd(const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
-                               uint64_t offset, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype, int tab_dtype,
-                               int alpha_dtype, int64_t R, int NT, int C, dsp_stream_t stream)
+static int pa_bwd(const char* who, const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
+                  uint64_t offset, const uint64_t* rng_state, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype,
+                  int tab_dtype, int alpha_dtype, int64_t R, int NT, int C, dsp_stream_t stream)
 {
-    const char* who = "pos_add_bwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = pa_check(who, act_dtype, tab_dtype, alpha_dtype, R, NT, C, thr);
     if (rc < 0) return rc;
     if (!dx && !dalpha) return DSP_OK;
@@ -546,7 +609,23 @@ extern "C" int dsp_pos_add_bwd(const void* dy, const void* tab, const int32_t* p
         if (!dalpha) return DSP_OK;
     }
     DSP_DISPATCH_ELEM(act_dtype, T, hipLaunchKernelGGL(pa_bwd_kernel<T>, dim3((unsigned)nchunks), dim3(64), 0, st, (const T*)dy, tab, tab_dtype, pos32,
-                                                       keep_scale, (uint32_t)thr, seed, offset, (T*)dx, part, (long)R, NT, C));
+                                                       keep_scale, (uint32_t)thr, seed, offset, rng_state, (T*)dx, part, (long)R, NT, C));
     if (dalpha) hipLaunchKernelGGL(pa_dalpha_kernel, dim3(1), dim3(256), 0, st, (const float*)part, nchunks, dalpha, alpha_dtype);
     return check_launch(who);
+}
+
+extern "C" int dsp_pos_add_bwd(const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
+                               uint64_t offset, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype, int tab_dtype,
+                               int alpha_dtype, int64_t R, int NT, int C, dsp_stream_t stream)
+{
+    return pa_bwd("pos_add_bwd", dy, tab, pos32, keep_scale, thr, seed, offset, nullptr, dx, dalpha, workspace, workspace_bytes, act_dtype,
+                  tab_dtype, alpha_dtype, R, NT, C, stream);
+}
+
+extern "C" int dsp_pos_add_bwd_state(const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
+                                     uint64_t offset, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype,
+                                     int tab_dtype, int alpha_dtype, int64_t R, int NT, int C, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return pa_bwd("pos_add_bwd_state", dy, tab, pos32, keep_scale, thr, seed, offset, rng_state, dx, dalpha, workspace, workspace_bytes, act_dtype,
+                  tab_dtype, alpha_dtype, R, NT, C, stream);
 }

@@ -168,11 +168,13 @@ __device__ __forceinline__ void mh_store_row(E* dst, const ra_acc& t0, const ra_
 template <typename E>
 __global__ __launch_bounds__(MH_THREADS, 2) void mh_fwd_kernel(const E* __restrict__ q, long ldq, const E* __restrict__ k, const E* __restrict__ v, long ldkv,
                                                                const unsigned char* __restrict__ mask, float keep_scale, uint32_t thr, uint64_t seed,
-                                                               uint64_t offset, E* __restrict__ out, float* __restrict__ lse, int N, int M, int H)
+                                                               uint64_t offset, const uint64_t* __restrict__ rng_state, E* __restrict__ out,
+                                                               float* __restrict__ lse, int N, int M, int H)
 {
     using V = typename Ra<E>::V;
     __shared__ __attribute__((aligned(16))) ra_u16 Ks[32 * RA_P64], Vt[64 * RA_P32];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, il = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int nI = (N + MH_OWN - 1) / MH_OWN, C = H * 64, Mp = (M + 3) & ~3;
     const int ib = blockIdx.x % nI, bh = blockIdx.x / nI, h = bh % H, b = bh / H, i0 = ib * MH_OWN + wave * 32, i = i0 + il;
     const E* kb = k + (long)b * M * ldkv + h * 64;
@@ -239,11 +241,13 @@ template <typename E>
 __global__ __launch_bounds__(MH_THREADS, 2) void mh_bwd_q_kernel(const E* __restrict__ dout, const E* __restrict__ q, long ldq, const E* __restrict__ k,
                                                                  const E* __restrict__ v, long ldkv, const unsigned char* __restrict__ mask,
                                                                  const float* __restrict__ lse, float keep_scale, uint32_t thr, uint64_t seed,
-                                                                 uint64_t offset, float* __restrict__ dsum, E* __restrict__ dq, int N, int M, int H)
+                                                                 uint64_t offset, const uint64_t* __restrict__ rng_state, float* __restrict__ dsum,
+                                                                 E* __restrict__ dq, int N, int M, int H)
 {
     using V = typename Ra<E>::V;
     __shared__ __attribute__((aligned(16))) ra_u16 Ks[32 * RA_P64], Vs[32 * RA_P64], KT[64 * RA_P32];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, il = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int nI = (N + MH_OWN - 1) / MH_OWN, C = H * 64, Mp = (M + 3) & ~3;
     const int ib = blockIdx.x % nI, bh = blockIdx.x / nI, h = bh % H, b = bh / H, i0 = ib * MH_OWN + wave * 32, i = i0 + il;
     const E* kb = k + (long)b * M * ldkv + h * 64;
@@ -319,14 +323,15 @@ template <typename E>
 __global__ __launch_bounds__(MH_THREADS, 2) void mh_bwd_kv_kernel(const E* __restrict__ dout, const E* __restrict__ q, long ldq, const E* __restrict__ k,
                                                                   const E* __restrict__ v, long ldkv, const unsigned char* __restrict__ mask,
                                                                   const float* __restrict__ lse, const float* __restrict__ dsum, float keep_scale,
-                                                                  uint32_t thr, uint64_t seed, uint64_t offset, E* __restrict__ dk, E* __restrict__ dv,
-                                                                  int N, int M, int H)
+                                                                  uint32_t thr, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state,
+                                                                  E* __restrict__ dk, E* __restrict__ dv, int N, int M, int H)
 {
     using V = typename Ra<E>::V;
     __shared__ __attribute__((aligned(16))) ra_u16 Qs[32 * RA_P64], dOs[32 * RA_P64], QT[64 * RA_P32], dOT[64 * RA_P32];
     __shared__ __attribute__((aligned(16))) unsigned char kbs[MH_WAVES][1024];
     __shared__ float Dl[32], Ll[32];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, jl = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int nJ = (M + MH_OWN - 1) / MH_OWN, C = H * 64, Mp = (M + 3) & ~3;
     const int jb = blockIdx.x % nJ, bh = blockIdx.x / nJ, h = bh % H, b = bh / H, j0 = jb * MH_OWN + wave * 32, j = j0 + jl;
     const E* qb = q + (long)b * N * ldq + h * 64;
@@ -411,11 +416,11 @@ using namespace dsp;
 
 #define MH_DISPATCH(dtype, ...) DSP_DISPATCH_ELEM_16(dtype, E, __VA_ARGS__)
 
-extern "C" int dsp_mha_train_fwd(const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask, float keep_scale,
-                                 unsigned int thr, uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype, int B, int N, int M, int H,
-                                 dsp_stream_t stream)
+static int mh_fwd(const char* who, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask, float keep_scale,
+                  unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* out, float* lse, int act_dtype, int B, int N,
+                  int M, int H, dsp_stream_t stream)
 {
-    const char* who = "mha_train_fwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = mh_check(who, act_dtype, B, N, M, H, ldq, ldkv, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!q || !k || !v || !out || !lse || out == q || out == k || out == v || (const void*)lse == q || (const void*)lse == k || (const void*)lse == v ||
@@ -428,8 +433,23 @@ extern "C" int dsp_mha_train_fwd(const void* q, long ldq, const void* k, const v
     const unsigned grid = (unsigned)((long)B * H * ((N + MH_OWN - 1) / MH_OWN));
     hipStream_t st = as_stream(stream);
     MH_DISPATCH(act_dtype, hipLaunchKernelGGL((mh_fwd_kernel<E>), dim3(grid), dim3(MH_THREADS), 0, st, (const E*)q, ldq, (const E*)k, (const E*)v, ldkv, pad_mask,
-                                              keep_scale, (uint32_t)thr, seed, offset, (E*)out, lse, N, M, H));
+                                              keep_scale, (uint32_t)thr, seed, offset, rng_state, (E*)out, lse, N, M, H));
     return check_launch(who);
+}
+
+extern "C" int dsp_mha_train_fwd(const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask, float keep_scale,
+                                 unsigned int thr, uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype, int B, int N, int M, int H,
+                                 dsp_stream_t stream)
+{
+    return mh_fwd("mha_train_fwd", q, ldq, k, v, ldkv, pad_mask, keep_scale, thr, seed, offset, nullptr, out, lse, act_dtype, B, N, M, H, stream);
+}
+
+extern "C" int dsp_mha_train_fwd_state(const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
+                                       float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype,
+                                       int B, int N, int M, int H, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return mh_fwd("mha_train_fwd_state", q, ldq, k, v, ldkv, pad_mask, keep_scale, thr, seed, offset, rng_state, out, lse, act_dtype, B, N, M, H,
+                  stream);
 }
 
 extern "C" size_t dsp_mha_train_workspace_bytes(int B, int N, int M, int H)
@@ -438,11 +458,11 @@ extern "C" size_t dsp_mha_train_workspace_bytes(int B, int N, int M, int H)
     return ((size_t)B * (size_t)H * (size_t)N * sizeof(float) + 15) & ~(size_t)15;      // D [B,H,N]
 }
 
-extern "C" int dsp_mha_train_bwd(const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
-                                 const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
-                                 void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream)
+static int mh_bwd(const char* who, const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
+                  const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dq,
+                  void* dk, void* dv, void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream)
 {
-    const char* who = "mha_train_bwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = mh_check(who, act_dtype, B, N, M, H, ldq, ldkv, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dq && !dk && !dv) return DSP_OK;
@@ -468,10 +488,28 @@ extern "C" int dsp_mha_train_bwd(const void* dout, const void* q, long ldq, cons
 #define MH_IN (const E*)dout, (const E*)q, ldq, (const E*)k, (const E*)v, ldkv, pad_mask, lse
     // the owner of the queries first: it forms D for both (without dq: its first walk only)
     MH_DISPATCH(act_dtype, hipLaunchKernelGGL((mh_bwd_q_kernel<E>), dim3((unsigned)((long)B * H * ((N + MH_OWN - 1) / MH_OWN))), dim3(MH_THREADS), 0, st, MH_IN,
-                                              keep_scale, (uint32_t)thr, seed, offset, dsum, (E*)dq, N, M, H));
+                                              keep_scale, (uint32_t)thr, seed, offset, rng_state, dsum, (E*)dq, N, M, H));
     if (dk || dv)
         MH_DISPATCH(act_dtype, hipLaunchKernelGGL((mh_bwd_kv_kernel<E>), dim3((unsigned)((long)B * H * ((M + MH_OWN - 1) / MH_OWN))), dim3(MH_THREADS), 0, st, MH_IN,
-                                                  (const float*)dsum, keep_scale, (uint32_t)thr, seed, offset, (E*)dk, (E*)dv, N, M, H));
+                                                  (const float*)dsum, keep_scale, (uint32_t)thr, seed, offset, rng_state, (E*)dk, (E*)dv, N, M,
+                                                  H));
 #undef MH_IN
     return check_launch(who);
+}
+
+extern "C" int dsp_mha_train_bwd(const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
+                                 const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
+                                 void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream)
+{
+    return mh_bwd("mha_train_bwd", dout, q, ldq, k, v, ldkv, pad_mask, lse, keep_scale, thr, seed, offset, nullptr, dq, dk, dv, workspace,
+                  workspace_bytes, act_dtype, B, N, M, H, stream);
+}
+
+extern "C" int dsp_mha_train_bwd_state(const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv,
+                                       const unsigned char* pad_mask, const float* lse, float keep_scale, unsigned int thr, uint64_t seed,
+                                       uint64_t offset, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes, int act_dtype, int B,
+                                       int N, int M, int H, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return mh_bwd("mha_train_bwd_state", dout, q, ldq, k, v, ldkv, pad_mask, lse, keep_scale, thr, seed, offset, rng_state, dq, dk, dv, workspace,
+                  workspace_bytes, act_dtype, B, N, M, H, stream);
 }

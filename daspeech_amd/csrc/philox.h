@@ -1,6 +1,8 @@
 // philox.h — the counter-based dropout mask of the training operators (residual_norm_train.hip, relpos_attention_train.hip).
 // Element e of a call's index space keeps its value when word (e & 3) of Philox4x32-10(counter = (e >> 2, offset), key = seed) has its top
 // 24 bits >= thr (thr = ceil(p * 2^24)); dsp_dropout_keep_mask writes the same flags as bytes.
+// (seed, offset) are host integers, or — the ..._state entries, for launches recorded into a graph — come from a device-resident state
+// {seed, offset} to which the host integer `offset` is the call's distance (philox_stream): a replay reads whatever the state holds then.
 #pragma once
 #include "common.h"
 
@@ -17,6 +19,13 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// The (seed, offset) a kernel uses: its arguments as they are when state is null; else seed = state[0] and offset = state[1] + offset (the
+// argument is then the call's distance from the state's offset, the seed argument is not used).  Called once at kernel entry: `state` is a
+// kernel argument, so this is one uniform 16-byte load per wave.  Nothing but dsp_dropout_state_advance writes a state.
+__device__ __forceinline__ void philox_stream(uint64_t& seed, uint64_t& offset, const uint64_t* __restrict__ state)
+{
+    if (state) { seed = state[0]; offset += state[1]; }
 }
 // keep flags of the V elements from element e on (e a multiple of 4)
 template <int V> __device__ __forceinline__ void keep_flags(uint64_t e, uint64_t seed, uint64_t offset, uint32_t thr, bool (&keep)[V])

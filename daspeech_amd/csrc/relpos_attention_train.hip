@@ -91,11 +91,13 @@ template <typename E>
 __global__ __launch_bounds__(64) void ra_fwd_kernel(const E* __restrict__ q, const E* __restrict__ k, const E* __restrict__ v, long ld,
                                                     const E* __restrict__ pos, const void* __restrict__ bu, const void* __restrict__ bv, int pdtype,
                                                     const unsigned char* __restrict__ mask, float keep_scale, uint32_t thr, uint64_t seed,
-                                                    uint64_t offset, E* __restrict__ out, float* __restrict__ lse, int T_, int H)
+                                                    uint64_t offset, const uint64_t* __restrict__ rng_state, E* __restrict__ out,
+                                                    float* __restrict__ lse, int T_, int H)
 {
     __shared__ __attribute__((aligned(16))) ra_u16 Qu[32 * RA_P64], Qv[32 * RA_P64], Ks[32 * RA_P64], Ps[64 * RA_P64], Vt[64 * RA_P32], Pp[32 * RA_P32];
     __shared__ float Gs[32 * RA_PG], bias[128];
     const int lane = threadIdx.x, jl = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int T = T_, nI = (T + 31) / 32, C = H * 64;
     const int ib = blockIdx.x % nI, bh = blockIdx.x / nI, h = bh % H, b = bh / H, i0 = ib * 32;
     const E* qb = q + (long)b * T * ld + h * 64;
@@ -208,7 +210,8 @@ __global__ __launch_bounds__(64) void ra_bwd_kv_kernel(const E* __restrict__ dou
                                                        const E* __restrict__ v, long ld, const E* __restrict__ pos, const void* __restrict__ bu,
                                                        const void* __restrict__ bv, int pdtype, const unsigned char* __restrict__ mask,
                                                        const E* __restrict__ out, const float* __restrict__ lse, float keep_scale, uint32_t thr,
-                                                       uint64_t seed, uint64_t offset, E* __restrict__ dk, E* __restrict__ dv, int T_, int H)
+                                                       uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state, E* __restrict__ dk,
+                                                       E* __restrict__ dv, int T_, int H)
 {
     __shared__ __attribute__((aligned(16))) ra_u16 Qu[32 * RA_P64], Qv[32 * RA_P64], Ks[32 * RA_P64], Vs[32 * RA_P64], dOs[32 * RA_P64], Ps[64 * RA_P64],
         QuT[64 * RA_P32], dOT[64 * RA_P32];
@@ -220,6 +223,7 @@ __global__ __launch_bounds__(64) void ra_bwd_kv_kernel(const E* __restrict__ dou
     ra_u16* dST = PmT + 32 * RA_P32;
     static_assert(2 * 32 * RA_P32 * sizeof(ra_u16) <= 32 * RA_PG * sizeof(float), "both tiles fit the scratch");
     const int lane = threadIdx.x, jl = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int T = T_, nI = (T + 31) / 32, C = H * 64;
     const int jb = blockIdx.x % nI, bh = blockIdx.x / nI, h = bh % H, b = bh / H, j0 = jb * 32;
     const E* qb = q + (long)b * T * ld + h * 64;
@@ -269,13 +273,14 @@ __global__ __launch_bounds__(64) void ra_bwd_q_kernel(const E* __restrict__ dout
                                                       const E* __restrict__ v, long ld, const E* __restrict__ pos, const void* __restrict__ bu,
                                                       const void* __restrict__ bv, int pdtype, const unsigned char* __restrict__ mask,
                                                       const E* __restrict__ out, const float* __restrict__ lse, float keep_scale, uint32_t thr,
-                                                      uint64_t seed, uint64_t offset, E* __restrict__ dq, float* __restrict__ part_u,
-                                                      float* __restrict__ part_v, int T_, int H)
+                                                      uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state, E* __restrict__ dq,
+                                                      float* __restrict__ part_u, float* __restrict__ part_v, int T_, int H)
 {
     __shared__ __attribute__((aligned(16))) ra_u16 Qu[32 * RA_P64], Qv[32 * RA_P64], Ks[32 * RA_P64], Vs[32 * RA_P64], dOs[32 * RA_P64], Ps[64 * RA_P64],
         KT[64 * RA_P32], PosT[64 * RA_P64], dSs[32 * RA_P32], dG[32 * RA_P64];
     __shared__ float Gs[32 * RA_PG], bias[128], Dl[32], Ll[32];
     const int lane = threadIdx.x, jl = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int T = T_, nI = (T + 31) / 32, C = H * 64;
     const int ib = blockIdx.x % nI, bh = blockIdx.x / nI, h = bh % H, b = bh / H, i0 = ib * 32;
     const E* qb = q + (long)b * T * ld + h * 64;
@@ -343,12 +348,14 @@ __global__ __launch_bounds__(64) void ra_bwd_pos_kernel(const E* __restrict__ do
                                                         const E* __restrict__ v, long ld, const E* __restrict__ pos, const void* __restrict__ bu,
                                                         const void* __restrict__ bv, int pdtype, const unsigned char* __restrict__ mask,
                                                         const E* __restrict__ out, const float* __restrict__ lse, float keep_scale, uint32_t thr,
-                                                        uint64_t seed, uint64_t offset, float* __restrict__ part_pos, int T_, int H)
+                                                        uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state,
+                                                        float* __restrict__ part_pos, int T_, int H)
 {
     __shared__ __attribute__((aligned(16))) ra_u16 Qu[32 * RA_P64], Qv[32 * RA_P64], Ks[32 * RA_P64], Vs[32 * RA_P64], dOs[32 * RA_P64], Ps[64 * RA_P64],
         QvT[64 * RA_P32], dGT[32 * RA_P32];
     __shared__ float Gs[32 * RA_PG], bias[128], Dl[32], Ll[32];
     const int lane = threadIdx.x, jl = lane & 31, hi = lane >> 5;
+    philox_stream(seed, offset, rng_state);
     const int T = T_, NP = 2 * T - 1, nR = (NP + 31) / 32, C = H * 64;
     const int rbk = blockIdx.x % nR, bh = blockIdx.x / nR, h = bh % H, b = bh / H, r0 = rbk * 32;
     const E* qb = q + (long)b * T * ld + h * 64;
@@ -458,12 +465,11 @@ extern "C" size_t dsp_relpos_attention_train_workspace_bytes(int B, int T, int H
     return (floats * sizeof(float) + 15) & ~(size_t)15;
 }
 
-extern "C" int dsp_relpos_attention_train_fwd(const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
-                                              const void* bias_v, const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed,
-                                              uint64_t offset, void* out, float* lse, int act_dtype, int param_dtype, int B, int T, int H,
-                                              dsp_stream_t stream)
+static int ra_fwd(const char* who, const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u, const void* bias_v,
+                  const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state,
+                  void* out, float* lse, int act_dtype, int param_dtype, int B, int T, int H, dsp_stream_t stream)
 {
-    const char* who = "relpos_attention_train_fwd";
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = ra_check(who, act_dtype, param_dtype, B, T, H, ld);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!q || !k || !v || !pos || !bias_u || !bias_v || !out || !lse || out == q || out == k || out == v || out == pos) {
@@ -477,17 +483,35 @@ extern "C" int dsp_relpos_attention_train_fwd(const void* q, const void* k, cons
     const unsigned grid = (unsigned)((long)B * H * ((T + 31) / 32));
     hipStream_t st = as_stream(stream);
     RA_DISPATCH(act_dtype, hipLaunchKernelGGL((ra_fwd_kernel<E>), dim3(grid), dim3(64), 0, st, (const E*)q, (const E*)k, (const E*)v, ld, (const E*)pos,
-                                              bias_u, bias_v, param_dtype, pad_mask, keep_scale, (uint32_t)thr, seed, offset, (E*)out, lse, T, H));
+                                              bias_u, bias_v, param_dtype, pad_mask, keep_scale, (uint32_t)thr, seed, offset, rng_state, (E*)out, lse,
+                                              T, H));
     return check_launch(who);
 }
 
-extern "C" int dsp_relpos_attention_train_bwd(const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos,
-                                              const void* bias_u, const void* bias_v, const unsigned char* pad_mask, const void* out, const float* lse,
-                                              float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
-                                              void* dpos, void* dbias_u, void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype,
-                                              int param_dtype, int B, int T, int H, dsp_stream_t stream)
+extern "C" int dsp_relpos_attention_train_fwd(const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
+                                              const void* bias_v, const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed,
+                                              uint64_t offset, void* out, float* lse, int act_dtype, int param_dtype, int B, int T, int H,
+                                              dsp_stream_t stream)
 {
-    const char* who = "relpos_attention_train_bwd";
+    return ra_fwd("relpos_attention_train_fwd", q, k, v, ld, pos, bias_u, bias_v, pad_mask, keep_scale, thr, seed, offset, nullptr, out, lse,
+                  act_dtype, param_dtype, B, T, H, stream);
+}
+
+extern "C" int dsp_relpos_attention_train_fwd_state(const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
+                                                    const void* bias_v, const unsigned char* pad_mask, float keep_scale, unsigned int thr,
+                                                    uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype, int param_dtype, int B,
+                                                    int T, int H, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return ra_fwd("relpos_attention_train_fwd_state", q, k, v, ld, pos, bias_u, bias_v, pad_mask, keep_scale, thr, seed, offset, rng_state, out, lse,
+                  act_dtype, param_dtype, B, T, H, stream);
+}
+
+static int ra_bwd(const char* who, const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
+                  const void* bias_v, const unsigned char* pad_mask, const void* out, const float* lse, float keep_scale, unsigned int thr,
+                  uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dq, void* dk, void* dv, void* dpos, void* dbias_u, void* dbias_v,
+                  void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H, dsp_stream_t stream)
+{
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int rc = ra_check(who, act_dtype, param_dtype, B, T, H, ld);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dq && !dk && !dv && !dpos && !dbias_u && !dbias_v) return DSP_OK;
@@ -518,7 +542,7 @@ extern "C" int dsp_relpos_attention_train_bwd(const void* dout, const void* q, c
     float* part_pos = part_u ? part_v + ra_part_bias_floats(B, T, H) : nullptr;
     hipStream_t st = as_stream(stream);
 #define RA_IN (const E*)dout, (const E*)q, (const E*)k, (const E*)v, ld, (const E*)pos, bias_u, bias_v, param_dtype, pad_mask, (const E*)out, lse, keep_scale, \
-              (uint32_t)thr, seed, offset
+              (uint32_t)thr, seed, offset, rng_state
     if (dk || dv)
         RA_DISPATCH(act_dtype, hipLaunchKernelGGL((ra_bwd_kv_kernel<E>), dim3((unsigned)((long)B * H * nI)), dim3(64), 0, st, RA_IN, (E*)dk, (E*)dv, T, H));
     if (dq || dbias_u || dbias_v) {
@@ -535,4 +559,25 @@ extern "C" int dsp_relpos_attention_train_bwd(const void* dout, const void* q, c
     }
 #undef RA_IN
     return check_launch(who);
+}
+
+extern "C" int dsp_relpos_attention_train_bwd(const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos,
+                                              const void* bias_u, const void* bias_v, const unsigned char* pad_mask, const void* out, const float* lse,
+                                              float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
+                                              void* dpos, void* dbias_u, void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype,
+                                              int param_dtype, int B, int T, int H, dsp_stream_t stream)
+{
+    return ra_bwd("relpos_attention_train_bwd", dout, q, k, v, ld, pos, bias_u, bias_v, pad_mask, out, lse, keep_scale, thr, seed, offset, nullptr, dq,
+                  dk, dv, dpos, dbias_u, dbias_v, workspace, workspace_bytes, act_dtype, param_dtype, B, T, H, stream);
+}
+
+extern "C" int dsp_relpos_attention_train_bwd_state(const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos,
+                                                    const void* bias_u, const void* bias_v, const unsigned char* pad_mask, const void* out,
+                                                    const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq,
+                                                    void* dk, void* dv, void* dpos, void* dbias_u, void* dbias_v, void* workspace,
+                                                    size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H,
+                                                    const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return ra_bwd("relpos_attention_train_bwd_state", dout, q, k, v, ld, pos, bias_u, bias_v, pad_mask, out, lse, keep_scale, thr, seed, offset,
+                  rng_state, dq, dk, dv, dpos, dbias_u, dbias_v, workspace, workspace_bytes, act_dtype, param_dtype, B, T, H, stream);
 }

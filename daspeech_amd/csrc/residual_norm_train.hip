@@ -32,9 +32,11 @@ template <typename T, int NG>
 __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, const T* __restrict__ res, const void* __restrict__ bias,
                                                      const void* __restrict__ gamma, const void* __restrict__ beta, int pdtype, float eps,
                                                      float alpha, float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset,
-                                                     T* __restrict__ s_out, T* __restrict__ y, float* __restrict__ stats, long R, int C, int W)
+                                                     const uint64_t* __restrict__ rng_state, T* __restrict__ s_out, T* __restrict__ y,
+                                                     float* __restrict__ stats, long R, int C, int W)
 {
     constexpr int V = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rpw = 64 / W, sub = lane / W, l = lane % W, G = C / V;
     const float invC = 1.f / (float)C;
@@ -122,10 +124,12 @@ __global__ __launch_bounds__(256) void rn_fwd_kernel(const T* __restrict__ h, co
 template <typename T, int NG>
 __global__ __launch_bounds__(256) void rn_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ ds, const T* __restrict__ s,
                                                      const float* __restrict__ stats, const void* __restrict__ gamma, int pdtype, float alpha,
-                                                     float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset, T* __restrict__ dh,
-                                                     T* __restrict__ dres, float* __restrict__ part, int want_dh, long R, int C, int W)
+                                                     float keep_scale, uint32_t thr, uint64_t seed, uint64_t offset,
+                                                     const uint64_t* __restrict__ rng_state, T* __restrict__ dh, T* __restrict__ dres,
+                                                     float* __restrict__ part, int want_dh, long R, int C, int W)
 {
     constexpr int V = elems16<T>;
+    philox_stream(seed, offset, rng_state);
     __shared__ float red[RN_WAVES][NG * 64 * V];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rpw = 64 / W, sub = lane / W, l = lane % W, G = C / V;
@@ -260,8 +264,10 @@ __global__ __launch_bounds__(256) void rn_bwd_merge_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- the mask alone, as bytes
-__global__ __launch_bounds__(256) void rn_keep_mask_kernel(uint64_t seed, uint64_t offset, uint32_t thr, unsigned char* __restrict__ out, long n)
+__global__ __launch_bounds__(256) void rn_keep_mask_kernel(uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rng_state, uint32_t thr,
+                                                           unsigned char* __restrict__ out, long n)
 {
+    philox_stream(seed, offset, rng_state);
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     if (4 * g >= n) return;
     bool keep[4];
@@ -270,11 +276,18 @@ __global__ __launch_bounds__(256) void rn_keep_mask_kernel(uint64_t seed, uint64
         if (4 * g + i < n) out[4 * g + i] = keep[i] ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- state[1] += by: the one kernel that writes a dropout state
+__global__ void rn_state_advance_kernel(uint64_t* __restrict__ state, uint64_t by)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[1] += by;
+}
+
 static long rn_chunks(long R) { return (R + RN_CHUNK - 1) / RN_CHUNK; }
 
 // what both entry points check; 1: nothing to do (R == 0), 0: go on, < 0: refused
-static int rn_check(const char* who, int act_dtype, int param_dtype, long R, int C)
+static int rn_check(const char* who, int act_dtype, int param_dtype, long R, int C, const uint64_t* rng_state)
 {
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     const int es = elem_size(act_dtype);
     if (!es || !elem_size(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (h, residual, s, y and their gradients) / %d (gamma, beta, bias: the same, or fp32)", who, act_dtype, param_dtype);
@@ -316,12 +329,11 @@ extern "C" size_t dsp_resnorm_train_workspace_bytes(int64_t R, int C)
     return ((size_t)rn_chunks((long)R) * 3 * (size_t)C * sizeof(float) + 15) & ~(size_t)15;
 }
 
-extern "C" int dsp_resnorm_train_fwd(const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
-                                     float alpha, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* s, void* y,
-                                     float* stats, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream)
+static int rn_fwd(const char* who, const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
+                  float alpha, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* s, void* y,
+                  float* stats, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream)
 {
-    const char* who = "resnorm_train_fwd";
-    const int rc = rn_check(who, act_dtype, param_dtype, (long)R, C);
+    const int rc = rn_check(who, act_dtype, param_dtype, (long)R, C, rng_state);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!residual || !gamma || !beta || !y || !stats || (h && !s) || y == residual || y == h || (h && (s == residual || s == h || s == y))) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
@@ -337,17 +349,34 @@ extern "C" int dsp_resnorm_train_fwd(const void* h, const void* residual, const 
     const unsigned grid = (unsigned)((R + rows_per_wg - 1) / rows_per_wg);
     hipStream_t st = as_stream(stream);
     RN_DISPATCH(act_dtype, NG, hipLaunchKernelGGL((rn_fwd_kernel<E, NGC>), dim3(grid), dim3(256), 0, st, (const E*)h, (const E*)residual, bias, gamma,
-                                                  beta, param_dtype, eps, alpha, keep_scale, (uint32_t)thr, seed, offset, (E*)s, (E*)y, stats, (long)R, C, W));
+                                                  beta, param_dtype, eps, alpha, keep_scale, (uint32_t)thr, seed, offset, rng_state, (E*)s, (E*)y, stats,
+                                                  (long)R, C, W));
     return check_launch(who);
 }
 
-extern "C" int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha,
-                                     float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dresidual, void* dbias,
-                                     void* dgamma, void* dbeta, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype,
-                                     int64_t R, int C, dsp_stream_t stream)
+extern "C" int dsp_resnorm_train_fwd(const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
+                                     float alpha, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* s, void* y,
+                                     float* stats, int act_dtype, int param_dtype, int64_t R, int C, dsp_stream_t stream)
 {
-    const char* who = "resnorm_train_bwd";
-    const int rc = rn_check(who, act_dtype, param_dtype, (long)R, C);
+    return rn_fwd("resnorm_train_fwd", h, residual, bias, gamma, beta, eps, alpha, keep_scale, thr, seed, offset, nullptr, s, y, stats, act_dtype,
+                  param_dtype, R, C, stream);
+}
+
+extern "C" int dsp_resnorm_train_fwd_state(const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
+                                           float alpha, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* s, void* y,
+                                           float* stats, int act_dtype, int param_dtype, int64_t R, int C, const uint64_t* rng_state,
+                                           dsp_stream_t stream)
+{
+    return rn_fwd("resnorm_train_fwd_state", h, residual, bias, gamma, beta, eps, alpha, keep_scale, thr, seed, offset, rng_state, s, y, stats,
+                  act_dtype, param_dtype, R, C, stream);
+}
+
+static int rn_bwd(const char* who, const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha,
+                  float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dh, void* dresidual,
+                  void* dbias, void* dgamma, void* dbeta, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R, int C,
+                  dsp_stream_t stream)
+{
+    const int rc = rn_check(who, act_dtype, param_dtype, (long)R, C, rng_state);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dh && !dresidual && !dbias && !dgamma && !dbeta) return DSP_OK;
     if ((dy && (!s || !stats || !gamma)) || (dh && (dh == dy || dh == ds || dh == s || dh == dresidual)) ||
@@ -370,20 +399,59 @@ extern "C" int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void*
     float* part = sums ? (float*)workspace : (float*)nullptr;
     hipStream_t st = as_stream(stream);
     RN_DISPATCH(act_dtype, NG, hipLaunchKernelGGL((rn_bwd_kernel<E, NGC>), dim3((unsigned)nchunks), dim3(256), 0, st, (const E*)dy, (const E*)ds,
-                                                  (const E*)s, stats, gamma, param_dtype, alpha, keep_scale, (uint32_t)thr, seed, offset, (E*)dh,
-                                                  (E*)dresidual, part, (dh || dbias) ? 1 : 0, (long)R, C, W));
+                                                  (const E*)s, stats, gamma, param_dtype, alpha, keep_scale, (uint32_t)thr, seed, offset, rng_state,
+                                                  (E*)dh, (E*)dresidual, part, (dh || dbias) ? 1 : 0, (long)R, C, W));
     if (sums)
         hipLaunchKernelGGL(rn_bwd_merge_kernel, dim3((unsigned)((3 * C + 63) / 64)), dim3(256), 0, st, part, nchunks, dgamma, dbeta, dbias, param_dtype, C);
     return check_launch(who);
 }
 
-extern "C" int dsp_dropout_keep_mask(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, dsp_stream_t stream)
+extern "C" int dsp_resnorm_train_bwd(const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha,
+                                     float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dresidual, void* dbias,
+                                     void* dgamma, void* dbeta, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype,
+                                     int64_t R, int C, dsp_stream_t stream)
 {
-    const char* who = "dropout_keep_mask";
+    return rn_bwd("resnorm_train_bwd", dy, ds, s, stats, gamma, alpha, keep_scale, thr, seed, offset, nullptr, dh, dresidual, dbias, dgamma, dbeta,
+                  workspace, workspace_bytes, act_dtype, param_dtype, R, C, stream);
+}
+
+extern "C" int dsp_resnorm_train_bwd_state(const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha,
+                                           float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dresidual,
+                                           void* dbias, void* dgamma, void* dbeta, void* workspace, size_t workspace_bytes, int act_dtype,
+                                           int param_dtype, int64_t R, int C, const uint64_t* rng_state, dsp_stream_t stream)
+{
+    return rn_bwd("resnorm_train_bwd_state", dy, ds, s, stats, gamma, alpha, keep_scale, thr, seed, offset, rng_state, dh, dresidual, dbias, dgamma,
+                  dbeta, workspace, workspace_bytes, act_dtype, param_dtype, R, C, stream);
+}
+
+static int rn_keep_mask(const char* who, uint64_t seed, uint64_t offset, const uint64_t* rng_state, unsigned int thr, unsigned char* out, int64_t n,
+                        dsp_stream_t stream)
+{
+    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
     if (n < 0 || n > (1L << 36) || thr > (1u << 24)) { set_error("%s: bad arguments n=%ld thr=%u", who, (long)n, thr); return DSP_EINVAL; }
     if (n == 0) return DSP_OK;
     if (!out) { set_error("%s: null pointer", who); return DSP_EINVAL; }
     const long groups = (n + 3) / 4;
-    hipLaunchKernelGGL(rn_keep_mask_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, as_stream(stream), seed, offset, (uint32_t)thr, out, (long)n);
+    hipLaunchKernelGGL(rn_keep_mask_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, as_stream(stream), seed, offset, rng_state,
+                       (uint32_t)thr, out, (long)n);
+    return check_launch(who);
+}
+
+extern "C" int dsp_dropout_keep_mask(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, dsp_stream_t stream)
+{
+    return rn_keep_mask("dropout_keep_mask", seed, offset, nullptr, thr, out, n, stream);
+}
+
+extern "C" int dsp_dropout_keep_mask_state(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, const uint64_t* rng_state,
+                                           dsp_stream_t stream)
+{
+    return rn_keep_mask("dropout_keep_mask_state", seed, offset, rng_state, thr, out, n, stream);
+}
+
+extern "C" int dsp_dropout_state_advance(uint64_t* rng_state, uint64_t by, dsp_stream_t stream)
+{
+    const char* who = "dropout_state_advance";
+    if (!rng_state || ((uintptr_t)rng_state & 7)) { set_error("%s: rng_state must be a non-null, 8-byte aligned pointer", who); return DSP_EINVAL; }
+    hipLaunchKernelGGL(rn_state_advance_kernel, dim3(1), dim3(64), 0, as_stream(stream), rng_state, by);
     return check_launch(who);
 }

@@ -24,7 +24,9 @@ Host-side mirror of the reference code these replace:
   residual_dropout_layer_norm_autograd   the residual sites of the layers in TRAINING mode, s = residual + alpha * dropout(h [+ bias]); y = LayerNorm(s)
                       (fairseq conformer_layer.py:254-281, transformer_layer.py:467-511, fastspeech2.py:42-95), under autograd
                       (csrc/residual_norm_train.hip): fp32 / fp16 / bf16, the mask recomputed from a Philox counter keyed by the default CUDA
-                      generator, column sums in a fixed order without float atomics; ConformerLayer / NATDecoderLayer / FFTLayer keep their
+                      generator — or, inside DropoutState.draws(), by the dropout state on the device, which is what lets a captured graph
+                      (torch.cuda.graph) run this operator and the five below that draw masks, with new masks on every replay —, column sums in a
+                      fixed order without float atomics; ConformerLayer / NATDecoderLayer / FFTLayer keep their
                       torch lines where residual_dropout_layer_norm_served says no (set_residual_norm_hip(False): always);
                       residual_dropout_layer_norm_checked / _sites_served are internal to those layers (no argument checks: not an API)
   bias_act_dropout_autograd   the element-wise pass between the two GEMMs of a feed-forward block in TRAINING mode, y = dropout(act(h + bias))
@@ -89,7 +91,8 @@ caller's torch lines run; the alignment gates of the C ABI are never reached wit
 The training operators share one host layer: each states its dtype / shape / layout rule once, in a _..._problem() function
 that returns None or the reason — the ..._served() predicate asks it behind the switch and autocast gates, the raising ..._autograd() function
 raises the reason (_settled: after a dense copy where the reason begins with _LAYOUT) — and every autograd.Function launches through _launch
-(device, raw stream, return code), with _dropout_call / _dropout_thr_scale for the generator bookkeeping, _row_pitch for row-pitched views, the
+(device, raw stream, return code), with _dropout_call / _dropout_thr_scale for the generator bookkeeping (DropoutState / _masked where the
+random state lives on the device: graph capture), _row_pitch for row-pitched views, the
 dtype tables _FLOAT_CODES / _HALF_CODES, _ptr and _workspace.
 """
 import ctypes
@@ -101,6 +104,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .dropout_state import (DropoutState, _DRAWS, _NOT_GPU_DEVICE, _StateDraws, _active_dropout_state, _capture_ok, _capturing,      # the dropout state on
+                            _device_index)                                                                                       # the device: public here
 
 
 _NOT_GPU = "expected GPU tensors (HIP op, no CPU path)"
@@ -176,10 +181,6 @@ def _ptr(t: Optional[Tensor]) -> Optional[int]:
 
 def _workspace(dev, nbytes: int) -> Optional[Tensor]:
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-
-
-def _capturing() -> bool:
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 def _launch(dev, entry, *args) -> None:
@@ -1239,12 +1240,27 @@ def _reserve_dropout_stream(device) -> Tuple[int, int]:
     return seed & 0xFFFFFFFFFFFFFFFF, offset
 
 
-def _dropout_call(p: float, training: bool, device) -> Tuple[float, int, int]:
+def _dropout_call(p: float, training: bool, device):
     """(p_eff, seed, offset) of one call of a training operator: dropout is active with `training and p > 0`, and only then is a (seed, offset)
-    reserved (the generator's offset moves on by 4, else by nothing)"""
+    reserved (the generator's offset moves on by 4, else by nothing).  Inside DropoutState.draws() on that device the pair is
+    (_StateDraws, intra) instead — the state on the device and the call's distance from its offset; the generator is not touched."""
     p_eff = float(p) if training else 0.0
-    seed, offset = _reserve_dropout_stream(device) if p_eff > 0.0 else (0, 0)
-    return p_eff, seed, offset
+    if p_eff > 0.0:
+        if _DRAWS:
+            st = _DRAWS.get(_device_index(device))
+            if st is not None:
+                return (p_eff,) + st._reserve()
+        seed, offset = _reserve_dropout_stream(device)
+        return p_eff, seed, offset
+    return p_eff, 0, 0
+
+
+def _masked(lib, name: str, seed, offset) -> tuple:
+    """(entry, seed, offset, tail) of a masked launch: the entry `name` with host integers; for a _StateDraws the entry name_state with
+    (0, intra) and the state pointer as the tail — the argument before the stream.  Raises when the scope that reserved the call has exited."""
+    if seed.__class__ is _StateDraws:
+        return getattr(lib, name + "_state"), 0, offset, (seed.pointer(),)
+    return getattr(lib, name), seed, offset, ()
 
 
 def _dropout_thr_scale(p: float) -> Tuple[int, float]:
@@ -1253,17 +1269,24 @@ def _dropout_thr_scale(p: float) -> Tuple[int, float]:
     return thr, (1.0 / (1.0 - p) if thr else 1.0)
 
 
-def dropout_keep_mask(seed: int, offset: int, p: float, shape, device) -> Tensor:
+def dropout_keep_mask(seed, offset: int, p: float, shape, device=None) -> Tensor:
     """The keep mask (bool, `shape`) that residual_dropout_layer_norm_autograd applies for (seed, offset, p) to a contiguous tensor of that
-    shape (dsp_dropout_keep_mask): for tests and diagnostics — the operator itself stores no mask."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("dropout_keep_mask: expected a GPU device (HIP op, no CPU path)")
-    lib = _lib.load()
+    shape (dsp_dropout_keep_mask): for tests and diagnostics — the operator itself stores no mask.  The device form takes a DropoutState in
+    place of the seed and an intra in place of the offset, dropout_keep_mask(state, intra, p, shape): the mask for seed = state[0],
+    offset = state[1] + intra, read on the device when the launch runs (dsp_dropout_keep_mask_state) — the one a masked call that reserved
+    `intra` inside state.draws() applies; it works inside and outside a scope and does not move the state."""
+    if isinstance(seed, DropoutState):
+        device, tail = seed.device, (_lib.ptr(seed.tensor),)
+        entry, name, seed = _lib.load().dsp_dropout_keep_mask_state, "dsp_dropout_keep_mask_state", 0
+    else:
+        device, tail = torch.device(device), ()
+        if device.type != "cuda":
+            raise RuntimeError(f"dropout_keep_mask: {_NOT_GPU_DEVICE}")
+        entry, name = _lib.load().dsp_dropout_keep_mask, "dsp_dropout_keep_mask"
     with torch.cuda.device(device):
         out = torch.empty(tuple(shape), dtype=torch.uint8, device=device)
-        _lib.check(lib.dsp_dropout_keep_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), dropout_threshold(p), _lib.ptr(out), out.numel(),
-                                             _lib.current_stream_handle()), "dsp_dropout_keep_mask")
+        _lib.check(entry(int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), dropout_threshold(p), _lib.ptr(out), out.numel(), *tail,
+                         _lib.current_stream_handle()), name)
     return out.view(torch.bool)
 
 
@@ -1309,11 +1332,13 @@ def _resnorm_problem(h, residual, ln, bias) -> Optional[str]:
     return None
 
 
-def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln: "torch.nn.LayerNorm", *, bias: Optional[Tensor] = None) -> bool:
+def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln: "torch.nn.LayerNorm", *, bias: Optional[Tensor] = None,
+                                       masked: Optional[bool] = None) -> bool:
     """True when residual_dropout_layer_norm_autograd serves a training branch on these arguments: the switch is on, autocast off, residual
     (and h, when given: same shape, dtype and device) a contiguous GPU tensor [..., C] in fp32 / fp16 / bf16 with C a multiple of the elements
     in 16 bytes, C <= 2048 and at most 2^24 rows, ln an affine LayerNorm(C) whose weight and bias (and `bias`) are in that dtype or all in
-    fp32, and the current stream not capturing a graph (the random offset is reserved on the host).  Everything else keeps the torch lines."""
+    fp32; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training) — `masked` left at None means "h is given": the call of this very question; a caller that asks with h = None as a stand-in for an h it
+    has yet to make dense says what its call will draw.  Everything else keeps the torch lines."""
     if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
         return False
     if _resnorm_problem(h, residual, ln, bias) is not None:
@@ -1322,13 +1347,13 @@ def residual_dropout_layer_norm_served(h: Optional[Tensor], residual: Tensor, ln
         return False
     if not _on_grid(residual, h, ln.weight, ln.bias, bias if h is not None else None):         # 16-byte loads of every one of them
         return False
-    return not _capturing()
+    return _capture_ok(residual.device, h is not None if masked is None else masked)
 
 
-def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
+def residual_dropout_layer_norm_sites_served(x: Tensor, sites, masked: bool = True) -> bool:
     """residual_dropout_layer_norm_served(x, x, ln, bias=bias) for every (ln, bias) of `sites` — the residual sites of ONE layer, whose block
     outputs have the shape, dtype and device of the layer input x — with the questions about x, the switch, autocast and the stream asked
-    once: a layer asks this once per forward, and the step follows the host time of these sites."""
+    once: a layer asks this once per forward, and the step follows the host time of these sites.  `masked` as there."""
     if not RESIDUAL_NORM_HIP or torch.is_autocast_enabled():
         return False
     dt = x.dtype
@@ -1340,7 +1365,7 @@ def residual_dropout_layer_norm_sites_served(x: Tensor, sites) -> bool:
         if not (_resnorm_param_dtypes_ok(w, b, bias, dt) and _resnorm_param_shapes_ok(ln.normalized_shape, w, b, bias, C, dev)
                 and _on_grid(w, b, bias)):
             return False
-    return not _capturing()
+    return _capture_ok(dev, masked)
 
 
 class _ResidualNormTrainFn(torch.autograd.Function):
@@ -1359,9 +1384,10 @@ class _ResidualNormTrainFn(torch.autograd.Function):
         y = torch.empty_like(residual)
         s = torch.empty_like(residual) if has_h else None
         stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
-        _launch(dev, lib.dsp_resnorm_train_fwd, h.data_ptr() if has_h else None, residual.data_ptr(), bias.data_ptr() if has_bias else None,
-                gamma.data_ptr(), beta.data_ptr(), eps, alpha, scale, thr, seed, offset, s.data_ptr() if has_h else None, y.data_ptr(),
-                stats.data_ptr(), _FLOAT_CODES[residual.dtype], _FLOAT_CODES[gamma.dtype], R, C)
+        entry, sd, off, tail = _masked(lib, "dsp_resnorm_train_fwd", seed, offset)
+        _launch(dev, entry, h.data_ptr() if has_h else None, residual.data_ptr(), bias.data_ptr() if has_bias else None,
+                gamma.data_ptr(), beta.data_ptr(), eps, alpha, scale, thr, sd, off, s.data_ptr() if has_h else None, y.data_ptr(),
+                stats.data_ptr(), _FLOAT_CODES[residual.dtype], _FLOAT_CODES[gamma.dtype], R, C, *tail)
         ctx.save_for_backward(s if has_h else residual, stats, gamma)
         ctx.call = (alpha, scale, thr, seed, offset, has_h, has_bias)
         ctx.set_materialize_grads(False)
@@ -1402,9 +1428,10 @@ class _ResidualNormTrainFn(torch.autograd.Function):
         nbytes = int(lib.dsp_resnorm_train_workspace_bytes(R, C)) if sums else 0
         ws = _workspace(dev, nbytes)
         if dh is not None or dres is not None or sums:
-            _launch(dev, lib.dsp_resnorm_train_bwd, _ptr(dy), _ptr(ds), s.data_ptr(), stats.data_ptr(), g.data_ptr(), alpha, scale, thr, seed,
-                    offset, _ptr(dh), _ptr(dres), _ptr(dbias), _ptr(kg), _ptr(kb), _ptr(ws), nbytes, _FLOAT_CODES[s.dtype],
-                    _FLOAT_CODES[g.dtype], R, C)
+            entry, sd, off, tail = _masked(lib, "dsp_resnorm_train_bwd", seed, offset)
+            _launch(dev, entry, _ptr(dy), _ptr(ds), s.data_ptr(), stats.data_ptr(), g.data_ptr(), alpha, scale, thr, sd,
+                    off, _ptr(dh), _ptr(dres), _ptr(dbias), _ptr(kg), _ptr(kb), _ptr(ws), nbytes, _FLOAT_CODES[s.dtype],
+                    _FLOAT_CODES[g.dtype], R, C, *tail)
         return (dres if shared else dh), dres, dbias, dgamma, dbeta, None, None, None, None, None
 
 
@@ -1492,24 +1519,23 @@ def _actdrop_problem(h, bias, act) -> Optional[str]:
     return None
 
 
-def bias_act_dropout_served(h: Tensor, bias: Optional[Tensor], act: str) -> bool:
+def bias_act_dropout_served(h: Tensor, bias: Optional[Tensor], act: str, masked: bool = True) -> bool:
     """True when bias_act_dropout_autograd serves a training branch on these arguments as they are: the switch is on, autocast off, h a GPU
     tensor [..., Cin] in fp32 / fp16 / bf16 with Cin a multiple of the elements in 16 bytes (twice that with glu) and at most 8192, unit
     column stride, rows one common pitch apart (a multiple of those elements) and a 16-byte aligned start, bias None or [Cin] contiguous and
-    aligned in that dtype or fp32 on the same device, `act` one of ACT_CODES, and the current stream not capturing a graph (the random offset
-    is reserved on the host).  Everything else — CPU tensors, float64, another layout, an unknown activation — keeps the torch lines."""
+    aligned in that dtype or fp32 on the same device, `act` one of ACT_CODES; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training).  Everything else — CPU tensors, float64, another layout, an unknown activation — keeps the torch lines."""
     if not ACT_DROPOUT_HIP or torch.is_autocast_enabled():
         return False
     if _actdrop_problem(h, bias, act) is not None:
         return False
-    return _as_handed_over(bias) and not _capturing()
+    return _as_handed_over(bias) and _capture_ok(h.device, masked)
 
 
-def bias_act_dropout_sites_served(x: Tensor, sites) -> bool:
+def bias_act_dropout_sites_served(x: Tensor, sites, masked: bool = True) -> bool:
     """bias_act_dropout_served(F.linear(x, W), bias, act) for every (Cin, bias, act) of `sites` — the activation sites of ONE layer, each
     behind a bias-free F.linear of a tensor with the leading dimensions, dtype and device of the layer input x, whose result is a fresh dense
     tensor [..., Cin] — asked BEFORE those products exist, with the questions about the switch, autocast, x and the stream asked once: a
-    layer asks this once per forward, and the step follows the host time of these sites."""
+    layer asks this once per forward, and the step follows the host time of these sites.  `masked` as there."""
     if not ACT_DROPOUT_HIP or torch.is_autocast_enabled():
         return False
     dt = x.dtype
@@ -1521,7 +1547,7 @@ def bias_act_dropout_sites_served(x: Tensor, sites) -> bool:
             return False
         if bias is not None and not (_actdrop_bias_ok(bias, C, dt, dev) and _as_handed_over(bias)):
             return False
-    return not _capturing()
+    return _capture_ok(dev, masked)
 
 
 class _BiasActDropoutTrainFn(torch.autograd.Function):
@@ -1537,8 +1563,9 @@ class _BiasActDropoutTrainFn(torch.autograd.Function):
         dev = h.device
         y = torch.empty(h.shape[:-1] + (Cout,), dtype=h.dtype, device=dev)
         if R:
-            _launch(dev, lib.dsp_act_dropout_train_fwd, h.data_ptr(), ld, None if bias is None else bias.data_ptr(), act, scale, thr, seed, offset,
-                    y.data_ptr(), _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin)
+            entry, sd, off, tail = _masked(lib, "dsp_act_dropout_train_fwd", seed, offset)
+            _launch(dev, entry, h.data_ptr(), ld, None if bias is None else bias.data_ptr(), act, scale, thr, sd, off,
+                    y.data_ptr(), _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin, *tail)
         ctx.save_for_backward(h, bias)
         ctx.call = (act, ld, scale, thr, seed, offset)
         ctx.set_materialize_grads(False)
@@ -1564,8 +1591,9 @@ class _BiasActDropoutTrainFn(torch.autograd.Function):
         if R:
             nbytes = int(lib.dsp_act_dropout_train_workspace_bytes(R, Cin)) if want_db else 0
             ws = _workspace(dev, nbytes)
-            _launch(dev, lib.dsp_act_dropout_train_bwd, dy.data_ptr(), h.data_ptr(), ld, _ptr(bias), act, scale, thr, seed, offset, _ptr(dh),
-                    _ptr(dbias), _ptr(ws), nbytes, _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin)
+            entry, sd, off, tail = _masked(lib, "dsp_act_dropout_train_bwd", seed, offset)
+            _launch(dev, entry, dy.data_ptr(), h.data_ptr(), ld, _ptr(bias), act, scale, thr, sd, off, _ptr(dh),
+                    _ptr(dbias), _ptr(ws), nbytes, _FLOAT_CODES[h.dtype], _FLOAT_CODES[(h if bias is None else bias).dtype], R, Cin, *tail)
         elif dbias is not None:
             dbias.zero_()                                                  # no rows: the empty sum
         return dh, dbias, None, None, None, None, None
@@ -1641,12 +1669,11 @@ def _embed_entry_problem(tokens, E, P, pad) -> Optional[str]:
     return None
 
 
-def embed_entry_served(tokens: Tensor, embed_tokens: "torch.nn.Embedding", embed_positions: "torch.nn.Embedding") -> bool:
+def embed_entry_served(tokens: Tensor, embed_tokens: "torch.nn.Embedding", embed_positions: "torch.nn.Embedding", masked: bool = True) -> bool:
     """True when embed_entry_autograd serves a training branch on these arguments as they are: the switch is on, autocast off, tokens a GPU
     int64 tensor [B, L], both nn.Embedding weights on that device in one of fp32 / fp16 / bf16, contiguous and on the 16-byte grid (a view
     into a flat parameter buffer at an odd offset is NOT served: the torch lines run), one padding_idx, C a multiple of the elements in 16
-    bytes and at most 2048, L + pad + 1 <= NP, B * L <= 2^24, and the current stream not capturing a graph (the random offset is reserved on
-    the host).  Everything else keeps the torch lines."""
+    bytes and at most 2048, L + pad + 1 <= NP, B * L <= 2^24; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training).  Everything else keeps the torch lines."""
     if not EMBED_ENTRY_HIP or torch.is_autocast_enabled():
         return False
     pad = embed_tokens.padding_idx
@@ -1654,7 +1681,7 @@ def embed_entry_served(tokens: Tensor, embed_tokens: "torch.nn.Embedding", embed
         return False
     if _embed_entry_problem(tokens, embed_tokens.weight, embed_positions.weight, pad) is not None:
         return False
-    return not _capturing()
+    return _capture_ok(tokens.device, masked)
 
 
 class _EmbedEntryFn(torch.autograd.Function):
@@ -1671,8 +1698,9 @@ class _EmbedEntryFn(torch.autograd.Function):
         y = torch.empty((B, L, C), dtype=E.dtype, device=dev)
         idx = torch.empty((2, B * L), dtype=torch.int32, device=dev)
         if B * L:
-            _launch(dev, lib.dsp_embed_entry_fwd, tokens.data_ptr(), ld, E.data_ptr(), P.data_ptr(), pad, embed_scale, scale, thr, seed, offset,
-                    y.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), _FLOAT_CODES[E.dtype], B, L, V, NP, C)
+            entry, sd, off, tail = _masked(lib, "dsp_embed_entry_fwd", seed, offset)
+            _launch(dev, entry, tokens.data_ptr(), ld, E.data_ptr(), P.data_ptr(), pad, embed_scale, scale, thr, sd, off,
+                    y.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), _FLOAT_CODES[E.dtype], B, L, V, NP, C, *tail)
         ctx.save_for_backward(idx)
         ctx.call = (pad, embed_scale, scale, thr, seed, offset, V, NP, C, E.dtype)
         ctx.set_materialize_grads(False)
@@ -1695,8 +1723,9 @@ class _EmbedEntryFn(torch.autograd.Function):
         dP = torch.empty((NP, C), dtype=dt, device=dev) if need[2] else None
         nbytes = int(lib.dsp_embed_entry_bwd_workspace_bytes(n, V, NP, C, thr))
         ws = _workspace(dev, nbytes)
-        _launch(dev, lib.dsp_embed_entry_bwd, dy.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), pad, embed_scale, scale, thr, seed, offset,
-                _ptr(dE), _ptr(dP), _ptr(ws), nbytes, _FLOAT_CODES[dt], n, V, NP, C)
+        entry, sd, off, tail = _masked(lib, "dsp_embed_entry_bwd", seed, offset)
+        _launch(dev, entry, dy.data_ptr(), idx[0].data_ptr(), idx[1].data_ptr(), pad, embed_scale, scale, thr, sd, off,
+                _ptr(dE), _ptr(dP), _ptr(ws), nbytes, _FLOAT_CODES[dt], n, V, NP, C, *tail)
         return None, dE, dP, None, None, None, None, None, None
 
 
@@ -1758,17 +1787,16 @@ def _posadd_problem(x, table, padding_mask, alpha) -> Optional[str]:
     return None
 
 
-def positional_add_dropout_served(x: Tensor, padding_mask: Tensor, table: Tensor, alpha: Tensor) -> bool:
+def positional_add_dropout_served(x: Tensor, padding_mask: Tensor, table: Tensor, alpha: Tensor, masked: bool = True) -> bool:
     """True when positional_add_dropout_autograd serves a training branch on these arguments as they are: the switch (set_embed_entry_hip)
     is on, autocast off, x a GPU tensor [B, N, C] in fp32 / fp16 / bf16 with C a multiple of the elements in 16 bytes and at most 2048, unit
     column stride, rows one common pitch apart and a 16-byte aligned start, padding_mask [B, N] bool, the table [NT, C] contiguous and aligned
-    in that dtype or fp32 without gradient, alpha one element in that dtype or fp32, everything on one device, and the current stream not
-    capturing a graph.  Everything else keeps the torch lines."""
+    in that dtype or fp32 without gradient, alpha one element in that dtype or fp32, everything on one device; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training).  Everything else keeps the torch lines."""
     if not EMBED_ENTRY_HIP or torch.is_autocast_enabled():
         return False
     if _posadd_problem(x, table, padding_mask, alpha) is not None:
         return False
-    return not _capturing()
+    return _capture_ok(x.device, masked)
 
 
 class _PosAddDropoutFn(torch.autograd.Function):
@@ -1785,8 +1813,9 @@ class _PosAddDropoutFn(torch.autograd.Function):
         pos = torch.empty((B * N,), dtype=torch.int32, device=dev)
         codes = (_FLOAT_CODES[x.dtype], _FLOAT_CODES[table.dtype], _FLOAT_CODES[alpha.dtype])
         if B * N:
-            _launch(dev, lib.dsp_pos_add_fwd, x.data_ptr(), ld, mask.data_ptr(), table.data_ptr(), alpha.data_ptr(), 1, scale, thr, seed, offset,
-                    y.data_ptr(), pos.data_ptr(), codes[0], codes[1], codes[2], B, N, NT, C)
+            entry, sd, off, tail = _masked(lib, "dsp_pos_add_fwd", seed, offset)
+            _launch(dev, entry, x.data_ptr(), ld, mask.data_ptr(), table.data_ptr(), alpha.data_ptr(), 1, scale, thr, sd, off,
+                    y.data_ptr(), pos.data_ptr(), codes[0], codes[1], codes[2], B, N, NT, C, *tail)
         ctx.save_for_backward(table, pos)
         ctx.call = (scale, thr, seed, offset, codes, alpha.shape)
         ctx.set_materialize_grads(False)
@@ -1813,8 +1842,9 @@ class _PosAddDropoutFn(torch.autograd.Function):
         if R:
             nbytes = int(lib.dsp_pos_add_bwd_workspace_bytes(R)) if want_da else 0
             ws = _workspace(dev, nbytes)
-            _launch(dev, lib.dsp_pos_add_bwd, dy.data_ptr(), table.data_ptr(), pos.data_ptr(), scale, thr, seed, offset,
-                    _ptr(dx) if thr else None, _ptr(dalpha), _ptr(ws), nbytes, codes[0], codes[1], codes[2], R, table.shape[0], C)
+            entry, sd, off, tail = _masked(lib, "dsp_pos_add_bwd", seed, offset)
+            _launch(dev, entry, dy.data_ptr(), table.data_ptr(), pos.data_ptr(), scale, thr, sd, off,
+                    _ptr(dx) if thr else None, _ptr(dalpha), _ptr(ws), nbytes, codes[0], codes[1], codes[2], R, table.shape[0], C, *tail)
         elif dalpha is not None:
             dalpha.zero_()                                                 # no rows: the empty sum
         return (dx if want_dx else None), None, None, dalpha, None, None, None, None
@@ -1890,16 +1920,15 @@ def _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) -> Opti
 
 
 def relpos_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pos: Tensor, bias_u: Tensor, bias_v: Tensor, pad_mask: Optional[Tensor],
-                                     heads: int) -> bool:
+                                     heads: int, masked: bool = True) -> bool:
     """True when relpos_attention_autograd serves RelPosSelfAttention's training branch on these arguments: the switch is on, autocast off,
     q / k / v [B,T,heads*64] GPU tensors in fp16 or bf16 with one common row stride (a multiple of 8 elements), pos the [2T-1, heads*64]
-    projected positions in that dtype, bias_u / bias_v [heads,64] in that dtype or fp32, T <= 2048, and the current stream not capturing a graph
-    (the random offset is reserved on the host).  Everything else — fp32 data, CPU tensors, another head width — keeps the torch lines."""
+    projected positions in that dtype, bias_u / bias_v [heads,64] in that dtype or fp32, T <= 2048; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training).  Everything else — fp32 data, CPU tensors, another head width — keeps the torch lines."""
     if not RELPOS_ATTENTION_HIP or torch.is_autocast_enabled():
         return False
     if _relpos_train_problem(q, k, v, pos, bias_u, bias_v, pad_mask, heads) is not None:
         return False
-    return _as_handed_over(pos, bias_u, bias_v) and not _capturing()
+    return _as_handed_over(pos, bias_u, bias_v) and _capture_ok(q.device, masked)
 
 
 class _RelPosAttentionTrainFn(torch.autograd.Function):
@@ -1914,9 +1943,10 @@ class _RelPosAttentionTrainFn(torch.autograd.Function):
         dev = q.device
         o = torch.empty((B, T, C), dtype=q.dtype, device=dev)
         lse = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
-        _launch(dev, lib.dsp_relpos_attention_train_fwd, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(), bias_u.data_ptr(),
-                bias_v.data_ptr(), _ptr(mask), scale, thr, seed, offset, o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype],
-                _FLOAT_CODES[bias_u.dtype], B, T, heads)
+        entry, sd, off, tail = _masked(lib, "dsp_relpos_attention_train_fwd", seed, offset)
+        _launch(dev, entry, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(), bias_u.data_ptr(),
+                bias_v.data_ptr(), _ptr(mask), scale, thr, sd, off, o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype],
+                _FLOAT_CODES[bias_u.dtype], B, T, heads, *tail)
         ctx.save_for_backward(q, k, v, pos, bias_u, bias_v, o, lse, mask)
         ctx.call = (heads, scale, thr, seed, offset)
         ctx.set_materialize_grads(False)
@@ -1944,9 +1974,10 @@ class _RelPosAttentionTrainFn(torch.autograd.Function):
         dbv = torch.empty_like(bias_v) if need[5] else None
         nbytes = int(lib.dsp_relpos_attention_train_workspace_bytes(B, T, heads)) if (need[3] or need[4] or need[5]) else 0
         ws = _workspace(dev, nbytes)
-        _launch(dev, lib.dsp_relpos_attention_train_bwd, do.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(),
-                bias_u.data_ptr(), bias_v.data_ptr(), _ptr(mask), o.data_ptr(), lse.data_ptr(), scale, thr, seed, offset, _ptr(dq), _ptr(dk),
-                _ptr(dv), _ptr(dpos), _ptr(du), _ptr(dbv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], _FLOAT_CODES[bias_u.dtype], B, T, heads)
+        entry, sd, off, tail = _masked(lib, "dsp_relpos_attention_train_bwd", seed, offset)
+        _launch(dev, entry, do.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), pos.data_ptr(),
+                bias_u.data_ptr(), bias_v.data_ptr(), _ptr(mask), o.data_ptr(), lse.data_ptr(), scale, thr, sd, off, _ptr(dq), _ptr(dk),
+                _ptr(dv), _ptr(dpos), _ptr(du), _ptr(dbv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], _FLOAT_CODES[bias_u.dtype], B, T, heads, *tail)
         return dq, dk, dv, dpos, du, dbv, None, None, None, None, None
 
 
@@ -2018,16 +2049,16 @@ def _mha_train_problem(q, k, v, pad_mask, heads) -> Optional[str]:
     return None
 
 
-def mha_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pad_mask: Optional[Tensor], heads: int) -> bool:
+def mha_attention_autograd_served(q: Tensor, k: Tensor, v: Tensor, pad_mask: Optional[Tensor], heads: int, masked: bool = True) -> bool:
     """True when mha_attention_autograd serves the training branch of _MHA / _SelfAttention on these arguments: the switch is on, autocast off,
     q [B,N,heads*64] and k, v [B,M,heads*64] GPU tensors in fp16 or bf16 (row strides multiples of 8 elements, one for k and v), N, M <= 4096,
-    pad_mask [B,M] or None, and the current stream not capturing a graph (the random offset is reserved on the host).  Everything else — fp32
+    pad_mask [B,M] or None; while a graph is being captured only inside DropoutState.draws() on that device (the state on the device takes the place of the host's random offset) or with masked=False (a call that draws no mask: p == 0 or not training).  Everything else — fp32
     data, CPU tensors, another head width — keeps the torch lines."""
     if not MHA_ATTENTION_HIP or torch.is_autocast_enabled():
         return False
     if _mha_train_problem(q, k, v, pad_mask, heads) is not None:
         return False
-    return not _capturing()
+    return _capture_ok(q.device, masked)
 
 
 class _MhaTrainFn(torch.autograd.Function):
@@ -2043,8 +2074,9 @@ class _MhaTrainFn(torch.autograd.Function):
         dev = q.device
         o = torch.empty((B, N, C), dtype=q.dtype, device=dev)
         lse = torch.empty((B, heads, N), dtype=torch.float32, device=dev)
-        _launch(dev, lib.dsp_mha_train_fwd, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), scale, thr, seed, offset,
-                o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype], B, N, M, heads)
+        entry, sd, off, tail = _masked(lib, "dsp_mha_train_fwd", seed, offset)
+        _launch(dev, entry, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), scale, thr, sd, off,
+                o.data_ptr(), lse.data_ptr(), _HALF_CODES[q.dtype], B, N, M, heads, *tail)
         ctx.save_for_backward(q, k, v, lse, mask)
         ctx.call = (heads, scale, thr, seed, offset)
         ctx.set_materialize_grads(False)
@@ -2070,8 +2102,9 @@ class _MhaTrainFn(torch.autograd.Function):
         dv = torch.empty((B, M, C), dtype=q.dtype, device=dev) if need[2] else None
         nbytes = int(lib.dsp_mha_train_workspace_bytes(B, N, M, heads))     # D [B,H,N] fp32, rounded up to 16 bytes: the library's own answer
         ws = _workspace(dev, nbytes)
-        _launch(dev, lib.dsp_mha_train_bwd, do.data_ptr(), q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), lse.data_ptr(),
-                scale, thr, seed, offset, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], B, N, M, heads)
+        entry, sd, off, tail = _masked(lib, "dsp_mha_train_bwd", seed, offset)
+        _launch(dev, entry, do.data_ptr(), q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1), _ptr(mask), lse.data_ptr(),
+                scale, thr, sd, off, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), nbytes, _HALF_CODES[q.dtype], B, N, M, heads, *tail)
         return dq, dk, dv, None, None, None, None, None
 
 

@@ -533,9 +533,30 @@ class DAGDecoder(nn.Module):
 @contextmanager
 def _same_draws(seed: int, device, active: bool):
     """The reference runs both decoder passes of the GLAT forward under `torch_seed(rand_seed)` (s2t_conformer_dag.py:39-50,214-215): the
-    same dropout masks in the glancing pass and in the training pass, the surrounding random stream untouched."""
+    same dropout masks in the glancing pass and in the training pass, the surrounding random stream untouched.
+    While a decode_ops.DropoutState.draws() scope is active on the model's device (a graph capture refuses a reseeded generator, and the
+    HIP operators draw from the state there): the first pass under a seed marks the state's host counter, a later pass under that seed
+    rewinds to the mark — the same masks — and the generator is not touched.  What differs from the eager form there, by construction:
+    the passes CONSUME offsets of the scope (the surrounding stream is not left untouched: the calls behind the pair go on from the highest
+    offset either pass reached); marks pair up — the second pass under a seed rewinds and forgets the mark, so a third pass under the same
+    seed in that scope starts a pair of its own instead of sharing masks; and only the HIP operators' masks are repeated — a dropout
+    site that stays on its torch lines inside the scope (fp32 attention, a switched-off operator) draws from the generator in both passes
+    and is NOT the same in the two, as nothing reseeds it."""
     if not active:
         yield
+        return
+    state = decode_ops._active_dropout_state(device)
+    if state is not None:
+        mark = state._seed_marks.pop(seed, None)
+        if mark is None:
+            state._seed_marks[seed] = state.mark()
+            yield
+        else:
+            state.rewind(mark)
+            try:
+                yield
+            finally:
+                state._catch_up()            # a second pass that drew fewer masks leaves no spent offset to the calls behind it
         return
     if device.type == "cuda":
         # the generator of the MODEL's device (not the current one): state saved, seeded and restored on that device

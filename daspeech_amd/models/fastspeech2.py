@@ -39,7 +39,7 @@ def _conv_bias_relu(x: Tensor, conv: nn.Conv1d, training: bool) -> Tensor:
     """relu(conv(x)) of a convolution that decode_ops.conv1d_channels_last_sites_served accepted, on the channels-last x: the HIP convolution
     without its bias, then bias + ReLU as one HIP operator (csrc/act_dropout_train.hip) where that serves the site, else the torch lines"""
     h = decode_ops.conv1d_channels_last_checked(x, conv.weight)
-    if decode_ops.bias_act_dropout_served(h, conv.bias, "relu"):
+    if decode_ops.bias_act_dropout_served(h, conv.bias, "relu", masked=False):
         return decode_ops.bias_act_dropout_checked(h, conv.bias, "relu", 0.0, training)
     return F.relu(h if conv.bias is None else h + conv.bias)
 
@@ -134,7 +134,8 @@ class _ConvFFN(nn.Module):
                                                                  return_sum=False)
             return self.layer_norm(_drop(h if c2.bias is None else h + c2.bias, self.p, self.training) + x)
         h = self.ffn(x.transpose(1, 2)).transpose(1, 2)
-        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(None, x, self.layer_norm):
+        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(
+                None, x, self.layer_norm, masked=self.training and self.p > 0):
             # dropout, residual add and LayerNorm as one HIP operator (csrc/residual_norm_train.hip) on the channels-last copy of the
             # convolution's output; the Conv1d bias stays in the convolution
             return _dops.residual_dropout_layer_norm_checked(h.contiguous(), x, self.layer_norm, p=self.p, training=self.training, return_sum=False)
@@ -152,7 +153,7 @@ class FFTLayer(nn.Module):
         """lens [B] int32 + slack (eval-mode inference on the GPU only): rows from lens[b] + slack on are padding that no valid frame of
         the model's output depends on; the matrix-core kernels skip their tiles and return zeros there."""
         from .. import decode_ops as _dops
-        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(x, x, self.layer_norm):
+        if (self.training or torch.is_grad_enabled()) and _dops.residual_dropout_layer_norm_served(x, x, self.layer_norm, masked=False):
             # residual add and LayerNorm (no dropout at this site) as one HIP operator under autograd (csrc/residual_norm_train.hip)
             x = _dops.residual_dropout_layer_norm_checked(self.self_attn(x, padding_mask, lens, slack), x, self.layer_norm,
                                                          training=self.training, return_sum=False)
@@ -167,7 +168,7 @@ def _ln_drop(h: Tensor, ln: nn.LayerNorm, p: float, training: bool) -> Tensor:
     rule takes the tensor, else the torch line"""
     from .. import decode_ops as _dops
     y = _dops.residual_dropout_layer_norm_checked(None, h, ln) if _dops.residual_dropout_layer_norm_served(None, h, ln) else ln(h)
-    if _dops.bias_act_dropout_served(y, None, "identity"):
+    if _dops.bias_act_dropout_served(y, None, "identity", masked=training and p > 0):
         return _dops.bias_act_dropout_checked(y, None, "identity", p, training)
     return _drop(y, p, training)
 

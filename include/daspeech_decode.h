@@ -547,6 +547,64 @@ int dsp_mha_train_bwd(const void* dout, const void* q, long ldq, const void* k, 
                       const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
                       void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream);
 
+/* The dropout state on the device: the masked launches above for a stream that is being captured into a graph, where no host integer can
+ * name the offset of a replay.  rng_state points at TWO uint64 of device memory, {seed, offset}, 8-byte aligned.  Every ..._state entry is the
+ * entry of the same name with ONE more argument before the stream, `const uint64_t* rng_state`, and runs the SAME kernel:
+ *     rng_state != NULL:  the kernel uses seed = rng_state[0] and offset = rng_state[1] + `offset` — the `seed` argument is not read, and the
+ *                         `offset` argument is the call's distance from the state's offset (a host integer: 0, 4, 8, ... for the masked calls
+ *                         of one pass, as the default generator's offset would have moved);
+ *     rng_state == NULL:  (seed, offset) as given — the entry without the suffix, bit for bit.
+ *   The state is read ONCE per thread at kernel entry through a kernel argument (a uniform load, not one per element), when the kernel runs:
+ *   a replayed graph draws from whatever the state holds at that moment.  None of these kernels writes it.  A misaligned rng_state:
+ *   DSP_EINVAL before any launch; everything else as the entry without the suffix says.
+ *   dsp_dropout_state_advance: rng_state[1] += by, one tiny launch on the stream (an ordinary vector store) — the ONLY kernel that writes a
+ *   state.  Recorded as the last node of a graph, it leaves the state where one eager pass of `by / 4` masked calls leaves the generator, so
+ *   every replay draws new masks without host work.  A backward reads the state its forward read, so it has to run before the advance. */
+int dsp_resnorm_train_fwd_state(const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
+                                float alpha, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* s, void* y, float* stats,
+                                int act_dtype, int param_dtype, int64_t R, int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_resnorm_train_bwd_state(const void* dy, const void* ds, const void* s, const float* stats, const void* gamma, float alpha,
+                                float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dh, void* dresidual, void* dbias,
+                                void* dgamma, void* dbeta, void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int64_t R,
+                                int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_dropout_keep_mask_state(uint64_t seed, uint64_t offset, unsigned int thr, unsigned char* out, int64_t n, const uint64_t* rng_state,
+                                dsp_stream_t stream);
+int dsp_act_dropout_train_fwd_state(const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
+                                    uint64_t offset, void* y, int act_dtype, int param_dtype, int64_t R, int Cin, const uint64_t* rng_state,
+                                    dsp_stream_t stream);
+int dsp_act_dropout_train_bwd_state(const void* dy, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr,
+                                    uint64_t seed, uint64_t offset, void* dh, void* dbias, void* workspace, size_t workspace_bytes,
+                                    int act_dtype, int param_dtype, int64_t R, int Cin, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_embed_entry_fwd_state(const int64_t* tokens, long ld_tok, const void* E, const void* P, int64_t pad, float embed_scale, float keep_scale,
+                              unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* tok32, int32_t* pos32, int dtype, int B, int L,
+                              int V, int NP, int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_embed_entry_bwd_state(const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
+                              unsigned int thr, uint64_t seed, uint64_t offset, void* dE, void* dP, void* workspace, size_t workspace_bytes,
+                              int dtype, int64_t n, int V, int NP, int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_pos_add_fwd_state(const void* x, long ld_x, const unsigned char* padding_mask, const void* tab, const void* alpha, int pad,
+                          float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* y, int32_t* pos32, int act_dtype,
+                          int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_pos_add_bwd_state(const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
+                          uint64_t offset, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype, int tab_dtype,
+                          int alpha_dtype, int64_t R, int NT, int C, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_relpos_attention_train_fwd_state(const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u,
+                                         const void* bias_v, const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed,
+                                         uint64_t offset, void* out, float* lse, int act_dtype, int param_dtype, int B, int T, int H,
+                                         const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_relpos_attention_train_bwd_state(const void* dout, const void* q, const void* k, const void* v, long ld, const void* pos,
+                                         const void* bias_u, const void* bias_v, const unsigned char* pad_mask, const void* out, const float* lse,
+                                         float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
+                                         void* dpos, void* dbias_u, void* dbias_v, void* workspace, size_t workspace_bytes, int act_dtype,
+                                         int param_dtype, int B, int T, int H, const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_mha_train_fwd_state(const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask, float keep_scale,
+                            unsigned int thr, uint64_t seed, uint64_t offset, void* out, float* lse, int act_dtype, int B, int N, int M, int H,
+                            const uint64_t* rng_state, dsp_stream_t stream);
+int dsp_mha_train_bwd_state(const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
+                            const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, void* dq, void* dk, void* dv,
+                            void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, const uint64_t* rng_state,
+                            dsp_stream_t stream);
+int dsp_dropout_state_advance(uint64_t* rng_state, uint64_t by, dsp_stream_t stream);
+
 /* Conv1d(Cin, Cout, K, stride 1, dilation 1, groups 1, padding P = (K-1)/2) on CHANNELS-LAST data under autograd (csrc/conv1d_train.hip),
  * fp16 / bf16 data — the FastSpeech2 feed-forward and variance-predictor convolutions of the training step without their transposes:
  *     y [b,t,co]  = [bias[co] +] sum_k sum_ci x[b, t+k-P, ci] * W[co,ci,k]        rows outside [0, T) of a sample count as zeros
