@@ -192,6 +192,8 @@ SIGNATURES = {
     "dsp_fp16_optim_grad_sumsq": (_c_int, [_c_p, _c_int, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_sz, _c_p, _c_p]),
     "dsp_fp16_optim_adam_step": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p] + [ctypes.c_double] * 8
                                  + [_c_int, _c_p]),
+    "dsp_fp16_optim_scale_step": (_c_int, [_c_p, _c_p] + [ctypes.c_double] * 6 + [_c_i64, ctypes.c_double, _c_p]),
+    "dsp_fp16_optim_adam_step_state": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "dsp_dag_alignment_trace_optional": (_c_int, [_c_int, _c_int]),
     "dsp_dag_debug_k5": (_c_int, [ctypes.POINTER(ctypes.c_uint)]),
     "dsp_dag_set_option": (_c_int, [ctypes.c_char_p, _c_int]),

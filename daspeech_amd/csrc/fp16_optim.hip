@@ -4,6 +4,10 @@
 //   grad_sumsq   S = sum float(g)^2 over the 16-bit gradients: 2 B per element, one fp32 partial per work item, one workgroup adds them in double.
 //   adam_step    g = c * float(g16), decoupled decay, Adam on the flat fp32 master / exp_avg / exp_avg_sq, the 16-bit parameter rounded from the
 //                stored master: 2 + 12 read, 12 + 2 written per element, no flat fp32 gradient.
+//   scale_step   one thread: from S and the optimizer state (a block of 8-byte slots, daspeech_optim.h) the norm, the overflow decision, the
+//                clip coefficient, the loss scale, the step count with its bias corrections and the Adam scalars — the host arithmetic of
+//                FP16FlatOptimizer._step_hip and DynamicLossScaler in double, bit for bit, so that a step waits for nothing.
+//   adam_step_state   adam_step with its scalars and the `applied` flag read from that state instead of the argument list: the same kernel.
 //
 // One workgroup serves one work item (a run of <= chunk elements of one tensor).  The fp32 streams carry 24 of the 28 bytes of an element, so they
 // decide the layout: an item peels elements until its FLAT index is a multiple of 4, then every thread moves groups of four as float4; what is
@@ -167,13 +171,31 @@ __device__ __forceinline__ void adam_groups(const T* __restrict__ g, T* __restri
     }
 }
 
+// where the kernel takes its scalars from: the argument list (the host decided that the step is applied), or the optimizer state that
+// fo_scale_step_kernel wrote in the launch before (applied == 0: the workgroup returns before its first store)
+struct ScalarsByValue {
+    AdamScalars k;
+    __device__ __forceinline__ bool load(AdamScalars& out) const { out = k; return true; }
+};
+struct ScalarsFromState {
+    const uint64_t* state;
+    __device__ __forceinline__ bool load(AdamScalars& out) const
+    {
+        if (*reinterpret_cast<const int*>(state + DSP_OPTIM_SLOT_APPLIED) == 0) return false;      // uniform over the grid
+        out = *reinterpret_cast<const AdamScalars*>(state + DSP_OPTIM_SLOT_SCALARS);
+        return true;
+    }
+};
+
 // grid: one workgroup per item
-template <typename T>
+template <typename T, typename SRC>
 __global__ __launch_bounds__(FO_THREADS) void fo_adam_kernel(const void* const* __restrict__ grads, void* const* __restrict__ params16,
                                                              const int64_t* __restrict__ offsets, const int64_t* __restrict__ items,
                                                              float* __restrict__ master, float* __restrict__ exp_avg,
-                                                             float* __restrict__ exp_avg_sq, AdamScalars k)
+                                                             float* __restrict__ exp_avg_sq, SRC src)
 {
+    AdamScalars k;
+    if (!src.load(k)) return;
     const int64_t* it = items + 3 * (size_t)blockIdx.x;
     const int64_t ti = it[0], first = it[1];
     const int cnt = (int)it[2];
@@ -211,6 +233,70 @@ __global__ __launch_bounds__(FO_THREADS) void fo_adam_kernel(const void* const* 
     else if ((a & 3u) == 0) FO_GROUPS(4);
     else FO_GROUPS(2);
 #undef FO_GROUPS
+}
+
+static_assert(sizeof(AdamScalars) == 4 * DSP_OPTIM_N_SCALARS, "AdamScalars: the floats of the state's scalar slots");
+static_assert(8 * (DSP_OPTIM_STATE_SLOTS - DSP_OPTIM_SLOT_SCALARS) >= (int)sizeof(AdamScalars), "AdamScalars past the end of the state");
+
+// The Adam scalars derived in double and rounded once: 1 - beta2 from a float beta2 would carry the float's error at 1000 x its relative size.
+// One function for the host entry and the device update.  Contraction off: hipcc contracts by default, and 1 - lr*wd fused into an fma on
+// the device would differ in the last bit from what the host computes.
+__host__ __device__ inline AdamScalars derive_scalars(double c, double lr, double beta1, double beta2, double eps, double lr_wd, double bias1,
+                                                      double sqrt_bias2)
+{
+#pragma clang fp contract(off)
+    AdamScalars k;
+    k.c = (float)c; k.beta1 = (float)beta1; k.beta2 = (float)beta2; k.eps = (float)eps;
+    k.decay = (float)(1.0 - lr_wd); k.step = (float)(lr / bias1); k.omb1 = (float)(1.0 - beta1); k.omb2 = (float)(1.0 - beta2);
+    k.sqrt_bias2 = (float)sqrt_bias2;
+    return k;
+}
+
+struct ScaleConsts {
+    double beta1, beta2, eps, weight_decay, clip_norm, scale_factor, min_loss_scale;
+    int64_t scale_window;
+};
+
+// One thread.  Every operation is an IEEE double multiply, add, divide or square root in the order of FP16FlatOptimizer._step_hip and
+// DynamicLossScaler, so plain host floats reproduce every slot bit for bit — which holds only with floating-point contraction OFF in this
+// body: hipcc contracts by default, and 1 - pow1*beta1 or 1 - lr*wd fused into an fma would differ from the host in the last bit.
+// Plain vector stores, no atomics.
+__global__ __launch_bounds__(64) void fo_scale_step_kernel(const double* __restrict__ S_ptr, uint64_t* __restrict__ state, ScaleConsts k)
+{
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double* sd = reinterpret_cast<double*>(state);
+    int64_t* si = reinterpret_cast<int64_t*>(state);
+    const double S = *S_ptr;
+    double loss_scale = sd[DSP_OPTIM_SLOT_LOSS_SCALE];
+    int64_t iter = si[DSP_OPTIM_SLOT_ITER];
+    const double lr = sd[DSP_OPTIM_SLOT_LR];
+    double c = sd[DSP_OPTIM_SLOT_GRAD_MULT] / loss_scale;
+    const double nv = (S == S && S >= 0.0) ? fabs(c) * sqrt(S) : __builtin_nan("");
+    sd[DSP_OPTIM_SLOT_GRAD_NORM] = nv;
+    int* applied = reinterpret_cast<int*>(state + DSP_OPTIM_SLOT_APPLIED);
+    if (nv != nv || nv == __builtin_inf()) {            // the overflow: the scale shrinks, nothing else moves
+        si[DSP_OPTIM_SLOT_LAST_OVERFLOW_ITER] = iter;
+        loss_scale = loss_scale / k.scale_factor;
+        iter += 1;
+        if (loss_scale <= k.min_loss_scale) *reinterpret_cast<int*>(state + DSP_OPTIM_SLOT_FLOOR_HIT) = 1;      // sticky
+        *applied = 0;
+    } else {
+        if (k.clip_norm > 0.0 && nv > k.clip_norm) c = c * (k.clip_norm / (nv + 1e-6));
+        const double pow1 = sd[DSP_OPTIM_SLOT_POW1] * k.beta1, pow2 = sd[DSP_OPTIM_SLOT_POW2] * k.beta2;
+        si[DSP_OPTIM_SLOT_T] += 1;
+        sd[DSP_OPTIM_SLOT_POW1] = pow1;
+        sd[DSP_OPTIM_SLOT_POW2] = pow2;
+        const double bias1 = 1.0 - pow1, sqrt_bias2 = sqrt(1.0 - pow2);
+        *reinterpret_cast<AdamScalars*>(state + DSP_OPTIM_SLOT_SCALARS) =
+            derive_scalars(c, lr, k.beta1, k.beta2, k.eps, lr * k.weight_decay, bias1, sqrt_bias2);
+        *applied = 1;
+        if ((iter - si[DSP_OPTIM_SLOT_LAST_OVERFLOW_ITER]) % k.scale_window == 0) loss_scale = loss_scale * k.scale_factor;
+        iter += 1;
+    }
+    sd[DSP_OPTIM_SLOT_LOSS_SCALE] = loss_scale;
+    si[DSP_OPTIM_SLOT_ITER] = iter;
+    *reinterpret_cast<float*>(state + DSP_OPTIM_SLOT_LOSS_SCALE_F32) = (float)loss_scale;
 }
 
 static bool chunk_on_grid(int chunk) { return chunk >= FO_CHUNK_GRID && chunk <= FO_CHUNK_MAX && chunk % FO_CHUNK_GRID == 0; }
@@ -264,13 +350,49 @@ extern "C" int dsp_fp16_optim_adam_step(const void* const* grads, void* const* p
         set_error("fp16_optim_adam_step: master / exp_avg / exp_avg_sq must start on a 16-byte boundary");
         return DSP_EINVAL;
     }
-    AdamScalars k;
-    // derived in double, rounded once: 1 - beta2 from a float beta2 would carry the float's error at 1000 x its relative size
-    k.c = (float)c; k.beta1 = (float)beta1; k.beta2 = (float)beta2; k.eps = (float)eps;
-    k.decay = (float)(1.0 - lr_wd); k.step = (float)(lr / bias1); k.omb1 = (float)(1.0 - beta1); k.omb2 = (float)(1.0 - beta2);
-    k.sqrt_bias2 = (float)sqrt_bias2;
+    ScalarsByValue src;
+    src.k = derive_scalars(c, lr, beta1, beta2, eps, lr_wd, bias1, sqrt_bias2);
     DSP_DISPATCH_ELEM_16(dtype, T,
-        hipLaunchKernelGGL((fo_adam_kernel<T>), dim3((unsigned)n_items), dim3(FO_THREADS), 0, as_stream(stream), grads, params16, offsets, items,
-                           master, exp_avg, exp_avg_sq, k));
+        hipLaunchKernelGGL((fo_adam_kernel<T, ScalarsByValue>), dim3((unsigned)n_items), dim3(FO_THREADS), 0, as_stream(stream), grads, params16,
+                           offsets, items, master, exp_avg, exp_avg_sq, src));
     return check_launch("fp16_optim_adam_step");
+}
+
+extern "C" int dsp_fp16_optim_scale_step(const double* S, void* state, double beta1, double beta2, double eps, double weight_decay,
+                                         double clip_norm, double scale_factor, int64_t scale_window, double min_loss_scale, dsp_stream_t stream)
+{
+    if (!S || !state) { set_error("fp16_optim_scale_step: null pointer"); return DSP_EINVAL; }
+    if (((uintptr_t)S & 7) != 0 || ((uintptr_t)state & 7) != 0) { set_error("fp16_optim_scale_step: S / state must start on an 8-byte boundary"); return DSP_EINVAL; }
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) { set_error("fp16_optim_scale_step: betas (%g, %g) outside [0, 1)", beta1, beta2); return DSP_EINVAL; }
+    if (!(scale_factor > 1.0) || scale_window < 1) {
+        set_error("fp16_optim_scale_step: scale_factor = %g (> 1), scale_window = %lld (>= 1)", scale_factor, (long long)scale_window);
+        return DSP_EINVAL;
+    }
+    ScaleConsts k;
+    k.beta1 = beta1; k.beta2 = beta2; k.eps = eps; k.weight_decay = weight_decay; k.clip_norm = clip_norm; k.scale_factor = scale_factor;
+    k.min_loss_scale = min_loss_scale; k.scale_window = scale_window;
+    hipLaunchKernelGGL(fo_scale_step_kernel, dim3(1), dim3(64), 0, as_stream(stream), S, (uint64_t*)state, k);
+    return check_launch("fp16_optim_scale_step");
+}
+
+extern "C" int dsp_fp16_optim_adam_step_state(const void* const* grads, void* const* params16, int dtype, const int64_t* offsets, int N,
+                                              const int64_t* items, int64_t n_items, int chunk, float* master, float* exp_avg,
+                                              float* exp_avg_sq, const void* state, dsp_stream_t stream)
+{
+    if (dtype != DSP_F16 && dtype != DSP_BF16) { set_error("fp16_optim_adam_step_state: unsupported dtype %d (DSP_F16 / DSP_BF16)", dtype); return DSP_EINVAL; }
+    if (N < 0 || n_items < 0 || n_items > 0x7fffffffLL) { set_error("fp16_optim_adam_step_state: bad sizes"); return DSP_EINVAL; }
+    if (!chunk_on_grid(chunk)) { set_error("fp16_optim_adam_step_state: chunk = %d (a multiple of %d up to %d)", chunk, FO_CHUNK_GRID, FO_CHUNK_MAX); return DSP_EINVAL; }
+    if (N == 0 || n_items == 0) return DSP_OK;
+    if (!grads || !params16 || !offsets || !items || !master || !exp_avg || !exp_avg_sq) { set_error("fp16_optim_adam_step_state: null pointer"); return DSP_EINVAL; }
+    if (!state || ((uintptr_t)state & 7) != 0) { set_error("fp16_optim_adam_step_state: state null or off its 8-byte boundary"); return DSP_EINVAL; }
+    if ((((uintptr_t)master | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) {
+        set_error("fp16_optim_adam_step_state: master / exp_avg / exp_avg_sq must start on a 16-byte boundary");
+        return DSP_EINVAL;
+    }
+    ScalarsFromState src;
+    src.state = (const uint64_t*)state;
+    DSP_DISPATCH_ELEM_16(dtype, T,
+        hipLaunchKernelGGL((fo_adam_kernel<T, ScalarsFromState>), dim3((unsigned)n_items), dim3(FO_THREADS), 0, as_stream(stream), grads, params16,
+                           offsets, items, master, exp_avg, exp_avg_sq, src));
+    return check_launch("fp16_optim_adam_step_state");
 }
