@@ -16,6 +16,8 @@
 // one fp32 partial per input column for its chunk, and ad_dbias_merge_kernel adds the chunks in ASCENDING order.  No float atomics, no hand-off
 // between workgroups inside a launch: same inputs, same bits.
 #include "common.h"
+#include "host_gates.h"
+#include "partial_merge.h"
 #include "philox.h"
 #include "../../include/daspeech_decode.h"
 
@@ -163,35 +165,13 @@ __global__ __launch_bounds__(64) void ad_bwd_kernel(const T* __restrict__ dy, co
 }
 
 // ---------------------------------------------------------------- backward tail: the chunks in ascending order
-// The partials are a [nchunks][Cin] matrix; a workgroup owns 64 of its columns.  As rn_bwd_merge_kernel (residual_norm_train.hip): all 256
-// threads bring a tile of AD_MT chunks x 64 columns into LDS (independent loads), then one thread per column adds the tile's values in
-// ascending chunk order — the sum a plain loop over the chunks gives, without its chain of load latencies.
-constexpr int AD_MT = 128;
+// The partials are a [nchunks][Cin] matrix; a workgroup owns 64 of its columns (partial_merge.h: the tiled form).
 __global__ __launch_bounds__(256) void ad_dbias_merge_kernel(const float* __restrict__ part, long nchunks, void* __restrict__ dbias, int pdtype,
                                                              int Cin)
 {
-    __shared__ float tile[AD_MT][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + tx;
-    float acc = 0.f;
-#pragma unroll 1
-    for (long k0 = 0; k0 < nchunks; k0 += AD_MT) {
-        float r[AD_MT / 4];
-#pragma unroll
-        for (int j = 0; j < AD_MT / 4; ++j) {
-            const long k = k0 + ty + 4 * j;
-            r[j] = (k < nchunks && c < Cin) ? part[(size_t)k * Cin + c] : 0.f;
-        }
-        __syncthreads();                                                   // the tile before this one has been added
-#pragma unroll
-        for (int j = 0; j < AD_MT / 4; ++j) tile[ty + 4 * j][tx] = r[j];
-        __syncthreads();
-        if (ty == 0) {
-            const int n = (int)(nchunks - k0 < AD_MT ? nchunks - k0 : AD_MT);
-            for (int k = 0; k < n; ++k) acc += tile[k][tx];
-        }
-    }
-    if (ty == 0 && c < Cin) param_store(dbias, pdtype, c, acc);
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float acc = merge_column_tiled<128>(part, nchunks, Cin, c);
+    if ((threadIdx.x >> 6) == 0 && c < Cin) param_store(dbias, pdtype, c, acc);
 }
 
 static long ad_chunks(long R) { return (R + AD_CHUNK - 1) / AD_CHUNK; }
@@ -200,7 +180,7 @@ static long ad_chunks(long R) { return (R + AD_CHUNK - 1) / AD_CHUNK; }
 static int ad_check(const char* who, int act, int act_dtype, int param_dtype, long R, int Cin, long ld_h, unsigned int thr,
                     const uint64_t* rng_state)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int es = elem_size(act_dtype);
     if (!es || !elem_size(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (h, y and their gradients) / %d (bias, dbias: the same, or fp32)", who, act_dtype, param_dtype);
@@ -236,7 +216,7 @@ using namespace dsp;
 extern "C" size_t dsp_act_dropout_train_workspace_bytes(int64_t R, int Cin)
 {
     if (R <= 0 || Cin < 1) return 0;
-    return ((size_t)ad_chunks((long)R) * (size_t)Cin * sizeof(float) + 15) & ~(size_t)15;
+    return a16((size_t)ad_chunks((long)R) * (size_t)Cin * sizeof(float));
 }
 
 static int ad_fwd(const char* who, const void* h, long ld_h, const void* bias, int act, float keep_scale, unsigned int thr, uint64_t seed,
@@ -245,7 +225,7 @@ static int ad_fwd(const char* who, const void* h, long ld_h, const void* bias, i
     const int rc = ad_check(who, act, act_dtype, param_dtype, (long)R, Cin, ld_h, thr, rng_state);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!h || !y || y == h || (bias && (bias == h || bias == y))) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
-    if ((((uintptr_t)h) | ((uintptr_t)bias) | ((uintptr_t)y)) & 15) { set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(tensors16_gate(who, h, bias, y));
     const int V = 16 / elem_size(act_dtype), Cout = act == DSP_ACT_GLU ? Cin / 2 : Cin;
     const dim3 grid((unsigned)ad_chunks((long)R), (unsigned)((Cout / V + AD_SLAB - 1) / AD_SLAB));
     hipStream_t st = as_stream(stream);
@@ -278,13 +258,9 @@ static int ad_bwd(const char* who, const void* dy, const void* h, long ld_h, con
     if (!dy || !h || (dh && (dh == dy || dh == h || dh == bias || dh == dbias)) || (dbias && (dbias == dy || dbias == h || dbias == bias))) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
-    if ((((uintptr_t)dy) | ((uintptr_t)h) | ((uintptr_t)bias) | ((uintptr_t)dh) | ((uintptr_t)dbias)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
-    if (dbias && (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_act_dropout_train_workspace_bytes(R, Cin))) {
-        set_error("%s: workspace of dsp_act_dropout_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    DSP_GATE(tensors16_gate(who, dy, h, bias, dh, dbias));
+    if (dbias)
+        DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_act_dropout_train_workspace_bytes(R, Cin), "dsp_act_dropout_train_workspace_bytes"));
     const int V = 16 / elem_size(act_dtype), Cout = act == DSP_ACT_GLU ? Cin / 2 : Cin;
     const long nchunks = ad_chunks((long)R);
     const dim3 grid((unsigned)nchunks, (unsigned)((Cout / V + AD_SLAB - 1) / AD_SLAB));

@@ -17,6 +17,8 @@
 // consumer merges the partials in ASCENDING chunk order.  The statistics are merged as (count, mean, M2) triples (Chan et al.), each
 // tile's M2 from its centred values.  No float atomics, no hand-off between workgroups inside a launch: same inputs, same bits.
 #include "common.h"
+#include "host_gates.h"
+#include "partial_merge.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -429,23 +431,13 @@ __global__ __launch_bounds__(256) void cm_bwd_dxdw_kernel(const T* __restrict__ 
     }
 }
 
-// ---------------------------------------------------------------- backward 4: dw[c,k] = its chunk sums in ascending chunk order
-template <typename T>
-__global__ __launch_bounds__(256) void cm_bwd_dw_merge_kernel(const float* __restrict__ wpart, int nchunks, T* __restrict__ dw, int CK)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= CK) return;
-    float a = 0.f;
-    for (int k = 0; k < nchunks; ++k) a += wpart[(size_t)k * CK + e];
-    dw[e] = from_f<T>(a);
-}
+// backward 4: dw[c,k] = its chunk sums in ascending chunk order, merge_store_kernel (partial_merge.h)
 
-static size_t cm_a16(size_t n) { return (n + 15) & ~(size_t)15; }
 static long cm_chunks(int B, int T) { return ((long)B * ((T + CM_TT - 1) / CM_TT) + DSP_CONVMOD_CHUNK_TILES - 1) / DSP_CONVMOD_CHUNK_TILES; }
 // the workspace: [chunks][3][C] statistics (forward) or [chunks][2][C] dbeta / dgamma sums (backward) | dz [B,T,C] | [chunks][C][K] dw sums
-static size_t cm_stat_bytes(int B, int T, int C) { return cm_a16((size_t)cm_chunks(B, T) * 3 * C * sizeof(float)); }
-static size_t cm_dz_bytes(int B, int T, int C) { return cm_a16((size_t)B * T * C * sizeof(float)); }
-static size_t cm_wpart_bytes(int B, int T, int C, int K) { return cm_a16((size_t)cm_chunks(B, T) * C * K * sizeof(float)); }
+static size_t cm_stat_bytes(int B, int T, int C) { return a16((size_t)cm_chunks(B, T) * 3 * C * sizeof(float)); }
+static size_t cm_dz_bytes(int B, int T, int C) { return a16((size_t)B * T * C * sizeof(float)); }
+static size_t cm_wpart_bytes(int B, int T, int C, int K) { return a16((size_t)cm_chunks(B, T) * C * K * sizeof(float)); }
 
 // what both entry points check; 1: nothing to do (B == 0), 0: go on, < 0: refused
 static int cm_check(const char* who, int act_dtype, int bn_dtype, int B, int T, int C, int K)
@@ -495,11 +487,8 @@ extern "C" int dsp_dwconv_bn_silu_train_fwd(const void* x, const void* w, const 
     if (!x || !w || !gamma || !beta || !y || !save_mean || !save_invstd || x == y || save_mean == save_invstd) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
-    if ((((uintptr_t)x) | ((uintptr_t)y)) & 15) { set_error("%s: x / y must be 16-byte aligned", who); return DSP_EINVAL; }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < cm_stat_bytes(B, T, C)) {
-        set_error("%s: workspace of dsp_dwconv_bn_silu_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    if (!on16(x, y)) { set_error("%s: x / y must be 16-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(workspace_gate(who, workspace, workspace_bytes, cm_stat_bytes(B, T, C), "dsp_dwconv_bn_silu_train_workspace_bytes"));
     const int V = 16 / elem_size(act_dtype);
     const int nchunks = (int)cm_chunks(B, T);
     const dim3 grid((unsigned)nchunks, (unsigned)((C / V + CM_CG - 1) / CM_CG));
@@ -523,11 +512,9 @@ extern "C" int dsp_dwconv_bn_silu_train_bwd(const void* x, const void* w, const 
     if (!x || !w || !gamma || !beta || !save_mean || !save_invstd || !grad_y || dx == x || dx == grad_y || (dw && dw == w)) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
-    if ((((uintptr_t)x) | ((uintptr_t)grad_y) | ((uintptr_t)dx)) & 15) { set_error("%s: x / grad_y / dx must be 16-byte aligned", who); return DSP_EINVAL; }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K)) {
-        set_error("%s: workspace of dsp_dwconv_bn_silu_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    if (!on16(x, grad_y, dx)) { set_error("%s: x / grad_y / dx must be 16-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_dwconv_bn_silu_train_workspace_bytes(B, T, C, K),
+                            "dsp_dwconv_bn_silu_train_workspace_bytes"));
     const int V = 16 / elem_size(act_dtype);
     const int nchunks = (int)cm_chunks(B, T);
     const unsigned gy_ = (unsigned)((C / V + CM_CG - 1) / CM_CG);
@@ -554,11 +541,7 @@ extern "C" int dsp_dwconv_bn_silu_train_bwd(const void* x, const void* w, const 
     }
     if (dw) {
         const int CK = C * K;
-        switch (act_dtype) {
-            case DSP_F32: hipLaunchKernelGGL(cm_bwd_dw_merge_kernel<float>, dim3((CK + 255) / 256), dim3(256), 0, st, wpart, nchunks, (float*)dw, CK); break;
-            case DSP_F16: hipLaunchKernelGGL(cm_bwd_dw_merge_kernel<__half>, dim3((CK + 255) / 256), dim3(256), 0, st, wpart, nchunks, (__half*)dw, CK); break;
-            default: hipLaunchKernelGGL(cm_bwd_dw_merge_kernel<__hip_bfloat16>, dim3((CK + 255) / 256), dim3(256), 0, st, wpart, nchunks, (__hip_bfloat16*)dw, CK); break;
-        }
+        DSP_DISPATCH_ELEM(act_dtype, E, hipLaunchKernelGGL(merge_store_kernel<E>, dim3((CK + 255) / 256), dim3(256), 0, st, wpart, nchunks, (long)CK, (E*)dw));
     }
     return check_launch(who);
 }

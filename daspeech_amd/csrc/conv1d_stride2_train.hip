@@ -106,40 +106,13 @@ __global__ __launch_bounds__(256) void cs_conv_kernel(const E* __restrict__ in, 
     }
 }
 
-static int cs_tout(int T) { return (T - 1) / 2 + 1; }
-
-// what the entry points check; 1: nothing to do (no rows), 0: go on, < 0: refused
-static int cs_check(const char* who, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, long ld_a, int Ca, long ld_b, int Cb)
-{
-    if ((act_dtype != DSP_F16 && act_dtype != DSP_BF16) || (bias_dtype != act_dtype && bias_dtype != DSP_F32)) {
-        set_error("%s: dtype codes %d (x, W, y and their gradients: fp16 or bf16) / %d (bias, db: the same, or fp32)", who, act_dtype, bias_dtype);
-        return DSP_EINVAL;
-    }
-    if (Cin < 16 || Cout < 64 || (Cin % 16) || (Cout % 64) || Cin > CV_MAX_C || Cout > CV_MAX_C || K < 1 || K > CV_MAX_K || !(K & 1)) {
-        set_error("%s: Cin=%d Cout=%d K=%d not served (Cin a multiple of 16 from 16, Cout a multiple of 64, both up to %d, K odd and 1 <= K <= %d)",
-                  who, Cin, Cout, K, CV_MAX_C, CV_MAX_K);
-        return DSP_EINVAL;
-    }
-    if (B < 0 || T < 1 || (long)B * T > (1L << 24) || ld_a < Ca || (ld_a % 8) || ld_b < Cb || (ld_b % 8)) {
-        set_error("%s: bad sizes B=%d T=%d row strides %ld / %ld (T >= 1 input rows, B T <= 2^24, a row stride at least the channel count and a "
-                  "multiple of 8)", who, B, T, ld_a, ld_b);
-        return DSP_EINVAL;
-    }
-    return B == 0 ? 1 : 0;
-}
-
 }  // namespace dsp
 
 using namespace dsp;
 
 extern "C" size_t dsp_conv1d_s2_train_workspace_bytes(int phase, int B, int T, int Cin, int Cout, int K)
 {
-    if (B <= 0 || T <= 0 || Cin <= 0 || Cout <= 0 || K <= 0) return 0;
-    const size_t pack = cv_pack_bytes(Cin, Cout, K);
-    if (phase == 0) return pack;
-    const long rows = (long)B * cs_tout(T);
-    return pack + cv_align16((size_t)cv_splits(rows) * (size_t)K * Cin * Cout * sizeof(float)) +
-           cv_align16((size_t)cv_db_chunks(rows) * (size_t)Cout * sizeof(float));
+    return cv_workspace_bytes<2>(phase, B, T, Cin, Cout, K);
 }
 
 extern "C" int dsp_conv1d_s2_train_fwd(const void* x, long ld_x, const void* w, const void* bias, void* y, long ld_y, void* workspace,
@@ -147,19 +120,12 @@ extern "C" int dsp_conv1d_s2_train_fwd(const void* x, long ld_x, const void* w, 
                                        dsp_stream_t stream)
 {
     const char* who = "conv1d_s2_train_fwd";
-    const int rc = cs_check(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_y, Cout);
+    const int rc = cv_fwd_gates<2>(who, "dsp_conv1d_s2_train_workspace_bytes(0, ...)", x, ld_x, w, bias, y, ld_y, workspace, workspace_bytes, act_dtype,
+                                   bias_dtype, B, T, Cin, Cout, K);
     if (rc) return rc < 0 ? rc : DSP_OK;
-    if (!x || !w || !y || y == x || y == w || y == bias || workspace == x || workspace == w || workspace == y || (bias && workspace == bias)) {
-        set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
-    }
-    if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)bias) | ((uintptr_t)y)) & 15) { set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL; }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_conv1d_s2_train_workspace_bytes(0, B, T, Cin, Cout, K)) {
-        set_error("%s: workspace of dsp_conv1d_s2_train_workspace_bytes(0, ...) bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
     hipStream_t st = as_stream(stream);
     const long n = (long)K * Cin * Cout;
-    const int To = cs_tout(T), tiles = (To + CV_ROWS - 1) / CV_ROWS;
+    const int To = cv_tout<2>(T), tiles = (To + CV_ROWS - 1) / CV_ROWS;
     hipLaunchKernelGGL(cv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const cv_u16*)w, (cv_u16*)workspace, Cin, Cout, K, 0);
     DSP_DISPATCH_ELEM_16(act_dtype, E,
                          hipLaunchKernelGGL((cs_conv_kernel<E, true>), dim3((unsigned)((long)B * tiles), (unsigned)((Cout + CV_COLS - 1) / CV_COLS)),
@@ -173,43 +139,21 @@ extern "C" int dsp_conv1d_s2_train_bwd(const void* dy, long ld_dy, const void* x
                                        int K, dsp_stream_t stream)
 {
     const char* who = "conv1d_s2_train_bwd";
-    const int rc = cs_check(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_dy, Cout);
+    const int rc = cv_bwd_gates<2>(who, "dsp_conv1d_s2_train_workspace_bytes(1, ...)", dy, ld_dy, x, ld_x, w, dx, dw, db, workspace, workspace_bytes,
+                                   act_dtype, bias_dtype, B, T, Cin, Cout, K);
     if (rc) return rc < 0 ? rc : DSP_OK;
-    if (!dx && !dw && !db) return DSP_OK;
-    if (!dy || !x || !w) { set_error("%s: null pointer", who); return DSP_EINVAL; }
-    const void* ins[] = {dy, x, w, workspace};
-    void* outs[] = {dx, dw, db};
-    for (int a = 0; a < 3; ++a) {
-        if (!outs[a]) continue;
-        for (const void* in : ins)
-            if (outs[a] == in) { set_error("%s: an output aliases an input or the workspace", who); return DSP_EINVAL; }
-        for (int c = a + 1; c < 3; ++c)
-            if (outs[a] == outs[c]) { set_error("%s: two outputs alias", who); return DSP_EINVAL; }
-    }
-    if (workspace == dy || workspace == x || workspace == w) { set_error("%s: the workspace aliases an input", who); return DSP_EINVAL; }
-    if ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)dx) | ((uintptr_t)dw) | ((uintptr_t)db)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_conv1d_s2_train_workspace_bytes(1, B, T, Cin, Cout, K)) {
-        set_error("%s: workspace of dsp_conv1d_s2_train_workspace_bytes(1, ...) bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
-    const int To = cs_tout(T), rows = B * To;
-    char* base = (char*)workspace;
-    void* wp = base;
-    float* part_w = (float*)(base + cv_pack_bytes(Cin, Cout, K));
-    float* part_b = (float*)((char*)part_w + cv_align16((size_t)cv_splits(rows) * (size_t)K * Cin * Cout * sizeof(float)));
+    const CvWorkspace ws = cv_carve<2>(workspace, B, T, Cin, Cout, K);
     hipStream_t st = as_stream(stream);
     if (dx) {    // both parities of the rows of dx in one launch: a stride-1 convolution each over dy, Nin = Cout, Nout = Cin
         const long n = (long)K * Cin * Cout;
         const int tiles = ((T + 1) / 2 + CV_ROWS - 1) / CV_ROWS;
-        hipLaunchKernelGGL(cv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const cv_u16*)w, (cv_u16*)wp, Cin, Cout, K, 1);
+        hipLaunchKernelGGL(cv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const cv_u16*)w, (cv_u16*)ws.wp, Cin, Cout, K, 1);
         DSP_DISPATCH_ELEM_16(act_dtype, E,
                              hipLaunchKernelGGL((cs_conv_kernel<E, false>),
                                                 dim3((unsigned)((long)B * tiles), (unsigned)((Cin + CV_COLS - 1) / CV_COLS), 2u), dim3(256), 0, st,
-                                                (const E*)dy, ld_dy, (const E*)wp, nullptr, bias_dtype, (E*)dx, (long)Cin, To, T, Cout, Cin, K, tiles));
+                                                (const E*)dy, ld_dy, (const E*)ws.wp, nullptr, bias_dtype, (E*)dx, (long)Cin, cv_tout<2>(T), T, Cout, Cin, K,
+                                                tiles));
     }
-    if (dw) DSP_DISPATCH_ELEM_16(act_dtype, E, (cv_launch_wgrad<E, 2>(st, dy, ld_dy, x, ld_x, part_w, dw, To, T, rows, Cin, Cout, K)));
-    if (db) DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_db<E>(st, dy, ld_dy, part_b, db, bias_dtype, rows, Cout));
+    DSP_DISPATCH_ELEM_16(act_dtype, E, (cv_launch_param_grads<E, 2>(st, dy, ld_dy, x, ld_x, ws, dw, db, bias_dtype, B, T, Cin, Cout, K)));
     return check_launch(who);
 }

@@ -1,9 +1,13 @@
 // conv1d_train.h — what the two channels-last Conv1d training operators share (conv1d_train.hip: stride 1; conv1d_stride2_train.hip: stride 2):
 // the operand types and the fragment read of the "NT" v_mfma_f32_32x32x16 products, the weight re-lay, the weight gradient over row splits with
-// its ascending merge, and the chunked column sums of the bias gradient.  Everything here is a template, an inline function or has internal
+// its ascending merge, the chunked column sums of the bias gradient, and the host half behind the C entries, written once for a STRIDE of
+// 1 or 2: the size check, the workspace question and its carving, the gate sequences of the two entries.  The .hip files keep their
+// extern "C" entries and the convolution launches, which differ.  Everything here is a template, an inline function or has internal
 // linkage: each of the two translation units gets its own copy.
 #pragma once
 #include "common.h"
+#include "host_gates.h"
+#include "partial_merge.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -148,8 +152,7 @@ __global__ __launch_bounds__(256) void cv_wgrad_merge_kernel(const float* __rest
 {
     const long n = (long)K * Cin * Cout, e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
-    float acc = 0.f;
-    for (int s = 0; s < nsplit; ++s) acc += part[(size_t)s * n + e];
+    const float acc = merge_plain(part, nsplit, (size_t)n, (size_t)e);
     const int k = (int)(e / ((long)Cin * Cout));
     const int rem = (int)(e - (long)k * Cin * Cout);
     const int co = rem / Cin, ci = rem - co * Cin;
@@ -175,34 +178,111 @@ static __global__ __launch_bounds__(256) void cv_db_merge_kernel(const float* __
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= Cout) return;
-    float acc = 0.f;
-    for (int k = 0; k < nchunks; ++k) acc += part[(size_t)k * Cout + c];
-    param_store(db, bdtype, c, acc);
+    param_store(db, bdtype, c, merge_plain(part, nchunks, (size_t)Cout, (size_t)c));
 }
 
-static inline size_t cv_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-static inline size_t cv_pack_bytes(int Cin, int Cout, int K) { return cv_align16((size_t)K * Cin * Cout * 2); }
+static inline size_t cv_pack_bytes(int Cin, int Cout, int K) { return a16((size_t)K * Cin * Cout * 2); }
 static inline int cv_splits(long BT) { return (int)((BT + CV_WG_ROWS - 1) / CV_WG_ROWS); }
 static inline int cv_db_chunks(long BT) { return (int)((BT + CV_DB_CHUNK - 1) / CV_DB_CHUNK); }
 
-// dW and db of both operators: rows = B * (rows of dy per sample); part_w / part_b as the workspace questions lay them out
-template <typename E, int STRIDE>
-static void cv_launch_wgrad(hipStream_t st, const void* dy, long ld_dy, const void* x, long ld_x, float* part_w, void* dw, int T, int Tx, int rows,
-                            int Cin, int Cout, int K)
+// ---------------------------------------------------------------- the host half behind the C entries, STRIDE 1 or 2
+template <int STRIDE> static inline int cv_tout(int T) { return STRIDE == 1 ? T : (T - 1) / 2 + 1; }      // rows of y and dy per sample
+
+// what the entry points check; 1: nothing to do (no rows), 0: go on, < 0: refused.  Stride 2 takes Cin in steps of 16 (the filterbank's 80).
+template <int STRIDE>
+static int cv_check(const char* who, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, long ld_a, int Ca, long ld_b, int Cb)
 {
-    const int ci_tiles = (Cin + CV_WG_TILE - 1) / CV_WG_TILE, co_tiles = (Cout + CV_WG_TILE - 1) / CV_WG_TILE, nsplit = cv_splits(rows);
-    const size_t nw = (size_t)K * Cin * Cout;
-    hipLaunchKernelGGL((cv_wgrad_kernel<E, STRIDE>), dim3((unsigned)(ci_tiles * co_tiles), (unsigned)K, (unsigned)nsplit), dim3(256), 0, st,
-                       (const E*)dy, ld_dy, (const E*)x, ld_x, part_w, T, Tx, rows, Cin, Cout, K, ci_tiles);
-    hipLaunchKernelGGL((cv_wgrad_merge_kernel<E>), dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, part_w, nsplit, Cin, Cout, K, (E*)dw);
+    constexpr int CIN_STEP = STRIDE == 1 ? 64 : 16;
+    if ((act_dtype != DSP_F16 && act_dtype != DSP_BF16) || (bias_dtype != act_dtype && bias_dtype != DSP_F32)) {
+        set_error("%s: dtype codes %d (x, W, y and their gradients: fp16 or bf16) / %d (bias, db: the same, or fp32)", who, act_dtype, bias_dtype);
+        return DSP_EINVAL;
+    }
+    if (Cin < CIN_STEP || Cout < 64 || (Cin % CIN_STEP) || (Cout % 64) || Cin > CV_MAX_C || Cout > CV_MAX_C || K < 1 || K > CV_MAX_K || !(K & 1)) {
+        if (STRIDE == 1)
+            set_error("%s: Cin=%d Cout=%d K=%d not served (channels multiples of 64 up to %d, K odd and 1 <= K <= %d)", who, Cin, Cout, K, CV_MAX_C,
+                      CV_MAX_K);
+        else
+            set_error("%s: Cin=%d Cout=%d K=%d not served (Cin a multiple of 16 from 16, Cout a multiple of 64, both up to %d, K odd and 1 <= K <= %d)",
+                      who, Cin, Cout, K, CV_MAX_C, CV_MAX_K);
+        return DSP_EINVAL;
+    }
+    if (B < 0 || T < 1 || (long)B * T > (1L << 24) || ld_a < Ca || (ld_a % 8) || ld_b < Cb || (ld_b % 8)) {
+        if (STRIDE == 1)
+            set_error("%s: bad sizes B=%d T=%d row strides %ld / %ld (T >= 1, B T <= 2^24, a row stride at least the channel count and a multiple of 8)",
+                      who, B, T, ld_a, ld_b);
+        else
+            set_error("%s: bad sizes B=%d T=%d row strides %ld / %ld (T >= 1 input rows, B T <= 2^24, a row stride at least the channel count and a "
+                      "multiple of 8)", who, B, T, ld_a, ld_b);
+        return DSP_EINVAL;
+    }
+    return B == 0 ? 1 : 0;
 }
-template <typename E>
-static void cv_launch_db(hipStream_t st, const void* dy, long ld_dy, float* part_b, void* db, int bdtype, int rows, int Cout)
+
+// the workspace: the re-laid weight (phase 0: the forward stops here) | [splits][K][Cout][Cin] dW partials | [chunks][Cout] db partials
+static inline size_t cv_wpart_bytes(long rows, int Cin, int Cout, int K) { return a16((size_t)cv_splits(rows) * (size_t)K * Cin * Cout * sizeof(float)); }
+template <int STRIDE> static size_t cv_workspace_bytes(int phase, int B, int T, int Cin, int Cout, int K)
 {
-    const int nchunks = cv_db_chunks(rows);
-    hipLaunchKernelGGL((cv_db_part_kernel<E>), dim3((unsigned)nchunks, (unsigned)(Cout / 64)), dim3(256), 0, st, (const E*)dy, ld_dy, rows, Cout,
-                       part_b);
-    hipLaunchKernelGGL(cv_db_merge_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, st, part_b, nchunks, Cout, db, bdtype);
+    if (B <= 0 || T <= 0 || Cin <= 0 || Cout <= 0 || K <= 0) return 0;
+    const size_t pack = cv_pack_bytes(Cin, Cout, K);
+    if (phase == 0) return pack;
+    const long rows = (long)B * cv_tout<STRIDE>(T);
+    return pack + cv_wpart_bytes(rows, Cin, Cout, K) + a16((size_t)cv_db_chunks(rows) * (size_t)Cout * sizeof(float));
+}
+struct CvWorkspace { void* wp; float* part_w; float* part_b; };
+template <int STRIDE> static CvWorkspace cv_carve(void* workspace, int B, int T, int Cin, int Cout, int K)
+{
+    float* part_w = (float*)((char*)workspace + cv_pack_bytes(Cin, Cout, K));
+    return {workspace, part_w, (float*)((char*)part_w + cv_wpart_bytes((long)B * cv_tout<STRIDE>(T), Cin, Cout, K))};
+}
+
+// the gates of the two entries, in the order in which they report; asked: the entry's workspace question as its message names it
+template <int STRIDE>
+static int cv_fwd_gates(const char* who, const char* asked, const void* x, long ld_x, const void* w, const void* bias, const void* y, long ld_y,
+                        const void* workspace, size_t workspace_bytes, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K)
+{
+    const int rc = cv_check<STRIDE>(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_y, Cout);
+    if (rc) return rc;
+    if (!x || !w || !y || y == x || y == w || y == bias || workspace == x || workspace == w || workspace == y || (bias && workspace == bias)) {
+        set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
+    }
+    DSP_GATE(tensors16_gate(who, x, w, bias, y));
+    return workspace_gate(who, workspace, workspace_bytes, cv_workspace_bytes<STRIDE>(0, B, T, Cin, Cout, K), asked);
+}
+template <int STRIDE>
+static int cv_bwd_gates(const char* who, const char* asked, const void* dy, long ld_dy, const void* x, long ld_x, const void* w, void* dx, void* dw,
+                        void* db, const void* workspace, size_t workspace_bytes, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K)
+{
+    const int rc = cv_check<STRIDE>(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_dy, Cout);
+    if (rc) return rc;
+    if (!dx && !dw && !db) return 1;
+    if (!dy || !x || !w) { set_error("%s: null pointer", who); return DSP_EINVAL; }
+    const void* ins[] = {dy, x, w, workspace};
+    void* outs[] = {dx, dw, db};
+    DSP_GATE(alias_gate(who, outs, 3, ins, 4, "an output aliases an input or the workspace", "two outputs alias"));
+    if (workspace == dy || workspace == x || workspace == w) { set_error("%s: the workspace aliases an input", who); return DSP_EINVAL; }
+    DSP_GATE(tensors16_gate(who, dy, x, w, dx, dw, db));
+    return workspace_gate(who, workspace, workspace_bytes, cv_workspace_bytes<STRIDE>(1, B, T, Cin, Cout, K), asked);
+}
+
+// dW and db of a backward over the B * cv_tout(T) rows of dy, from the carved workspace
+template <typename E, int STRIDE>
+static void cv_launch_param_grads(hipStream_t st, const void* dy, long ld_dy, const void* x, long ld_x, const CvWorkspace& ws, void* dw, void* db,
+                                  int bdtype, int B, int T, int Cin, int Cout, int K)
+{
+    const int To = cv_tout<STRIDE>(T), rows = B * To;
+    if (dw) {
+        const int ci_tiles = (Cin + CV_WG_TILE - 1) / CV_WG_TILE, co_tiles = (Cout + CV_WG_TILE - 1) / CV_WG_TILE, nsplit = cv_splits(rows);
+        const size_t nw = (size_t)K * Cin * Cout;
+        hipLaunchKernelGGL((cv_wgrad_kernel<E, STRIDE>), dim3((unsigned)(ci_tiles * co_tiles), (unsigned)K, (unsigned)nsplit), dim3(256), 0, st,
+                           (const E*)dy, ld_dy, (const E*)x, ld_x, ws.part_w, To, T, rows, Cin, Cout, K, ci_tiles);
+        hipLaunchKernelGGL((cv_wgrad_merge_kernel<E>), dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, ws.part_w, nsplit, Cin, Cout, K, (E*)dw);
+    }
+    if (db) {
+        const int nchunks = cv_db_chunks(rows);
+        hipLaunchKernelGGL((cv_db_part_kernel<E>), dim3((unsigned)nchunks, (unsigned)(Cout / 64)), dim3(256), 0, st, (const E*)dy, ld_dy, rows, Cout,
+                           ws.part_b);
+        hipLaunchKernelGGL(cv_db_merge_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, st, ws.part_b, nchunks, Cout, db, bdtype);
+    }
 }
 
 }  // namespace dsp

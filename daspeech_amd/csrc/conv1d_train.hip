@@ -20,8 +20,7 @@
 //   cv_wgrad_kernel   a workgroup of 4 waves owns (128 co x 128 ci, one tap, one split of DSP_CONV1D_TRAIN_WGRAD_ROWS rows of the flattened
 //                     B*T); it walks its rows 64 at a time in ascending order, dy and the tap-shifted x staged TRANSPOSED (row index
 //                     contiguous, two rows per 32-bit LDS write), and writes one fp32 partial [split][K][Cout][Cin];
-//   cv_wgrad_merge_kernel   adds the splits in ASCENDING order, rounds once and writes nn.Conv1d's layout.
-//   cv_db_part_kernel / cv_db_merge_kernel   column sums of dy over chunks of 256 rows, then the chunks in ascending order.
+//   cv_wgrad_merge_kernel, cv_db_part_kernel / cv_db_merge_kernel   the splits, and dy's column sums over chunks of 256 rows, in ASCENDING order.
 // No float atomics, no hand-off between workgroups: the same inputs give the same bits on every call, and dx, dW, db are separate launches, so
 // leaving one out does not change the others.  Every row is computed, padded frames included.
 #include "conv1d_train.h"
@@ -95,26 +94,6 @@ __global__ __launch_bounds__(256) void cv_conv_kernel(const E* __restrict__ in, 
     }
 }
 
-// what the entry points check; 1: nothing to do (no rows), 0: go on, < 0: refused
-static int cv_check(const char* who, int act_dtype, int bias_dtype, int B, int T, int Cin, int Cout, int K, long ld_a, int Ca, long ld_b, int Cb)
-{
-    if ((act_dtype != DSP_F16 && act_dtype != DSP_BF16) || (bias_dtype != act_dtype && bias_dtype != DSP_F32)) {
-        set_error("%s: dtype codes %d (x, W, y and their gradients: fp16 or bf16) / %d (bias, db: the same, or fp32)", who, act_dtype, bias_dtype);
-        return DSP_EINVAL;
-    }
-    if (Cin < 64 || Cout < 64 || (Cin % 64) || (Cout % 64) || Cin > CV_MAX_C || Cout > CV_MAX_C || K < 1 || K > CV_MAX_K || !(K & 1)) {
-        set_error("%s: Cin=%d Cout=%d K=%d not served (channels multiples of 64 up to %d, K odd and 1 <= K <= %d)", who, Cin, Cout, K, CV_MAX_C,
-                  CV_MAX_K);
-        return DSP_EINVAL;
-    }
-    if (B < 0 || T < 1 || (long)B * T > (1L << 24) || ld_a < Ca || (ld_a % 8) || ld_b < Cb || (ld_b % 8)) {
-        set_error("%s: bad sizes B=%d T=%d row strides %ld / %ld (T >= 1, B T <= 2^24, a row stride at least the channel count and a multiple of 8)",
-                  who, B, T, ld_a, ld_b);
-        return DSP_EINVAL;
-    }
-    return B == 0 ? 1 : 0;
-}
-
 template <typename E>
 static void cv_launch_conv(hipStream_t st, const void* in, long ld_in, const void* w, void* wp, int transposed, const void* bias, int bdtype,
                            void* out, long ld_out, int B, int T, int Nin, int Nout, int Cin, int Cout, int K)
@@ -132,12 +111,7 @@ using namespace dsp;
 
 extern "C" size_t dsp_conv1d_train_workspace_bytes(int phase, int B, int T, int Cin, int Cout, int K)
 {
-    if (B <= 0 || T <= 0 || Cin <= 0 || Cout <= 0 || K <= 0) return 0;
-    const size_t pack = cv_pack_bytes(Cin, Cout, K);
-    if (phase == 0) return pack;
-    const long BT = (long)B * T;
-    return pack + cv_align16((size_t)cv_splits(BT) * (size_t)K * Cin * Cout * sizeof(float)) +
-           cv_align16((size_t)cv_db_chunks(BT) * (size_t)Cout * sizeof(float));
+    return cv_workspace_bytes<1>(phase, B, T, Cin, Cout, K);
 }
 
 extern "C" int dsp_conv1d_train_fwd(const void* x, long ld_x, const void* w, const void* bias, void* y, long ld_y, void* workspace,
@@ -145,16 +119,9 @@ extern "C" int dsp_conv1d_train_fwd(const void* x, long ld_x, const void* w, con
                                     dsp_stream_t stream)
 {
     const char* who = "conv1d_train_fwd";
-    const int rc = cv_check(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_y, Cout);
+    const int rc = cv_fwd_gates<1>(who, "dsp_conv1d_train_workspace_bytes(0, ...)", x, ld_x, w, bias, y, ld_y, workspace, workspace_bytes, act_dtype,
+                                   bias_dtype, B, T, Cin, Cout, K);
     if (rc) return rc < 0 ? rc : DSP_OK;
-    if (!x || !w || !y || y == x || y == w || y == bias || workspace == x || workspace == w || workspace == y || (bias && workspace == bias)) {
-        set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
-    }
-    if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)bias) | ((uintptr_t)y)) & 15) { set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL; }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_conv1d_train_workspace_bytes(0, B, T, Cin, Cout, K)) {
-        set_error("%s: workspace of dsp_conv1d_train_workspace_bytes(0, ...) bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
     hipStream_t st = as_stream(stream);
     DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_conv<E>(st, x, ld_x, w, workspace, 0, bias, bias_dtype, y, ld_y, B, T, Cin, Cout, Cin, Cout, K));
     return check_launch(who);
@@ -165,36 +132,13 @@ extern "C" int dsp_conv1d_train_bwd(const void* dy, long ld_dy, const void* x, l
                                     int K, dsp_stream_t stream)
 {
     const char* who = "conv1d_train_bwd";
-    const int rc = cv_check(who, act_dtype, bias_dtype, B, T, Cin, Cout, K, ld_x, Cin, ld_dy, Cout);
+    const int rc = cv_bwd_gates<1>(who, "dsp_conv1d_train_workspace_bytes(1, ...)", dy, ld_dy, x, ld_x, w, dx, dw, db, workspace, workspace_bytes,
+                                   act_dtype, bias_dtype, B, T, Cin, Cout, K);
     if (rc) return rc < 0 ? rc : DSP_OK;
-    if (!dx && !dw && !db) return DSP_OK;
-    if (!dy || !x || !w) { set_error("%s: null pointer", who); return DSP_EINVAL; }
-    const void* ins[] = {dy, x, w, workspace};
-    void* outs[] = {dx, dw, db};
-    for (int a = 0; a < 3; ++a) {
-        if (!outs[a]) continue;
-        for (const void* in : ins)
-            if (outs[a] == in) { set_error("%s: an output aliases an input or the workspace", who); return DSP_EINVAL; }
-        for (int c = a + 1; c < 3; ++c)
-            if (outs[a] == outs[c]) { set_error("%s: two outputs alias", who); return DSP_EINVAL; }
-    }
-    if (workspace == dy || workspace == x || workspace == w) { set_error("%s: the workspace aliases an input", who); return DSP_EINVAL; }
-    if ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)dx) | ((uintptr_t)dw) | ((uintptr_t)db)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_conv1d_train_workspace_bytes(1, B, T, Cin, Cout, K)) {
-        set_error("%s: workspace of dsp_conv1d_train_workspace_bytes(1, ...) bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
-    const int BT = B * T;
-    char* base = (char*)workspace;
-    void* wp = base;
-    float* part_w = (float*)(base + cv_pack_bytes(Cin, Cout, K));
-    float* part_b = (float*)((char*)part_w + cv_align16((size_t)cv_splits(BT) * (size_t)K * Cin * Cout * sizeof(float)));
+    const CvWorkspace ws = cv_carve<1>(workspace, B, T, Cin, Cout, K);
     hipStream_t st = as_stream(stream);
     if (dx)      // the forward kernel on dy: Nin = Cout, Nout = Cin, the weight [K][Cin][Cout] with the taps reversed
-        DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_conv<E>(st, dy, ld_dy, w, wp, 1, nullptr, bias_dtype, dx, (long)Cin, B, T, Cout, Cin, Cin, Cout, K));
-    if (dw) DSP_DISPATCH_ELEM_16(act_dtype, E, (cv_launch_wgrad<E, 1>(st, dy, ld_dy, x, ld_x, part_w, dw, T, T, BT, Cin, Cout, K)));
-    if (db) DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_db<E>(st, dy, ld_dy, part_b, db, bias_dtype, BT, Cout));
+        DSP_DISPATCH_ELEM_16(act_dtype, E, cv_launch_conv<E>(st, dy, ld_dy, w, ws.wp, 1, nullptr, bias_dtype, dx, (long)Cin, B, T, Cout, Cin, Cin, Cout, K));
+    DSP_DISPATCH_ELEM_16(act_dtype, E, (cv_launch_param_grads<E, 1>(st, dy, ld_dy, x, ld_x, ws, dw, db, bias_dtype, B, T, Cin, Cout, K)));
     return check_launch(who);
 }

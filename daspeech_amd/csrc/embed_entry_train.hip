@@ -42,6 +42,7 @@
 //     dsp_pos_add_bwd       n * (2 * C * es [dx] + C * ts [dalpha] + 4)
 // All of it is row traffic at a few MB per call: the bound is these bytes plus the launch latencies.
 #include "common.h"
+#include "host_gates.h"
 #include "philox.h"
 #include "embed_rows.h"
 #include "row_compact.h"
@@ -371,11 +372,10 @@ __global__ __launch_bounds__(256) void pa_dalpha_kernel(const float* __restrict_
     if (threadIdx.x == 0) param_store(dalpha, alpha_dtype, 0, (float)acc);
 }
 
-static size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static long ee_max_big(int64_t n) { return (long)(2 * n / (EE_SORT_MAX + 1)) + 1; }
 static long ee_max_chunks(int64_t n, int K) { return (long)((2 * n + EG_CHUNK - 1) / EG_CHUNK) + (K < 2 * n ? K : 2 * n); }
 // ints of the index: counts [K], cursor [K], offs [K], cstart [K + 1], nbig [1], big [max_big], perm [2n]
-static size_t ee_int_bytes(int64_t n, int K) { return up16(((size_t)4 * K + 2 + (size_t)ee_max_big(n) + (size_t)2 * n) * sizeof(int32_t)); }
+static size_t ee_int_bytes(int64_t n, int K) { return a16(((size_t)4 * K + 2 + (size_t)ee_max_big(n) + (size_t)2 * n) * sizeof(int32_t)); }
 
 static int ee_check(const char* who, int dtype, int64_t n, int V, int NP, int C, int64_t pad, unsigned int thr)
 {
@@ -416,13 +416,13 @@ static int ee_fwd(const char* who, const int64_t* tokens, long ld_tok, const voi
                   float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* y, int32_t* tok32,
                   int32_t* pos32, int dtype, int B, int L, int V, int NP, int C, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     if (B < 0 || L < 0) { set_error("%s: bad sizes B=%d L=%d", who, B, L); return DSP_EINVAL; }
     const int rc = ee_check(who, dtype, (int64_t)B * L, V, NP, C, pad, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (ld_tok < L) { set_error("%s: token row stride %ld below L=%d", who, ld_tok, L); return DSP_EINVAL; }
     if (!tokens || !E || !P || !y || !tok32 || !pos32 || y == E || y == P) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
-    if (((((uintptr_t)E) | ((uintptr_t)P) | ((uintptr_t)y)) & 15) || (((uintptr_t)tokens) & 7) || ((((uintptr_t)tok32) | ((uintptr_t)pos32)) & 3)) {
+    if (!on16(E, P, y) || (((uintptr_t)tokens) & 7) || ((((uintptr_t)tok32) | ((uintptr_t)pos32)) & 3)) {
         set_error("%s: tables and y must be 16-byte aligned, tokens 8-byte", who); return DSP_EINVAL;
     }
     const int tiles = (L + EE_TILE - 1) / EE_TILE;
@@ -453,18 +453,18 @@ extern "C" size_t dsp_embed_entry_bwd_workspace_bytes(int64_t n, int V, int NP, 
 {
     if (n <= 0 || V < 1 || NP < 1 || C < 1) return 0;
     const int K = V + NP;
-    return ee_int_bytes(n, K) + (thr ? up16((size_t)n * C * sizeof(float)) : 0) + up16((size_t)ee_max_chunks(n, K) * C * sizeof(float));
+    return ee_int_bytes(n, K) + (thr ? a16((size_t)n * C * sizeof(float)) : 0) + a16((size_t)ee_max_chunks(n, K) * C * sizeof(float));
 }
 
 static int ee_bwd(const char* who, const void* dy, const int32_t* tok32, const int32_t* pos32, int64_t pad, float embed_scale, float keep_scale,
                   unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dE, void* dP, void* workspace,
                   size_t workspace_bytes, int dtype, int64_t n, int V, int NP, int C, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = ee_check(who, dtype, n, V, NP, C, pad, thr);
     if (rc < 0) return rc;
     if (!dE && !dP) return DSP_OK;
-    if (((((uintptr_t)dy) | ((uintptr_t)dE) | ((uintptr_t)dP)) & 15) || (dE && dE == dP) || (dy && (dy == dE || dy == dP))) {
+    if (!on16(dy, dE, dP) || (dE && dE == dP) || (dy && (dy == dE || dy == dP))) {
         set_error("%s: gradients must be 16-byte aligned and distinct", who); return DSP_EINVAL;
     }
     const int es = elem_size(dtype);
@@ -477,9 +477,9 @@ static int ee_bwd(const char* who, const void* dy, const int32_t* tok32, const i
     }
     if (!dy || !tok32 || !pos32) { set_error("%s: null pointer", who); return DSP_EINVAL; }
     const size_t need = dsp_embed_entry_bwd_workspace_bytes(n, V, NP, C, thr);
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need) {
+    if (!workspace || !on16(workspace) || workspace_bytes < need) {
         set_error("%s: workspace of %zu bytes (16-byte aligned) needed, see dsp_embed_entry_bwd_workspace_bytes", who, need);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
+        return workspace && on16(workspace) ? DSP_ENOSPC : DSP_EINVAL;
     }
     const int K = V + NP, N = (int)n;
     const long max_big = ee_max_big(n), max_chunks = ee_max_chunks(n, K);
@@ -492,7 +492,7 @@ static int ee_bwd(const char* who, const void* dy, const int32_t* tok32, const i
     int32_t* perm = big + max_big;                                         // [2n]
     char* fl = (char*)workspace + ee_int_bytes(n, K);
     float* g32 = thr ? (float*)fl : nullptr;
-    float* partial = (float*)(fl + (thr ? up16((size_t)n * C * sizeof(float)) : 0));
+    float* partial = (float*)(fl + (thr ? a16((size_t)n * C * sizeof(float)) : 0));
     const int e0 = dE ? 0 : N, e1 = dP ? 2 * N : N;                        // the entries of a table that is not asked for do not exist
     const EeKeys ks{tok32, pos32, N, V, NP, (int)pad};
     hipLaunchKernelGGL(ee_zero_kernel, dim3(wave_grid(((long)2 * K + 63) / 64)), dim3(256), 0, st, counts, (long)2 * K);      // counts and cursor
@@ -542,14 +542,14 @@ static int pa_fwd(const char* who, const void* x, long ld_x, const unsigned char
                   float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* y, int32_t* pos32,
                   int act_dtype, int tab_dtype, int alpha_dtype, int B, int N, int NT, int C, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     if (B < 0 || N < 0 || pad < 0) { set_error("%s: bad sizes B=%d N=%d pad=%d", who, B, N, pad); return DSP_EINVAL; }
     const int rc = pa_check(who, act_dtype, tab_dtype, alpha_dtype, (int64_t)B * N, NT, C, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     const int VE = 16 / elem_size(act_dtype);
     if (ld_x < C || (ld_x % VE)) { set_error("%s: row pitch %ld (>= C, a multiple of %d)", who, ld_x, VE); return DSP_EINVAL; }
     if (!x || !padding_mask || !tab || !alpha || !y || !pos32 || y == x || y == tab) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
-    if ((((uintptr_t)x) | ((uintptr_t)tab) | ((uintptr_t)y)) & 15) { set_error("%s: x, the table and y must be 16-byte aligned", who); return DSP_EINVAL; }
+    if (!on16(x, tab, y)) { set_error("%s: x, the table and y must be 16-byte aligned", who); return DSP_EINVAL; }
     const int tiles = (N + EE_TILE - 1) / EE_TILE;
     DSP_DISPATCH_ELEM(act_dtype, T, hipLaunchKernelGGL(pa_fwd_kernel<T>, dim3((unsigned)B * (unsigned)tiles), dim3(256), 0, as_stream(stream),
                                                        (const T*)x, ld_x, padding_mask, tab, tab_dtype, alpha, alpha_dtype, pad, keep_scale,
@@ -576,14 +576,14 @@ extern "C" int dsp_pos_add_fwd_state(const void* x, long ld_x, const unsigned ch
 extern "C" size_t dsp_pos_add_bwd_workspace_bytes(int64_t R)
 {
     if (R <= 0) return 0;
-    return up16((size_t)((R + PA_CHUNK - 1) / PA_CHUNK) * 2 * sizeof(float));
+    return a16((size_t)((R + PA_CHUNK - 1) / PA_CHUNK) * 2 * sizeof(float));
 }
 
 static int pa_bwd(const char* who, const void* dy, const void* tab, const int32_t* pos32, float keep_scale, unsigned int thr, uint64_t seed,
                   uint64_t offset, const uint64_t* rng_state, void* dx, void* dalpha, void* workspace, size_t workspace_bytes, int act_dtype,
                   int tab_dtype, int alpha_dtype, int64_t R, int NT, int C, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = pa_check(who, act_dtype, tab_dtype, alpha_dtype, R, NT, C, thr);
     if (rc < 0) return rc;
     if (!dx && !dalpha) return DSP_OK;
@@ -596,11 +596,8 @@ static int pa_bwd(const char* who, const void* dy, const void* tab, const int32_
         return DSP_OK;
     }
     if (!dy || (dalpha && (!tab || !pos32)) || dx == dy) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
-    if ((((uintptr_t)dy) | ((uintptr_t)tab) | ((uintptr_t)dx)) & 15) { set_error("%s: dy, the table and dx must be 16-byte aligned", who); return DSP_EINVAL; }
-    if (dalpha && (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_pos_add_bwd_workspace_bytes(R))) {
-        set_error("%s: workspace of dsp_pos_add_bwd_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    if (!on16(dy, tab, dx)) { set_error("%s: dy, the table and dx must be 16-byte aligned", who); return DSP_EINVAL; }
+    if (dalpha) DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_pos_add_bwd_workspace_bytes(R), "dsp_pos_add_bwd_workspace_bytes"));
     const long nchunks = (long)((R + PA_CHUNK - 1) / PA_CHUNK);
     float* part = dalpha ? (float*)workspace : (float*)nullptr;
     if (dx && !thr) {                                                      // dx = dy: a caller that can hand dy on passes dx = NULL

@@ -4,6 +4,7 @@
 // destination's chunk sums are added in chunk order.  How the lists (counts, offs, cstart, perm) come about is the business of the caller.
 #pragma once
 #include "common.h"
+#include "host_gates.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -13,7 +14,7 @@ constexpr int GG_MAX_WG = 1024;                       // 4 waves each: a launch 
 
 static inline bool aligned16(const void* a, const void* b, size_t row_a, size_t row_b)
 {
-    return (((uintptr_t)a | (uintptr_t)b | row_a | row_b) & 15) == 0;
+    return on16(a, b) && ((row_a | row_b) & 15) == 0;
 }
 
 static inline unsigned wave_grid(long waves) { const long g = (waves + 3) / 4; return (unsigned)(g < 1 ? 1 : (g > GG_MAX_WG ? GG_MAX_WG : g)); }

@@ -16,6 +16,7 @@
 // by index, not by address — so that its summation order, and with it every bit of S, does not depend on where the gradients were allocated.
 // No LDS beyond the reductions' few words, no atomics, no scratch.
 #include "common.h"
+#include "host_gates.h"
 #include "../../include/daspeech_optim.h"
 
 namespace dsp {
@@ -308,7 +309,7 @@ using namespace dsp;
 extern "C" size_t dsp_fp16_optim_workspace_bytes(int64_t n_items)
 {
     if (n_items <= 0) return 0;
-    return (((size_t)n_items * sizeof(float)) + 15) & ~(size_t)15;
+    return a16((size_t)n_items * sizeof(float));
 }
 
 extern "C" int dsp_fp16_optim_grad_sumsq(const void* const* grads, int dtype, int N, const int64_t* items, int64_t n_items, int chunk,

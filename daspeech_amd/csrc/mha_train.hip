@@ -27,6 +27,7 @@
 //
 // The dropout mask is never stored: element e = ((b H + h) N + i) Mp + j, Mp = M rounded up to a multiple of 4, of the rule in philox.h.
 #include "common.h"
+#include "host_gates.h"
 #include "philox.h"
 #include "ra_frag.h"
 #include "../../include/daspeech_decode.h"
@@ -420,16 +421,14 @@ static int mh_fwd(const char* who, const void* q, long ldq, const void* k, const
                   unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* out, float* lse, int act_dtype, int B, int N,
                   int M, int H, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = mh_check(who, act_dtype, B, N, M, H, ldq, ldkv, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!q || !k || !v || !out || !lse || out == q || out == k || out == v || (const void*)lse == q || (const void*)lse == k || (const void*)lse == v ||
         (const void*)lse == out) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
-    if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)out) | ((uintptr_t)lse)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
+    DSP_GATE(tensors16_gate(who, q, k, v, out, lse));
     const unsigned grid = (unsigned)((long)B * H * ((N + MH_OWN - 1) / MH_OWN));
     hipStream_t st = as_stream(stream);
     MH_DISPATCH(act_dtype, hipLaunchKernelGGL((mh_fwd_kernel<E>), dim3(grid), dim3(MH_THREADS), 0, st, (const E*)q, ldq, (const E*)k, (const E*)v, ldkv, pad_mask,
@@ -455,34 +454,23 @@ extern "C" int dsp_mha_train_fwd_state(const void* q, long ldq, const void* k, c
 extern "C" size_t dsp_mha_train_workspace_bytes(int B, int N, int M, int H)
 {
     if (B <= 0 || N <= 0 || M <= 0 || H <= 0) return 0;
-    return ((size_t)B * (size_t)H * (size_t)N * sizeof(float) + 15) & ~(size_t)15;      // D [B,H,N]
+    return a16((size_t)B * (size_t)H * (size_t)N * sizeof(float));      // D [B,H,N]
 }
 
 static int mh_bwd(const char* who, const void* dout, const void* q, long ldq, const void* k, const void* v, long ldkv, const unsigned char* pad_mask,
                   const float* lse, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dq,
                   void* dk, void* dv, void* workspace, size_t workspace_bytes, int act_dtype, int B, int N, int M, int H, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = mh_check(who, act_dtype, B, N, M, H, ldq, ldkv, thr);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dq && !dk && !dv) return DSP_OK;
     if (!dout || !q || !k || !v || !lse) { set_error("%s: null pointer", who); return DSP_EINVAL; }
     const void* ins[] = {dout, q, k, v, lse, pad_mask};
     void* outs[] = {dq, dk, dv, workspace};
-    for (int a = 0; a < 4; ++a) {
-        if (!outs[a]) continue;
-        for (const void* in : ins)
-            if (outs[a] == in) { set_error("%s: an output aliases an input", who); return DSP_EINVAL; }
-        for (int c = a + 1; c < 4; ++c)
-            if (outs[a] == outs[c]) { set_error("%s: two outputs alias", who); return DSP_EINVAL; }
-    }
-    if ((((uintptr_t)dout) | ((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)lse) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_mha_train_workspace_bytes(B, N, M, H)) {
-        set_error("%s: workspace of dsp_mha_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    DSP_GATE(alias_gate(who, outs, 4, ins, 6, "an output aliases an input", "two outputs alias"));
+    DSP_GATE(tensors16_gate(who, dout, q, k, v, lse, dq, dk, dv));
+    DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_mha_train_workspace_bytes(B, N, M, H), "dsp_mha_train_workspace_bytes"));
     float* dsum = (float*)workspace;
     hipStream_t st = as_stream(stream);
 #define MH_IN (const E*)dout, (const E*)q, ldq, (const E*)k, (const E*)v, ldkv, pad_mask, lse

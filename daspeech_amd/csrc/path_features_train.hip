@@ -22,6 +22,7 @@
 // a few MB at the training shapes: the bound is the launch latency.  The tile sizes are read off the shapes (B = 32, W = 64: 256
 // forward workgroups; L = 400: 800 backward workgroups), not measured.
 #include "common.h"
+#include "host_gates.h"
 #include "row_compact.h"
 #include "../../include/daspeech_decode.h"
 
@@ -155,7 +156,7 @@ extern "C" int dsp_path_features_fwd(const void* features, long ld_f, const void
     const int VE = 16 / elem_size(dtype);
     if (ld_f < C || (ld_f % VE)) { set_error("%s: row pitch %ld (>= C, a multiple of %d)", who, ld_f, VE); return DSP_EINVAL; }
     if (!features || !out || !pad || !n || out == features) { set_error("%s: null or aliased pointer", who); return DSP_EINVAL; }
-    if (((((uintptr_t)features) | ((uintptr_t)out)) & 15) || (((uintptr_t)n) & 7)) {
+    if (!on16(features, out) || (((uintptr_t)n) & 7)) {
         set_error("%s: features and out must be 16-byte aligned, n 8-byte", who); return DSP_EINVAL;
     }
     const int tiles = (W + PF_TILE_W - 1) / PF_TILE_W;
@@ -173,8 +174,8 @@ extern "C" int dsp_path_features_bwd(const void* dy, long dy_sb, long dy_sr, con
     if (rc) return rc;
     if (B == 0) return DSP_OK;
     const int VE = 16 / elem_size(dtype);
-    if (!dfeatures || ((uintptr_t)dfeatures & 15) || dfeatures == dy) { set_error("%s: dfeatures must be non-null, 16-byte aligned, not dy", who); return DSP_EINVAL; }
-    if (W > 0 && (!dy || ((uintptr_t)dy & 15) || dy_sb < 0 || dy_sr < 0 || (dy_sb % VE) || (dy_sr % VE))) {
+    if (!dfeatures || !on16(dfeatures) || dfeatures == dy) { set_error("%s: dfeatures must be non-null, 16-byte aligned, not dy", who); return DSP_EINVAL; }
+    if (W > 0 && (!dy || !on16(dy) || dy_sb < 0 || dy_sr < 0 || (dy_sb % VE) || (dy_sr % VE))) {
         set_error("%s: dy must be non-null and 16-byte aligned, its batch and row strides %ld, %ld non-negative multiples of %d", who, dy_sb,
                   dy_sr, VE);
         return DSP_EINVAL;

@@ -23,6 +23,7 @@
 //
 // The dropout mask is never stored: element e = ((b H + h) T + i) Tp + j, Tp = T rounded up to a multiple of 4, of the rule in philox.h.
 #include "common.h"
+#include "host_gates.h"
 #include "philox.h"
 #include "ra_frag.h"
 #include "../../include/daspeech_decode.h"
@@ -462,24 +463,21 @@ extern "C" size_t dsp_relpos_attention_train_workspace_bytes(int B, int T, int H
 {
     if (B <= 0 || T <= 0 || H <= 0) return 0;
     const size_t floats = 2 * ra_part_bias_floats(B, T, H) + (size_t)B * (size_t)(2L * T - 1) * (size_t)H * 64;
-    return (floats * sizeof(float) + 15) & ~(size_t)15;
+    return a16(floats * sizeof(float));
 }
 
 static int ra_fwd(const char* who, const void* q, const void* k, const void* v, long ld, const void* pos, const void* bias_u, const void* bias_v,
                   const unsigned char* pad_mask, float keep_scale, unsigned int thr, uint64_t seed, uint64_t offset, const uint64_t* rng_state,
                   void* out, float* lse, int act_dtype, int param_dtype, int B, int T, int H, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = ra_check(who, act_dtype, param_dtype, B, T, H, ld);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!q || !k || !v || !pos || !bias_u || !bias_v || !out || !lse || out == q || out == k || out == v || out == pos) {
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
     if (thr > (1u << 24)) { set_error("%s: thr %u above 2^24", who, thr); return DSP_EINVAL; }
-    if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)pos) | ((uintptr_t)bias_u) | ((uintptr_t)bias_v) | ((uintptr_t)out) |
-         ((uintptr_t)lse)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
+    DSP_GATE(tensors16_gate(who, q, k, v, pos, bias_u, bias_v, out, lse));
     const unsigned grid = (unsigned)((long)B * H * ((T + 31) / 32));
     hipStream_t st = as_stream(stream);
     RA_DISPATCH(act_dtype, hipLaunchKernelGGL((ra_fwd_kernel<E>), dim3(grid), dim3(64), 0, st, (const E*)q, (const E*)k, (const E*)v, ld, (const E*)pos,
@@ -511,31 +509,19 @@ static int ra_bwd(const char* who, const void* dout, const void* q, const void* 
                   uint64_t seed, uint64_t offset, const uint64_t* rng_state, void* dq, void* dk, void* dv, void* dpos, void* dbias_u, void* dbias_v,
                   void* workspace, size_t workspace_bytes, int act_dtype, int param_dtype, int B, int T, int H, dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int rc = ra_check(who, act_dtype, param_dtype, B, T, H, ld);
     if (rc) return rc < 0 ? rc : DSP_OK;
     if (!dq && !dk && !dv && !dpos && !dbias_u && !dbias_v) return DSP_OK;
     if (!dout || !q || !k || !v || !pos || !bias_u || !bias_v || !out || !lse) { set_error("%s: null pointer", who); return DSP_EINVAL;}
     const void* ins[] = {dout, q, k, v, pos, bias_u, bias_v, out, lse, pad_mask};
     void* outs[] = {dq, dk, dv, dpos, dbias_u, dbias_v};
-    for (int a = 0; a < 6; ++a) {
-        if (!outs[a]) continue;
-        for (const void* in : ins)
-            if (outs[a] == in) { set_error("%s: an output aliases an input", who); return DSP_EINVAL; }
-        for (int c = a + 1; c < 6; ++c)
-            if (outs[a] == outs[c]) { set_error("%s: two outputs alias", who); return DSP_EINVAL; }
-    }
+    DSP_GATE(alias_gate(who, outs, 6, ins, 10, "an output aliases an input", "two outputs alias"));
     if (thr > (1u << 24)) { set_error("%s: thr %u above 2^24", who, thr); return DSP_EINVAL; }
-    if ((((uintptr_t)dout) | ((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)pos) | ((uintptr_t)bias_u) | ((uintptr_t)bias_v) |
-         ((uintptr_t)out) | ((uintptr_t)lse) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv) | ((uintptr_t)dpos) | ((uintptr_t)dbias_u) |
-         ((uintptr_t)dbias_v)) & 15) {
-        set_error("%s: tensors must be 16-byte aligned", who); return DSP_EINVAL;
-    }
-    const bool need_ws = dpos || dbias_u || dbias_v;
-    if (need_ws && (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_relpos_attention_train_workspace_bytes(B, T, H))) {
-        set_error("%s: workspace of dsp_relpos_attention_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    DSP_GATE(tensors16_gate(who, dout, q, k, v, pos, bias_u, bias_v, out, lse, dq, dk, dv, dpos, dbias_u, dbias_v));
+    if (dpos || dbias_u || dbias_v)
+        DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_relpos_attention_train_workspace_bytes(B, T, H),
+                                "dsp_relpos_attention_train_workspace_bytes"));
     const int nI = (T + 31) / 32, nR = (2 * T - 1 + 31) / 32, C = H * 64;
     float* part_u = (float*)workspace;
     float* part_v = part_u ? part_u + ra_part_bias_floats(B, T, H) : nullptr;

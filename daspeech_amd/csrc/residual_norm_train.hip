@@ -16,6 +16,7 @@
 // writes one fp32 partial per column for its chunk of DSP_RESNORM_CHUNK_ROWS rows, and rn_bwd_merge_kernel adds the chunks in ASCENDING
 // order.  No float atomics, no hand-off between workgroups inside a launch: same inputs, same bits.
 #include "common.h"
+#include "host_gates.h"
 #include "philox.h"
 #include "../../include/daspeech_decode.h"
 
@@ -287,7 +288,7 @@ static long rn_chunks(long R) { return (R + RN_CHUNK - 1) / RN_CHUNK; }
 // what both entry points check; 1: nothing to do (R == 0), 0: go on, < 0: refused
 static int rn_check(const char* who, int act_dtype, int param_dtype, long R, int C, const uint64_t* rng_state)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     const int es = elem_size(act_dtype);
     if (!es || !elem_size(param_dtype) || (param_dtype != act_dtype && param_dtype != DSP_F32)) {
         set_error("%s: dtype codes %d (h, residual, s, y and their gradients) / %d (gamma, beta, bias: the same, or fp32)", who, act_dtype, param_dtype);
@@ -326,7 +327,7 @@ using namespace dsp;
 extern "C" size_t dsp_resnorm_train_workspace_bytes(int64_t R, int C)
 {
     if (R <= 0 || C < 1) return 0;
-    return ((size_t)rn_chunks((long)R) * 3 * (size_t)C * sizeof(float) + 15) & ~(size_t)15;
+    return a16((size_t)rn_chunks((long)R) * 3 * (size_t)C * sizeof(float));
 }
 
 static int rn_fwd(const char* who, const void* h, const void* residual, const void* bias, const void* gamma, const void* beta, float eps,
@@ -339,8 +340,7 @@ static int rn_fwd(const char* who, const void* h, const void* residual, const vo
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
     if (thr > (1u << 24)) { set_error("%s: thr %u above 2^24", who, thr); return DSP_EINVAL; }
-    if ((((uintptr_t)h) | ((uintptr_t)residual) | ((uintptr_t)bias) | ((uintptr_t)gamma) | ((uintptr_t)beta) | ((uintptr_t)(h ? s : nullptr)) |
-         ((uintptr_t)y)) & 15 || ((uintptr_t)stats & 7)) {
+    if (!on16(h, residual, bias, gamma, beta, h ? s : nullptr, y) || ((uintptr_t)stats & 7)) {
         set_error("%s: tensors must be 16-byte aligned (stats: 8)", who); return DSP_EINVAL;
     }
     int W, NG;
@@ -384,15 +384,11 @@ static int rn_bwd(const char* who, const void* dy, const void* ds, const void* s
         set_error("%s: null or aliased pointer", who); return DSP_EINVAL;
     }
     if (thr > (1u << 24)) { set_error("%s: thr %u above 2^24", who, thr); return DSP_EINVAL; }
-    if ((((uintptr_t)dy) | ((uintptr_t)ds) | ((uintptr_t)s) | ((uintptr_t)gamma) | ((uintptr_t)dh) | ((uintptr_t)dresidual)) & 15 ||
-        ((uintptr_t)stats & 7)) {
+    if (!on16(dy, ds, s, gamma, dh, dresidual) || ((uintptr_t)stats & 7)) {
         set_error("%s: tensors must be 16-byte aligned (stats: 8)", who); return DSP_EINVAL;
     }
     const bool sums = dbias || dgamma || dbeta;
-    if (sums && (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_resnorm_train_workspace_bytes(R, C))) {
-        set_error("%s: workspace of dsp_resnorm_train_workspace_bytes bytes (16-byte aligned) needed", who);
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
-    }
+    if (sums) DSP_GATE(workspace_gate(who, workspace, workspace_bytes, dsp_resnorm_train_workspace_bytes(R, C), "dsp_resnorm_train_workspace_bytes"));
     int W, NG;
     rn_plan(C / (16 / elem_size(act_dtype)), W, NG);
     const long nchunks = rn_chunks((long)R);
@@ -427,7 +423,7 @@ extern "C" int dsp_resnorm_train_bwd_state(const void* dy, const void* ds, const
 static int rn_keep_mask(const char* who, uint64_t seed, uint64_t offset, const uint64_t* rng_state, unsigned int thr, unsigned char* out, int64_t n,
                         dsp_stream_t stream)
 {
-    if ((uintptr_t)rng_state & 7) { set_error("%s: rng_state must be 8-byte aligned", who); return DSP_EINVAL; }
+    DSP_GATE(rng_state_gate(who, rng_state));
     if (n < 0 || n > (1L << 36) || thr > (1u << 24)) { set_error("%s: bad arguments n=%ld thr=%u", who, (long)n, thr); return DSP_EINVAL; }
     if (n == 0) return DSP_OK;
     if (!out) { set_error("%s: null pointer", who); return DSP_EINVAL; }

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void lr_bwd_kernel(const T* __restrict__ g, co
     }
 }
 
-static size_t eg_int_bytes(int64_t n, int K) { return (((size_t)3 * K + 1 + (size_t)n) * sizeof(int32_t) + 15) & ~(size_t)15; }
+static size_t eg_int_bytes(int64_t n, int K) { return a16(((size_t)3 * K + 1 + (size_t)n) * sizeof(int32_t)); }
 static long eg_max_chunks(int64_t n, int K) { return (long)((n + EG_CHUNK - 1) / EG_CHUNK) + K; }
 
 }  // namespace dsp
@@ -155,9 +155,9 @@ extern "C" int dsp_embed_grad(const void* grad_out, int dtype, const int32_t* id
         return DSP_OK;
     }
     if (!grad_out || !idx) { set_error("embed_grad: null pointer"); return DSP_EINVAL; }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_embed_grad_workspace_bytes(n, nb, C)) {
+    if (!workspace || !on16(workspace) || workspace_bytes < dsp_embed_grad_workspace_bytes(n, nb, C)) {
         set_error("embed_grad: workspace of %zu bytes (16-byte aligned) needed, see dsp_embed_grad_workspace_bytes", dsp_embed_grad_workspace_bytes(n, nb, C));
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
+        return workspace && on16(workspace) ? DSP_ENOSPC : DSP_EINVAL;
     }
     int32_t* counts = (int32_t*)workspace;
     int32_t* offs = counts + K;

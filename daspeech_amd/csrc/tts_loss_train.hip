@@ -18,6 +18,7 @@
 //
 // All of it is row traffic of a few MB: 16-byte accesses per lane where C, the strides and the pointers allow, a scalar path otherwise.
 #include "common.h"
+#include "host_gates.h"
 #include "../../include/daspeech_decode.h"
 
 namespace dsp {
@@ -277,7 +278,7 @@ extern "C" size_t dsp_tts_loss_workspace_bytes(int B, int F_, int N)
 {
     if (B <= 0) return 0;
     const size_t n = 2 * (size_t)tl_chunks(F_ > 0 ? (long)B * F_ : 0, TL_ROWS) + 3 * (size_t)tl_chunks(N > 0 ? (long)B * N : 0, TL_ELEMS);
-    return (n * sizeof(float) + 15) & ~(size_t)15;
+    return a16(n * sizeof(float));
 }
 
 extern "C" int dsp_tts_loss_fwd(const void* feat_out, long fo_sb, long fo_sr, const void* feat_post, long fp_sb, long fp_sr,
@@ -308,9 +309,9 @@ extern "C" int dsp_tts_loss_fwd(const void* feat_out, long fo_sb, long fo_sr, co
         (((uintptr_t)audio_lens | (uintptr_t)src_lens) & (len64 ? 7 : 3)) || ((uintptr_t)durations & (dur64 ? 7 : 3))) {
         set_error("%s: a pointer is off the grid of its element type", who); return DSP_EINVAL;
     }
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < dsp_tts_loss_workspace_bytes(B, F_, N)) {
+    if (!workspace || !on16(workspace) || workspace_bytes < dsp_tts_loss_workspace_bytes(B, F_, N)) {
         set_error("%s: workspace of %zu bytes (16-byte aligned) needed, see dsp_tts_loss_workspace_bytes", who, dsp_tts_loss_workspace_bytes(B, F_, N));
-        return workspace && !((uintptr_t)workspace & 15) ? DSP_ENOSPC : DSP_EINVAL;
+        return workspace && on16(workspace) ? DSP_ENOSPC : DSP_EINVAL;
     }
     const void* vp[3] = {feat_out, target, feat_post};
     const bool vec = tl_vec(es, C, vp, strides, 3, 6);
